@@ -132,6 +132,12 @@ def parse():
     ap.add_argument("--launch-timeout", type=float, default=1500.,
                     help="`--gpus N` without a launcher starts the N ranks itself; seconds after "
                          "which it ends them and fails")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step "
+                         "(the arrays its caller receives: gamma, the statistics, lambda where the step "
+                         "has an M-step) as DIR/<name>.npy, float64, at most 64 MB in all; the timed "
+                         "regions then start at the first mini-batch of the stream, so that runs with "
+                         "the same arguments compute on the same inputs")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="exercise the rank launch only (no torch, no GPU): CPU test of the path")
     return ap.parse_args()
@@ -268,6 +274,46 @@ def launch_ranks(n, argv, timeout_s):
         return 1
     print(result, flush=True)
     return 0
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def lambda_of(L, model, K, V):
+    from trlda_amd import _ffi
+    lam = np.empty((K, V), order="F")
+    _ffi.check(L.trlda_model_get_lambda(model, lam))
+    return lam
+
+
+def dump_outputs(args, rank, last, out_sets, lanes, exchange, collective, get_lambda, B, K, V):
+    """--dump-outputs: the arrays the timed path's last step (`last`) handed its caller, read after the
+    fence that closed the last timed region, written by rank 0 as DIR/<name>.npy (float64).  An array
+    beyond its share of DUMP_BUDGET_BYTES is written as a fixed sample of its elements (seeded, the
+    same positions in every run; flattened in column-major order).  Returns what was written."""
+    g_out, s_out, _ = out_sets[last & 1 if lanes > 1 else 0]
+    outs = {"gamma": g_out.cpu().numpy().reshape(B, K).T}             # K x B, as do_e_step returns it
+    if exchange != "factors":                                         # (the factor path's M-step reads them
+        outs["sstats"] = s_out.cpu().numpy().reshape(K, V, order="F")  # in the kernel: none are returned)
+    if collective:
+        outs["lambda"] = get_lambda()                                 # after the step's M-step
+    if rank != 0:
+        return None
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(outs)
+    written = {}
+    for name, a in outs.items():
+        a = np.asarray(a, dtype=np.float64)
+        info = {"shape": list(a.shape), "dtype": "float64", "sampled": None}
+        if a.nbytes > share:
+            n = share // a.itemsize
+            pick = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            a = a.ravel(order="F")[pick]
+            info["sampled"] = {"elements": int(n), "of": int(np.prod(info["shape"])), "seed": 0}
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        written[name] = info
+    return {"dir": args.dump_outputs, "step": int(last), "mini_batch": int(last % args.num_batches),
+            "arrays": written}
 
 
 def main():
@@ -715,6 +761,18 @@ def main():
                 "settle_last_ms_per_step": round(1e3 * last / chunk, 5)}
 
     settled = settle()
+    if args.dump_outputs:
+        # untimed steps up to the start of the stream of mini-batches: the last timed step is then
+        # the same mini-batch in every run, however many steps the settle phase took; N > 1: lambda
+        # back to its initial value, so that the M-steps of the timed regions start from it
+        pad = -pos[0] % args.num_batches
+        for i in range(pos[0], pos[0] + pad):
+            step(i)
+        pos[0] += pad
+        settled["aligned_steps"] = pad
+        if collective:
+            fence()
+            _ffi.check(L.trlda_model_set_lambda(model, lam))
     def lane_report():
         two, one = C.c_double(), C.c_double()
         L.trlda_model_lane_timing(model, C.byref(two), C.byref(one))
@@ -724,6 +782,10 @@ def main():
     # the timed region, `--repeats` times back to back: the median is the result (20 steps of
     # 40 us are under a millisecond -- one scheduling hiccup moves a single sample by 10 %)
     samples = sorted(timed() for _ in range(max(1, args.repeats)))
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args, rank, pos[0] - 1, out_sets, lanes[0], exchange, collective,
+                              lambda: lambda_of(L, model, K, V), B, K, V)
     # (did the last launch of a timed region carry the statistics of an earlier step? -- asked here:
     # the first launches after a fence never do)
     carried_flag = bool(deferred and L.trlda_model_last_deferred(model) & 2)
@@ -1355,6 +1417,7 @@ def main():
         "cpu_baseline": cpu_baseline,
         "parity": parity,
         "update_parameters": update_rates,
+        "dump_outputs": dumped,
     }
     if collective and not vworld:
         dist.destroy_process_group()

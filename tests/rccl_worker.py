@@ -1,5 +1,6 @@
 """One rank of a REAL data-parallel run: one process per GPU, torch.distributed backend "nccl"
-(RCCL over xGMI), the sharded models of trlda_amd/distributed.py on top.  Test infrastructure for
+(RCCL over xGMI), the sharded models of trlda_amd/distributed.py on top -- or, with "backend":
+"gloo" in the config, ranks that share one GPU over a gloo group.  Test infrastructure for
 tests/test_gpu_rccl.py, which starts `world` of these (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in
 the environment, as torch.distributed.run would).
 
@@ -29,7 +30,14 @@ def main():
     from trlda_amd.utils.synthetic import make_corpus
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
-    dist.init_process_group("nccl", device_id=device)
+    # "gloo": the ranks share one GPU (RCCL refuses two ranks on a device) and the group moves host
+    # memory -- the sharded models compose their exchanges from torch.distributed's collectives
+    backend = cfg.get("backend", "nccl")
+    if backend == "nccl":
+        dist.init_process_group("nccl", device_id=device)
+    else:
+        dist.init_process_group(backend)
+    group_dev = device if backend == "nccl" else torch.device("cpu")
     out = {}
     try:
         K, V, D = cfg["K"], cfg["V"], cfg["D"]
@@ -62,10 +70,10 @@ def main():
                 paths.append(m.last_path)
             agree = m.replicas_agree()
             # bitwise: every rank's lambda against rank 0's
-            lam = torch.from_numpy(np.ascontiguousarray(m.lambdas)).to(device)
+            lam = torch.from_numpy(np.ascontiguousarray(m.lambdas)).to(group_dev)
             ref = lam.clone()
             dist.broadcast(ref, src=0)
-            same = torch.tensor([int(torch.equal(lam, ref))], device=device)
+            same = torch.tensor([int(torch.equal(lam, ref))], device=group_dev)
             dist.all_reduce(same, op=dist.ReduceOp.MIN)
             if rank == 0:
                 out["run%d_lambda" % r] = m.lambdas

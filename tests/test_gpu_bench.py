@@ -138,3 +138,29 @@ def test_bench_forced_distributed_line(hip_lib):
     assert j["n_gpus"] == 1 and j["rccl_ranks"] == 1
     same = j["same_step_n1"]
     assert abs(same["ms_per_step"] - j["ms_per_step"]) < 0.4 * j["ms_per_step"]
+
+
+def test_bench_dump_outputs_repeat_from_run_to_run(hip_lib, tmp_path):
+    """`--dump-outputs DIR`: what the last timed step computed -- gamma (K x B) and the statistics
+    (K x V) of one mini-batch -- the same bit for bit in two runs with the same arguments (however long
+    their settle phases took), the statistics holding the mini-batch's word counts."""
+    import numpy as np
+    from trlda_amd.utils.synthetic import SEED_BASE, make_corpus
+    got = []
+    for run in ("a", "b"):
+        j = run_bench("--no-cpu-baseline", "--no-update-rates", "--headline-only",
+                      "--dump-outputs", str(tmp_path / run))
+        d = j["dump_outputs"]
+        assert j["steps"] == 10 and sorted(d["arrays"]) == ["gamma", "sstats"]
+        assert d["step"] % j["config"]["num_batches"] == d["mini_batch"] == 3 * 10 - 1
+        got.append({n: np.load(str(tmp_path / run / (n + ".npy"))) for n in d["arrays"]})
+    K, V, B = 100, 7000, 200
+    gamma, sstats = got[0]["gamma"], got[0]["sstats"]
+    assert gamma.dtype == sstats.dtype == np.float64
+    assert gamma.shape == (K, B) and sstats.shape == (K, V)
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n]), n
+    assert np.all(np.isfinite(gamma)) and np.all(gamma > 0)
+    _, ids, cnts = make_corpus(B, V, seed=SEED_BASE + 1 + d["mini_batch"], mean_unique=100)
+    assert abs(sstats.sum() - cnts.sum()) < 1e-9 * cnts.sum()
+    assert np.array_equal(np.flatnonzero(sstats.sum(axis=0)), np.unique(ids))

