@@ -102,6 +102,20 @@ int trlda_estep(int K, int V, int B,
                 double *gamma, double *sstats,
                 int max_iter, double threshold, int32_t *iters_out, int device);
 
+/*
+ * LDA::updateVariables(documents, latents, parameters) with inferenceMethod == GIBBS:
+ * src/lda.cpp:142-156 -> LDA::updateVariablesGibbs, src/lda.cpp:224-293 (one-shot
+ * trlda_model_gibbs_host; the drop-in boundary of INTEGRATION.md).
+ *   theta        in (use_latents != 0): initial theta (K x B); out: sampled theta
+ *   sstats       out: K x V statistics, 1 / num_samples per token and sample
+ * Uploads, runs the HIP kernels, downloads, synchronises.
+ */
+int trlda_gibbs(int K, int V, int B,
+                const int32_t *indptr, const int32_t *ids, const int32_t *cnts,
+                const double *lambda, const double *alpha,
+                double *theta, int use_latents, double *sstats,
+                int num_samples, int burn_in, int device);
+
 /* lambda = (1-rho) lambda' + rho (eta + scale * sstats): src/onlinelda.cpp:99-100 and
  * :108-109 (scale = D / B); src/batchlda.cpp:60 is the rho = 1, scale = 1 case. */
 int trlda_mstep_blend(int K, int V, double rho, double eta, double scale,
@@ -414,6 +428,39 @@ int trlda_model_estep_host(trlda_model *model, const trlda_batch *batch,
 int trlda_model_lower_bound(trlda_model *model, const trlda_batch *batch, double *gamma,
                             double eta, double factor, int max_iter, double threshold,
                             double *bound_out);
+
+/* LDA::updateVariablesGibbs (src/lda.cpp:224-293), reached from python/src/ldainterface.cpp:311-390
+ * with inference_method='GIBBS': collapsed Gibbs sampling of the batch's topic assignments on the
+ * device (csrc/gibbs_kernels.h), one wave64 per document, K <= 1024 (more: TRLDA_ERR_ARG).
+ *   theta0_dev  K x B initial theta (lda.cpp:229-230), or NULL: Dirichlet(1) per column drawn from
+ *               the key (lda.cpp:123-128 draws sampleDirichlet from the host stream)
+ *   theta_dev   out: K x B, Dirichlet(alpha + topic counts) of the final state (lda.cpp:288)
+ *   sstats_dev  out: K x V, tokens per (topic, word) summed over the num_samples sweeps after
+ *               burn_in, times 1 / num_samples (lda.cpp:278-284; not multiplied by exp E[log beta])
+ *   key         the 64-bit Philox4x32-10 key: every draw is a function of (key, document index,
+ *               token or topic, sweep, purpose) -- the counter layout is pinned in gibbs_kernels.h
+ * Deviations from the reference: the init reads theta0's column i, not j
+ * (lda.cpp:254); Philox instead of rand() / mt19937; sstats as exact counts scaled once;
+ * Marsaglia-Tsang gamma draws in log space for theta.  A histogram that sums to 0 or is not
+ * finite fails the call with "Something went wrong while sampling from histogram."
+ * (utils.cpp:198).  num_samples or burn_in < 0: TRLDA_ERR_ARG.  Flushes the deferred work first
+ * and uses workspaces of its own: trlda_model_get_sstats, the deferred statistics, the lanes and
+ * the prefetch announcements keep what they held for the VI path.  Those workspaces -- the K x V
+ * double table, K x V uint32 counts, a uint16 per token of the largest batch so far (and, for
+ * trlda_model_gibbs_host, K x B and K x V double staging) -- stay allocated after the first Gibbs
+ * call until trlda_model_destroy: about 1 GB at K = 500, V = 100 000.  Synchronises. */
+int trlda_model_gibbs(trlda_model *model, const trlda_batch *batch, const double *theta0_dev,
+                      double *theta_dev, double *sstats_dev, int num_samples, int burn_in,
+                      uint64_t key);
+
+/* Host-pointer convenience around trlda_model_gibbs: theta (K x B host) is the initial theta when
+ * use_latents != 0 (else Dirichlet(1) is drawn on the device) and receives the sampled theta;
+ * sstats (K x V host) receives the statistics.  The key is the next two draws of the library's
+ * libc-compatible stream (first draw: low 32 bits).  Those draws are rand()'s 31-bit values, so
+ * bits 31 and 63 of the key are always 0: 62 bits vary.  trlda_seed() makes a call reproducible and
+ * successive calls differ.  src/lda.cpp:224-293, python/src/ldainterface.cpp:311-390. */
+int trlda_model_gibbs_host(trlda_model *model, const trlda_batch *batch, double *theta, int use_latents,
+                           double *sstats, int num_samples, int burn_in);
 
 /* model.lambda = (1-rho) lambda' + rho (eta + scale * sstats), all device pointers.
  * src/onlinelda.cpp:99-100, :108-109; src/batchlda.cpp:60 (rho = 1, scale = 1). */
@@ -786,6 +833,10 @@ int trlda_debug_fold16(int device, const double *in, double *out16, double *out4
  * phinorm per entry in word order, 3: the sstats buffer of the host entry points (K x V).
  * tests/fuzz_estep.py --passes uses it to say WHICH input of the statistics went wrong. */
 int trlda_debug_peek(trlda_model *model, int which, double *host_out, size_t count);
+/* test hook: the normalised exp E[log beta] table the model's last Gibbs call sampled from
+ * (K x V; only that batch's words are filled) -- the tests' restatement of the sampler
+ * (tests/gibbs_host.py) reads the same numbers the kernel did */
+int trlda_debug_gibbs_table(trlda_model *model, double *host_out);
 /* diagnostics: the s_memrealtime stamps of the model's last merged launch, 3 x 1024 values
  * (TRLDA_MERGED_STAMPS=1; tools/merged_stamps.py) */
 int trlda_debug_merged_stamps(trlda_model *model, unsigned long long *host_out);

@@ -103,6 +103,11 @@ _SIGNATURES = {
     "trlda_model_lane_steps": (C.c_longlong, [vp]),
     "trlda_model_get_lane_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "trlda_model_estep_host": (C.c_int, [vp, vp, f64p, f64p, C.c_int, C.c_double, vp]),
+    "trlda_model_gibbs": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64]),
+    "trlda_model_gibbs_host": (C.c_int, [vp, vp, f64p, C.c_int, f64p, C.c_int, C.c_int]),
+    "trlda_gibbs": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, f64p, f64p, f64p, C.c_int,
+                              f64p, C.c_int, C.c_int, C.c_int]),
+    "trlda_debug_gibbs_table": (C.c_int, [vp, f64p]),
     "trlda_model_blend": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_double]),
     "trlda_model_tr_init": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),
     "trlda_model_wordcounts": (C.c_int, [vp, vp, vp]),

@@ -64,6 +64,10 @@ void rng_speculation_cancel_if(uint64_t token);      // only if that one is the 
 // the process generator: its window (oldest word first), and moving it on by `draws`
 void rng_current_window(uint32_t (&w)[31]);
 void rng_advance(uint64_t draws);
+// a 64-bit key from the next two draws of the stream: the first the low half, the second the
+// high half (the Gibbs sampler's Philox key, trlda_model_gibbs_host).  The draws are 31-bit, so
+// bits 31 and 63 are 0: 62 bits vary.
+uint64_t rng_draw_key();
 // M[l][d - 1] = A^(d 16^l L), l < levels, d = 1 .. 15 (31 x 31 words each), once per L
 const std::vector<uint32_t> &rng_level_matrices(int L, int levels);
 

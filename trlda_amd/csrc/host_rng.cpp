@@ -223,6 +223,14 @@ void rng_speculation_cancel()
 
 void rng_current_window(uint32_t (&w)[31]) { rng_to_window(g_rng, w); }
 
+uint64_t rng_draw_key()
+{
+    rng_speculation_cancel();
+    const uint64_t lo = g_rng.next();
+    const uint64_t hi = g_rng.next();
+    return lo | (hi << 32);
+}
+
 void rng_advance(uint64_t draws)
 {
     uint32_t w[31];

@@ -43,6 +43,7 @@
 #include "eb_kernels.h"
 #include "rng_kernels.h"
 #include "dp_kernels.h"
+#include "gibbs_kernels.h"
 
 namespace {
 
@@ -584,6 +585,26 @@ struct trlda_model {
     size_t ev_used = 0;                // events recorded since the last collect
     double usec_sum[5] = {0, 0, 0, 0, 0};
     int64_t usec_cnt[5] = {0, 0, 0, 0, 0};
+    // Gibbs sampling (gibbs_kernels.h, trlda_model_gibbs): workspaces of its own, so that a Gibbs
+    // call leaves whatever the VI path keeps between calls -- exp(psi(lambda)) left behind, row sums,
+    // prefetched preambles, deferred statistics -- as it was
+    struct {
+        double *eeb = nullptr, *partial = nullptr, *psi_sum = nullptr;
+        size_t cap_eeb = 0, cap_partial = 0, cap_psi = 0;
+        uint32_t *cnt = nullptr;                // K x V, zero between calls (gibbs_finish_kernel)
+        size_t cap_cnt = 0;
+        uint16_t *z = nullptr;
+        size_t cap_z = 0;
+        int64_t *tokens = nullptr, *tok_off = nullptr;
+        int32_t *order = nullptr;
+        size_t cap_tokens = 0, cap_tok_off = 0, cap_order = 0;
+        int *flag = nullptr;
+        double *theta_in = nullptr, *theta = nullptr, *sstats = nullptr;   // trlda_model_gibbs_host's
+        size_t cap_theta_in = 0, cap_theta = 0, cap_sstats = 0;
+        // the plan (token offsets, document order) of the batch it was made for
+        uint64_t plan_batch = 0;
+        int64_t total_tokens = 0;
+    } gibbs;
 };
 
 namespace {
@@ -3791,6 +3812,10 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->upd_partial); (void)hipFree(m->ada_gradient); (void)hipFree(m->reduce_out);
         (void)hipFree(m->carry_out); (void)hipFree(m->upd_groups); (void)hipFree(m->group_counter);
         (void)hipFree(m->iters); (void)hipFree(m->rng_win); (void)hipFree(m->rng_vbuf);
+        (void)hipFree(m->gibbs.eeb); (void)hipFree(m->gibbs.partial); (void)hipFree(m->gibbs.psi_sum);
+        (void)hipFree(m->gibbs.cnt); (void)hipFree(m->gibbs.z); (void)hipFree(m->gibbs.tokens);
+        (void)hipFree(m->gibbs.tok_off); (void)hipFree(m->gibbs.order); (void)hipFree(m->gibbs.flag);
+        (void)hipFree(m->gibbs.theta_in); (void)hipFree(m->gibbs.theta); (void)hipFree(m->gibbs.sstats);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -4837,6 +4862,264 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     pw_pb -= (double)K * V * std::lgamma(eta) - lg_lambda;                 // :357
     *bound_out = pw_pb + factor * pz + factor * ptheta;                    // :359
     return TRLDA_OK;
+}
+
+// ---- Gibbs sampling: LDA::updateVariablesGibbs, src/lda.cpp:224-293 (gibbs_kernels.h) ----
+}  // extern "C"
+
+namespace {
+
+
+// token offsets and the longest-first document order of batch `b`, made once per batch (the
+// counts live on the device only: one small launch, one download)
+int gibbs_plan(trlda_model *m, const trlda_batch *b)
+{
+    auto &g = m->gibbs;
+    if (g.plan_batch == b->id)
+        return TRLDA_OK;
+    g.plan_batch = 0;
+    const int B = b->B;
+    const size_t nb = (size_t)std::max(B, 1);
+    int rc = grow(&g.tokens, &g.cap_tokens, nb);
+    if (!rc) rc = grow(&g.tok_off, &g.cap_tok_off, nb);
+    if (!rc) rc = grow(&g.order, &g.cap_order, nb);
+    if (rc)
+        return rc;
+    std::vector<int64_t> tok((size_t)B), off((size_t)B);
+    std::vector<int32_t> order((size_t)B);
+    if (B > 0) {
+        hipLaunchKernelGGL(trlda::gibbs_tokens_kernel<256>, dim3((B + 255) / 256), dim3(256), 0, m->stream, B,
+                           b->indptr, b->cnts, g.tokens);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(tok.data(), g.tokens, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost,
+                               m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    int64_t total = 0;
+    for (int d = 0; d < B; ++d) {
+        off[(size_t)d] = total;
+        total += tok[(size_t)d];
+    }
+    // (a token's index within its document is a 32-bit Philox counter word, and the statistics
+    // are 32-bit counts)
+    if (total > (int64_t)UINT32_MAX)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling: the batch holds more than 2^32 - 1 tokens");
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(),
+                     [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
+    rc = grow(&g.z, &g.cap_z, (size_t)std::max<int64_t>(total, 1));
+    if (rc)
+        return rc;
+    if (B > 0) {
+        HIP_TRY(hipMemcpyAsync(g.tok_off, off.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice,
+                               m->stream));
+        HIP_TRY(hipMemcpyAsync(g.order, order.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice,
+                               m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));       // (the host vectors go out of scope)
+    }
+    g.total_tokens = total;
+    g.plan_batch = b->id;
+    return TRLDA_OK;
+}
+
+// e = exp(psi(lambda) - psi(rowsum(lambda))) of the batch's active words into m->gibbs.eeb: the
+// non-fused preamble of the E-step (estep_kernels.h, kernels 1 and 2) on buffers of its own.  The
+// table is normalised -- the fused variants' exp(psi(lambda)) without the topic factors would
+// change the conditional -- and the row sums are formed from lambda itself, not taken from what
+// an update left behind, so that nothing of the VI path's state is read or resolved here.
+int gibbs_preamble(trlda_model *m, const trlda_batch *b)
+{
+    using namespace trlda;
+    auto &g = m->gibbs;
+    const int K = m->K, V = m->V;
+    const size_t KV = (size_t)K * V;
+    const bool big = KV >= ((size_t)1 << 22);
+    int G = std::min(big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, std::max(1, V / 32));
+    const int wpb = (V + G - 1) / G;
+    G = (V + wpb - 1) / wpb;
+    int rc = grow(&g.eeb, &g.cap_eeb, KV);
+    if (!rc) rc = grow(&g.partial, &g.cap_partial, ((size_t)G + 1) * K);
+    if (!rc) rc = grow(&g.psi_sum, &g.cap_psi, 3 * (size_t)K);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K, V,
+                       wpb, m->lambda, g.partial);
+    HIP_TRY(hipGetLastError());
+    const double *partial_in = g.partial;
+    int G_in = G;
+    if (G > kRowsumBlocks) {
+        double *combined = g.partial + (size_t)G * K;
+        hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>, dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
+                           dim3(kDenseThreads), 0, m->stream, K, G, g.partial, combined);
+        HIP_TRY(hipGetLastError());
+        partial_in = combined;
+        G_in = 1;
+    }
+    if (b->n_active <= 0)
+        return TRLDA_OK;
+    constexpr int TE = 1024;
+    const size_t total = (size_t)K * (size_t)b->n_active;
+    const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
+    const size_t lds = (size_t)K * 9 * sizeof(double);
+    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, G_in, m->lambda,
+                       partial_in, g.psi_sum, g.eeb, b->active);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+template <int KPL>
+int gibbs_launch_docs(trlda_model *m, const trlda::GibbsArgs &a)
+{
+    const size_t lds = (size_t)trlda::kGibbsWaves * (size_t)a.K * (sizeof(double) + sizeof(int));
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::gibbs_docs_kernel<KPL>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::gibbs_docs_kernel<KPL>, dim3((a.B + trlda::kGibbsWaves - 1) / trlda::kGibbsWaves),
+                       dim3(trlda::kGibbsWaves * trlda::kWave), lds, m->stream, a);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the whole call on the model's stream; waits for the device at the end (the sampling-failure flag)
+int gibbs_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, double *theta_dev,
+                        double *sstats_dev, int num_samples, int burn_in, uint64_t key)
+{
+    using namespace trlda;
+    const int K = m->K, V = m->V, B = b->B;
+    const size_t KV = (size_t)K * V;
+    if (b->V != V)
+        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    if (K > kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling supports at most 1024 topics");
+    if (num_samples < 0 || burn_in < 0 || (long long)num_samples + burn_in > INT32_MAX)
+        return fail(TRLDA_ERR_ARG, "num_samples and burn_in should not be negative");
+    if (!sstats_dev || (B > 0 && !theta_dev))
+        return fail(TRLDA_ERR_ARG, "NULL theta / sstats");
+    int rc = batch_begin(m, b);
+    if (!rc) rc = gibbs_plan(m, b);
+    if (rc)
+        return rc;
+    auto &g = m->gibbs;
+    if (g.total_tokens * (int64_t)std::max(num_samples, 1) > (int64_t)UINT32_MAX)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
+                                   "counters; split the batch");
+    const bool fresh_cnt = !g.cnt || g.cap_cnt < KV;
+    rc = grow(&g.cnt, &g.cap_cnt, std::max<size_t>(KV, 1));
+    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    if (rc)
+        return rc;
+    if (fresh_cnt)
+        HIP_TRY(hipMemsetAsync(g.cnt, 0, KV * sizeof(uint32_t), m->stream));
+    HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
+    if (B > 0 && g.total_tokens > 0 && (rc = gibbs_preamble(m, b)))
+        return rc;
+    if (B > 0) {
+        GibbsArgs a;
+        a.K = K; a.B = B; a.sweeps = num_samples + burn_in; a.burn_in = burn_in;
+        a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
+        a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
+        a.order = g.order; a.tok_off = g.tok_off;
+        a.eeb = g.eeb; a.alpha = m->alpha; a.theta0 = theta0_dev; a.theta = theta_dev;
+        a.z = g.z; a.cnt = g.cnt; a.flag = g.flag;
+        const int kpl = (K + kWave - 1) / kWave;
+        rc = kpl <= 1 ? gibbs_launch_docs<1>(m, a) : kpl <= 2 ? gibbs_launch_docs<2>(m, a)
+           : kpl <= 4 ? gibbs_launch_docs<4>(m, a) : kpl <= 8 ? gibbs_launch_docs<8>(m, a)
+           : gibbs_launch_docs<16>(m, a);
+        if (rc)
+            return rc;
+    }
+    if (KV) {
+        constexpr int TF = 256;
+        const int GF = (int)std::max<size_t>(1, std::min<size_t>((KV + TF - 1) / TF, 4096));
+        hipLaunchKernelGGL(gibbs_finish_kernel<TF>, dim3(GF), dim3(TF), 0, m->stream, KV,
+                           num_samples > 0 ? 1.0 / num_samples : 0.0, g.cnt, sstats_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    (void)batch_end(m, b);
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_gibbs(trlda_model *m, const trlda_batch *b, const double *theta0_dev, double *theta_dev,
+                      double *sstats_dev, int num_samples, int burn_in, uint64_t key)
+{
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b)
+        return fail(TRLDA_ERR_ARG, "NULL batch");
+    return gibbs_device(m, b, theta0_dev, theta_dev, sstats_dev, num_samples, burn_in, key);
+}
+
+int trlda_model_gibbs_host(trlda_model *m, const trlda_batch *b, double *theta, int use_latents, double *sstats,
+                           int num_samples, int burn_in)
+{
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b || !sstats || (b->B > 0 && !theta))
+        return fail(TRLDA_ERR_ARG, "NULL batch / theta / sstats");
+    if (num_samples < 0 || burn_in < 0)
+        return fail(TRLDA_ERR_ARG, "num_samples and burn_in should not be negative");
+    if (m->K > trlda::kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling supports at most 1024 topics");
+    auto &g = m->gibbs;
+    const size_t tcount = (size_t)m->K * std::max(b->B, 1);
+    const size_t KV = (size_t)m->K * m->V;
+    rc = grow(&g.theta, &g.cap_theta, tcount);
+    if (!rc && use_latents) rc = grow(&g.theta_in, &g.cap_theta_in, tcount);
+    if (!rc) rc = grow(&g.sstats, &g.cap_sstats, std::max<size_t>(KV, 1));
+    if (rc)
+        return rc;
+    const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
+    if (use_latents && tbytes)
+        HIP_TRY(hipMemcpyAsync(g.theta_in, theta, tbytes, hipMemcpyHostToDevice, m->stream));
+    const uint64_t key = trlda_host::rng_draw_key();
+    rc = gibbs_device(m, b, use_latents ? g.theta_in : nullptr, g.theta, g.sstats, num_samples, burn_in, key);
+    if (rc)
+        return rc;
+    if (tbytes)
+        HIP_TRY(hipMemcpyAsync(theta, g.theta, tbytes, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(sstats, g.sstats, KV * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    m->d2h_bytes += (int64_t)(tbytes + KV * sizeof(double));
+    return TRLDA_OK;
+}
+
+// the table the last Gibbs call sampled from (K x V; the batch's active columns), for the tests'
+// restatement of the sampler
+int trlda_debug_gibbs_table(trlda_model *m, double *host_eeb)
+{
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!host_eeb || !m->gibbs.eeb)
+        return fail(TRLDA_ERR_ARG, "no Gibbs call has run on this model");
+    HIP_TRY(hipMemcpyAsync(host_eeb, m->gibbs.eeb, (size_t)m->K * m->V * sizeof(double), hipMemcpyDeviceToHost,
+                           m->stream));
+    return sync_model(m);
 }
 
 int trlda_model_blend(trlda_model *m, const double *lambda_prime_dev, const double *sstats_dev,
@@ -6238,6 +6521,24 @@ int trlda_estep(int K, int V, int B, const int32_t *indptr, const int32_t *ids,
     if (!rc) rc = trlda_model_set_lambda(m, lambda);
     if (!rc) rc = trlda_model_set_alpha(m, alpha);
     if (!rc) rc = trlda_model_estep_host(m, b, gamma, sstats, max_iter, threshold, iters_out);
+    trlda_batch_destroy(b);
+    trlda_model_destroy(m);
+    return rc;
+}
+
+int trlda_gibbs(int K, int V, int B, const int32_t *indptr, const int32_t *ids, const int32_t *cnts,
+                const double *lambda, const double *alpha, double *theta, int use_latents, double *sstats,
+                int num_samples, int burn_in, int device)
+{
+    if (!lambda || !alpha || !sstats)
+        return fail(TRLDA_ERR_ARG, "NULL lambda / alpha / sstats");
+    trlda_model *m = nullptr;
+    trlda_batch *b = nullptr;
+    int rc = trlda_model_create(&m, device, K, V);
+    if (!rc) rc = trlda_batch_create(&b, device, V, B, indptr, ids, cnts);
+    if (!rc) rc = trlda_model_set_lambda(m, lambda);
+    if (!rc) rc = trlda_model_set_alpha(m, alpha);
+    if (!rc) rc = trlda_model_gibbs_host(m, b, theta, use_latents, sstats, num_samples, burn_in);
     trlda_batch_destroy(b);
     trlda_model_destroy(m);
     return rc;

@@ -223,11 +223,25 @@ class LDA(Distribution):
     # -- E-step (ldainterface.cpp:311-390 -> lda.cpp:119-220) ------------------------
     def update_variables(self, docs, latents=None, inference_method='VI', max_iter=100,
                          threshold=0.001, num_samples=1, burn_in=2, return_iterations=False):
-        """E-step: returns ``(gamma K x N, sstats K x V)`` as Fortran-ordered float64."""
+        """E-step: returns ``(gamma K x N, sstats K x V)`` as Fortran-ordered float64.
+
+        ``inference_method='GIBBS'`` (ldainterface.cpp:343-385 -> lda.cpp:224-293) returns
+        ``(theta K x N, sstats K x V)`` instead: collapsed Gibbs sampling of the tokens' topics on
+        the GPU (csrc/gibbs_kernels.h, K <= 1024), ``burn_in`` sweeps, then ``num_samples``
+        sweeps whose topic counts make up the statistics (each token adds ``1 / num_samples``;
+        they are not multiplied by exp E[log beta], unlike VI), and ``theta = Dirichlet(alpha +
+        topic counts)`` of the final state.  ``latents`` is the initial theta (default:
+        Dirichlet(1) per document).  Deviations from the reference: the
+        initialisation reads theta's column of the document, not of the word (lda.cpp:254);
+        the random numbers are Philox4x32-10 keyed by two draws of the seeded stream, so
+        ``trlda.seed`` makes a call reproducible and results do not depend on the launch; the
+        statistics are exact counts scaled once; theta's gamma draws are Marsaglia-Tsang in log
+        space.  ``return_iterations`` does not apply to Gibbs sampling (TypeError)."""
         method = _inference_method(inference_method)
-        if method != "VI":
-            raise NotImplementedError(
-                "Gibbs inference (lda.cpp:224-293) is outside the accelerated path.")
+        if method == "GIBBS":
+            if return_iterations:
+                raise TypeError("`return_iterations` applies to VI only.")
+            return self._update_variables_gibbs(docs, latents, num_samples, burn_in)
         batch, owned = self._batch(docs)
         try:
             self._settle()
@@ -260,6 +274,36 @@ class LDA(Distribution):
 
     do_e_step = update_variables                                     # module.cpp:103-106
 
+    def _update_variables_gibbs(self, docs, latents, num_samples, burn_in):
+        """lda.cpp:224-293 through trlda_model_gibbs_host (include/trlda_hip.h)."""
+        num_samples, burn_in = int(num_samples), int(burn_in)
+        if num_samples < 0 or burn_in < 0:
+            raise RuntimeError("`num_samples` and `burn_in` should not be negative.")
+        batch, owned = self._batch(docs)
+        try:
+            self._settle()
+            B = len(batch)
+            if latents is not None:
+                try:
+                    t = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if t.ndim == 1:
+                    t = t.reshape(-1, 1, order="F")
+                if t.ndim != 2 or t.shape != (self._K, B):
+                    raise RuntimeError("Initial theta has wrong dimensionality.")  # lda.cpp:229-230
+                theta = np.asfortranarray(t)
+            else:
+                theta = np.zeros((self._K, B), dtype=np.float64, order="F")
+            sstats = np.empty((self._K, self._V), dtype=np.float64, order="F")
+            _ffi.check(_ffi.lib().trlda_model_gibbs_host(self._handle, batch.handle, theta,
+                                                         int(latents is not None), sstats,
+                                                         num_samples, burn_in))
+        finally:
+            if owned:
+                batch.close()
+        return theta, sstats
+
     # -- the variational lower bound (ldainterface.cpp:394-470 -> lda.cpp:297-360) ----------
     def _default_num_documents(self):
         return -1                                                    # lda.h: numDocuments = -1
@@ -274,11 +318,14 @@ class LDA(Distribution):
         ``psiLambda.row(id)`` of the K x V matrix where the word's column is meant (an indexing
         slip its release build does not trap); this implements the column read -- the formula of
         the paper and of Hoffman's ``approx_bound`` -- so values differ from upstream's by about
-        1e-4 relative on its own test set-up (the oracle can reproduce either)."""
+        1e-4 relative on its own test set-up (the oracle can reproduce either).
+
+        ``inference_method='GIBBS'`` raises NotImplementedError: the reference's bound would plug
+        the sampled theta in as gamma, which does not bound anything."""
         method = _inference_method(inference_method)
         if method != "VI":
             raise NotImplementedError(
-                "Gibbs inference (lda.cpp:224-293) is outside the accelerated path.")
+                "A lower bound from Gibbs samples (lda.cpp:224-293) is outside the accelerated path.")
         num_documents = int(num_documents)
         if num_documents < 0:
             num_documents = self._default_num_documents()            # onlinelda.cpp:184-191
