@@ -202,8 +202,8 @@ int trlda_batch_num_long_words(const trlda_batch *batch);
  * the workgroup that finishes a word's last segment adds the segments' sums up in segment order
  * (csrc/estep_kernels.h, VeryLongArgs) -- the kernel no longer lasts as long as its longest list
  * (K = 200, 12 500 documents: one list of 12 500 entries kept a workgroup busy for ~100 us).  The
- * number of such words in the batch; trlda_model_set_split_lists(model, 0) (or TRLDA_SPLIT_LISTS=0)
- * keeps every list with one workgroup, for comparisons: same results to rounding. */
+ * number of such words in the batch; trlda_model_set_split_lists(model, 0) keeps every list
+ * with one workgroup, for comparisons: same results to rounding. */
 int trlda_batch_num_very_long_words(const trlda_batch *batch);
 
 /* ---- device-resident model ---------------------------------------------- */
@@ -273,8 +273,8 @@ int trlda_model_last_split_workgroups(const trlda_model *model);
  * counter, instead of a kernel of their own behind it: one launch per trust-region iteration
  * (csrc/estep_merged.h).  Same sums in the same order: bitwise the statistics of the stand-alone
  * kernel.  level 1 (default): where the statistics carry an M-step (the update entry points);
- * 2: plain E-steps too (the two forms take the same time there); 0, or TRLDA_MERGED=0 in the
- * environment: always the kernel of its own.  last_merged: what the model's last E-step did. */
+ * 2: plain E-steps too (the two forms take the same time there); 0: always the kernel of its
+ * own.  last_merged: what the model's last E-step did. */
 int trlda_model_set_merged_launch(trlda_model *model, int level);
 int trlda_model_set_split_lists(trlda_model *model, int enabled);
 int trlda_model_last_merged(const trlda_model *model);

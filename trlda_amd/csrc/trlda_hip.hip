@@ -288,7 +288,6 @@ struct trlda_model {
     // every entry point, trlda_model_flush, trlda_batch_destroy of the batch they read).  What the
     // pending statistics read is kept apart from what the next call writes: exp(psi(gamma)) rows
     // and weights in two alternating buffers, exp(psi(lambda)) of its batch in a third buffer.
-    bool deferred_stats = false;
     struct {
         bool valid = false;
         const trlda_batch *batch = nullptr;
@@ -397,15 +396,31 @@ struct trlda_model {
         bool dense = false;
     } prefetch;
     double *eeb_cur = nullptr;          // the exp E[log beta] buffer of the E-step in flight
-    int sstats_mode = TRLDA_SSTATS_SEGMENTED;
-    int doc_threads = 0;
-    int doc_kernel = 0;    // TRLDA_DOCS_*
-    int small_k = -1;      // a wave per document at K <= 32 (estep_docs_small_body): -1 where it applies, 0 never,
-                           // 1 asked for (trlda_model_set_doc_kernel(TRLDA_DOCS_SMALL / _REG); TRLDA_SMALL_K)
+    // The E-step's switches (the trlda_model_set_* setters, tests and comparisons).  A stream lane
+    // follows its owner's (lane_follow).
+    struct Switches {
+        int sstats_mode = TRLDA_SSTATS_SEGMENTED;
+        int doc_threads = 0;
+        int doc_kernel = 0;             // TRLDA_DOCS_*
+        // a wave per document at K <= 32 (estep_docs_small_body): -1 where it applies, 0 never,
+        // 1 asked for (trlda_model_set_doc_kernel(TRLDA_DOCS_SMALL / _REG))
+        int small_k = -1;
+        bool split_preamble = false;    // never fuse kernels 1 and 2
+        bool dense_preamble = false;    // true: exp E[log beta] for all V words, as the reference
+        bool prefetch_next = true;      // trlda_model_set_prefetch: honour "next batch" announcements
+        bool split_docs = true;         // trlda_model_set_split_docs
+        // the merged launch (trlda_model_set_merged_launch): 0 never; 1 where the statistics carry an
+        // M-step (13 us as a launch of their own, ~9 inside the document launch); 2 also plain E-steps
+        int merged_launch = 1;
+        bool split_long_lists = true;   // trlda_model_set_split_lists: very long lists over several workgroups
+        bool fused_update = true;       // trlda_model_set_fused_update: statistics + M-step in one pass
+        bool carry_rowsums = true;      // trlda_model_set_carry_rowsums
+        bool emit_next_preamble = true; // trlda_model_set_fused_update(.. & 2 == 0)
+        bool deferred_stats = false;    // trlda_model_set_deferred_stats (pending, above)
+        bool big_emit = true;           // TRLDA_BIG_EMIT=0: exp_elog_beta_kernel in every iteration
+    } sw;
     const char *last_doc_kernel = "";   // kernel that took most documents of the last E-step
     bool last_preamble_fused = false;
-    bool split_preamble = false;        // never fuse kernels 1 and 2 (tests, comparisons)
-    bool dense_preamble = false;   // true: exp E[log beta] for all V words, as the reference
     double *lambda = nullptr, *alpha = nullptr;
     double *eeb = nullptr, *psi_sum = nullptr, *partial = nullptr;
     unsigned int *counter = nullptr;
@@ -440,10 +455,6 @@ struct trlda_model {
         bool valid = false;
         uint64_t batch_id = 0, version = 0;
     } u_left;
-    bool big_emit = true;               // TRLDA_BIG_EMIT=0: exp_elog_beta_kernel in every iteration
-    bool emit_next_preamble = true;     // trlda_model_set_fused_update(.. & 2 == 0)
-    bool carry_rowsums = true;          // trlda_model_set_carry_rowsums (tests, comparisons)
-    bool fused_update = true;           // trlda_model_set_fused_update: statistics + M-step in one pass
     bool keep_sstats = false;           // updates also leave the statistics (and all of lambda') behind
     // A lower bound on every row sum of lambda, kept on the host: the fused preamble forms
     // exp(-psi(row sum)), which overflows below 1.4e-3 (estep_kernels.h, 2b)
@@ -455,8 +466,6 @@ struct trlda_model {
     // everything else that writes lambda.  Only then may an M-step kernel also emit exp(psi(lambda))
     // with the call-free positive-argument form (psi.h, exp_digamma_positive).
     bool lambda_positive = false;
-    bool pair_gathers = true;           // statistics kernel with two topics per lane (even K > 128)
-    bool prefetch_next = true;          // trlda_model_set_prefetch: honour "next batch" announcements
     // per-batch workspaces, grown on demand
     size_t cap_docs = 0, cap_tw_csr = 0, cap_tw_word = 0;
     // Data-parallel factor exchange (DpContext below): the gathered factors of all ranks, the
@@ -470,8 +479,6 @@ struct trlda_model {
     int (*allgatherv_hook)(void *, void *, const size_t *, int, int, void *) = nullptr;
     void *allgatherv_ctx = nullptr;
     bool word_sharding = true;          // trlda_model_set_word_sharding
-    bool split_long_lists = true;       // TRLDA_SPLIT_LISTS=0: very long lists stay one workgroup's (comparisons)
-    bool tiled_tasks = true;            // TRLDA_TILED_TASKS=0: segment tasks in word order (comparisons)
     bool last_word_sharded = false;     // the last *_dp call's M-steps were word-sharded
     // direct exchange (dp_kernels.h): this process's region [2 x world x max_slot doubles |
     // kDpMaxWorld step counters], exported through hipIpc; the peers' regions mapped here
@@ -494,11 +501,6 @@ struct trlda_model {
     // merged launch (estep_merged.h): the statistics as workgroups of the document launch.
     // Two counters that only grow (documents done | topic factors finished) and what they have
     // been asked to reach so far; the finished topic factors of an in-launch combine
-    // 0: never; 1 (default): where the statistics carry an M-step -- the update loops, where a
-    // launch of their own costs 13 us against ~9 inside the document launch (round 4: 0.53 -> 0.50 ms
-    // per update_parameters(max_iter_tr=10)); 2: also for plain E-steps, where the two forms take
-    // the same time to 1 % (39.6 / 40.0 us per step) and the kernel of its own is the default
-    int merged_launch = 1;              // trlda_model_set_merged_launch
     bool last_merged = false;
     unsigned int *sync_counters = nullptr;
     unsigned int docs_done_total = 0, c_ready_total = 0;
@@ -516,7 +518,6 @@ struct trlda_model {
     // `xerr` -- checking it after a synchronisation is a plain host read (check_split_exchange)
     int *xerr = nullptr;
     volatile int *xerr_host = nullptr;
-    bool split_docs = true;             // trlda_model_set_split_docs
     int last_split_wgs = 0;             // workgroups of the last document launch beyond one per document
     // update_parameters workspaces
     double *lambda_prime = nullptr, *sstats = nullptr, *gamma = nullptr, *wordcounts = nullptr;
@@ -1093,7 +1094,7 @@ struct EstepOut {
 // statistics + M-step + row sums in one kernel: K <= 512, segmented mode
 bool fused_update_available(const trlda_model *m)
 {
-    return m->fused_update && m->K <= trlda::kWideMaxK && m->sstats_mode == TRLDA_SSTATS_SEGMENTED;
+    return m->sw.fused_update && m->K <= trlda::kWideMaxK && m->sw.sstats_mode == TRLDA_SSTATS_SEGMENTED;
 }
 
 // the column-slot streaming kernels (stream_kernels.h) cover K <= 512
@@ -1131,7 +1132,7 @@ int resolve_carry(trlda_model *m)
 // something knows the row sums of the current lambda (and may be believed)
 bool rowsums_carried(const trlda_model *m)
 {
-    return !m->lambda_exposed && m->carry_rowsums && (m->rs_valid || m->carry_pending);
+    return !m->lambda_exposed && m->sw.carry_rowsums && (m->rs_valid || m->carry_pending);
 }
 
 template <int VEC>
@@ -1196,7 +1197,7 @@ int launch_sstats_update(trlda_model *m, const trlda_batch *b, EstepOut &out)
     const int G_long = std::min(kUpdLongBlocks, n_long);
     // the very long lists (of this rank's slice): segment tasks for whole workgroups
     trlda::VeryLongArgs vl{};
-    const bool segments = b->n_vl > 0 && b->n_vl <= kUpdVlRows && m->split_long_lists;
+    const bool segments = b->n_vl > 0 && b->n_vl <= kUpdVlRows && m->sw.split_long_lists;
     if (segments) {
         const int j_lo = out.sliced ? out.vl_lo : 0, j_n = out.sliced ? out.vl_n : b->n_vl;
         vl.j0 = j_lo;
@@ -1207,7 +1208,7 @@ int launch_sstats_update(trlda_model *m, const trlda_batch *b, EstepOut &out)
         vl.seg_len = b->seg_len;
         // (a rank's slice: its words' tasks are contiguous in the by-word order; the whole batch:
         // the order that keeps concurrently running workgroups on the same documents)
-        vl.task = reinterpret_cast<const int4 *>(out.sliced || !m->tiled_tasks ? b->vl_task : b->vl_task_tiled);
+        vl.task = reinterpret_cast<const int4 *>(out.sliced ? b->vl_task : b->vl_task_tiled);
         vl.word = reinterpret_cast<const int4 *>(b->vl_word);
         int rc0 = grow(&m->seg_partial, &m->cap_seg_partial, std::max<size_t>((size_t)vl.n_tasks * K, 1));
         if (!rc0 && (size_t)b->n_vl > m->cap_seg_counter) {
@@ -1281,7 +1282,7 @@ int sstats_update_device(trlda_model *m, const trlda_batch *b, EstepOut &out)
     const int K = m->K;
     // one wavefront per word; 16 words per workgroup for small K, 8 from K = 256 on
     // (measured: 7.1 vs 7.4 us at K = 100, 170 vs 145 us at K = 500)
-    if (K % 2 == 0 && m->pair_gathers) {
+    if (K % 2 == 0) {
         // a lane owns two adjacent topics: 16-byte gathers, 256 topics per pass over a list
 #ifdef TRLDA_EMIT_T512
         // measurement variant: the instantiation that also emits exp(psi(lambda)) as 512-thread
@@ -1577,30 +1578,118 @@ bool fused_preamble_possible(const trlda_model *m, const trlda_batch *docs)
 {
     // (whatever the documents' lengths: every variant of the K <= 128 document launch applies
     // the topic factors, estep_docs_tiered_kernel)
-    return (size_t)m->K * m->V < ((size_t)1 << 22) && docs->B > 0 && m->doc_threads == 0 &&
-           m->doc_kernel == TRLDA_DOCS_AUTO && !m->split_preamble && m->K <= trlda::kRegMaxK &&
+    return (size_t)m->K * m->V < ((size_t)1 << 22) && docs->B > 0 && m->sw.doc_threads == 0 &&
+           m->sw.doc_kernel == TRLDA_DOCS_AUTO && !m->sw.split_preamble && m->K <= trlda::kRegMaxK &&
            !m->lambda_exposed;
 }
 
 // may the M-step kernel of an E-step on `docs` leave the next preamble behind?
 bool can_emit_next(const trlda_model *m, const trlda_batch *docs)
 {
-    return m->emit_next_preamble && m->carry_rowsums && fused_preamble_possible(m, docs);
+    return m->sw.emit_next_preamble && m->sw.carry_rowsums && fused_preamble_possible(m, docs);
 }
 
-// The E-step launch sequence on the model's stream (no synchronisation).  `out` says what the
-// statistics stage writes; an M-step in it (out.upd.lambda) needs fused_update_available().
-int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepOut &out,
-                 int max_iter, double threshold, int32_t *iters_dev,
-                 const double *gamma_in_dev = nullptr, const trlda_batch *next = nullptr)
+template <class Op>
+int launch_elementwise(trlda_model *m, size_t total, const Op &op)
+{
+    size_t blocks = (total / 2 + kDenseThreads * 4 - 1) / (kDenseThreads * 4);
+    int G = (int)std::max<size_t>(1, std::min<size_t>(blocks, 256 * 8));
+    hipLaunchKernelGGL((trlda::elementwise_stream_kernel<kDenseThreads, Op>), dim3(G),
+                       dim3(kDenseThreads), 0, m->stream, total, op);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the device's compute units, asked of the runtime once per device
+int device_cus(int device)
+{
+    static std::atomic<int> cus_cache[64];
+    int cus = device < 64 ? cus_cache[device].load(std::memory_order_relaxed) : 0;
+    if (cus <= 0) {
+        cus = 256;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (device < 64)
+            cus_cache[device].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+// the workgroups of a row-sum pass over V words (at most `most`, ~32 words each at least), and
+// the words each adds up (wpb)
+int rowsum_blocks(int V, int most, int &wpb)
+{
+    const int G = std::min(most, std::max(1, V / 32));
+    wpb = (V + G - 1) / G;
+    return (V + wpb - 1) / wpb;
+}
+
+// f(std::integral_constant<int, ks>) for the single-orientation body's ks = 1..8 (estep_wide.h;
+// beyond 8: 8)
+template <int KS = 1, class F>
+auto ks_dispatch(int ks, F &&f)
+{
+    if constexpr (KS == 8)
+        return f(std::integral_constant<int, 8>{});
+    else
+        return ks == KS ? f(std::integral_constant<int, KS>{}) : ks_dispatch<KS + 1>(ks, f);
+}
+
+// LDS rows of the single-orientation body for the words past its registers: as many as the
+// longest document (max_n words) needs and fit
+int wide_lds_rows(int KS, int max_n)
 {
     using namespace trlda;
-    // data-parallel call: the preamble and the statistics cover the whole mini-batch `b`, the
-    // document stage this rank's shard `db` of it
+    const int jw = ks_dispatch(KS, [](auto ks) { return wide_cfg<decltype(ks)::value>::JW; });
+    const size_t fixed = wide_lds_doubles(KS, 0) * sizeof(double);
+    const int fit = (int)(((size_t)kLdsDynBytes - fixed) / ((size_t)(64 * KS + 1) * sizeof(double)));
+    return std::max(0, std::min(fit, max_n - kWideWaves * jw));
+}
+
+// may the statistics stage of a merged or deferred launch (estep_merged.h) take batch x: small
+// batches whose words' lists the stage's waves hold in one piece, pairs of topics per lane (a long
+// list goes to the stage's sixteen chunks of at most 16 entries: 256 entries -- a list can be
+// longer than B when ids repeat within documents)
+bool stats_stage_fits(const trlda_model *m, const trlda_batch *x)
+{
+    return m->K % 2 == 0 && x->long_len == trlda::kLongWord && x->B <= 256 && x->max_list <= 256 &&
+           x->n_active > 0 && x->V == m->V && x->device == m->device;
+}
+
+// diagnostics (TRLDA_MERGED_STAMPS=1): the time stamps of a merged or deferred launch, n of them
+unsigned long long *launch_stamps(unsigned long long *&buf, size_t n)
+{
+    static const bool want_stamps = std::getenv("TRLDA_MERGED_STAMPS") != nullptr;
+    if (want_stamps && !buf && dev_alloc(&buf, n) == TRLDA_OK)
+        (void)hipMemset(buf, 0, n * sizeof(unsigned long long));
+    return want_stamps ? buf : nullptr;
+}
+
+// What an E-step call launches, decided before anything is launched (estep_begin).  db: the
+// documents -- data-parallel: this rank's shard of the mini-batch; next: the batch announced to follow
+struct EstepPlan {
+    const trlda_batch *db = nullptr, *next = nullptr;
+    int K = 0, V = 0, B = 0, max_iter = 0, cus = 0;
+    bool atomic = false, big = false, carried = false;   // TRLDA_SSTATS_ATOMIC; K V >= 2^22; rowsums_carried
+    bool fused = false, fused_big = false, handed = false, comb = false, prefetched = false;
+    bool split = false;                   // documents of more than 192 words over several workgroups ...
+    size_t xcount = 0;                    // ... the doubles of their exchange rows
+    int n_long = 0, n_long_wgs = 0, doc_wgs = 0;
+    bool small = false, merged_capable = false;
+    bool reg = false, tiered = false;     // the K <= 128 launch takes every document / some of > 128 words
+    int KS = 0;                           // wave-slices of K topics
+    bool pre_next = false;                // the next batch's preamble rides on the document launch
+    bool merged = false;                  // the statistics are workgroups of the document launch
+    bool launch_ok = false, defer_self = false, carry = false;
+};
+
+// Stage 1: the checks, and the call's decisions
+int estep_begin(trlda_model *m, const trlda_batch *b, const EstepOut &out, int max_iter,
+                const trlda_batch *next, EstepPlan &p)
+{
+    using namespace trlda;
     DpContext *dp = m->dp;
     const trlda_batch *db = dp ? dp->shard : b;
     const int K = m->K, V = m->V, B = db->B;
-    const size_t KV = (size_t)K * V;
     if (b->V != V || db->V != V)
         return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
     if (m->eb.active)
@@ -1615,7 +1704,7 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
         rc = batch_begin(m, db);
     if (rc)
         return rc;
-    const bool atomic = m->sstats_mode == TRLDA_SSTATS_ATOMIC;
+    const bool atomic = m->sw.sstats_mode == TRLDA_SSTATS_ATOMIC;
     if (dp && atomic)
         return fail(TRLDA_ERR_ARG, "the factor exchange needs the segmented statistics mode");
     if (dp)
@@ -1629,21 +1718,19 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
         m->dp_gather = m->dp_gather_direct +
                        (size_t)((m->direct.step + 1ull) & 1ull) * (size_t)dp->world * m->direct.max_slot;
     }
-    double *sstats_dev = out.upd.sstats;
     m->last_split_wgs = 0;
     m->last_merged = false;
     if (m->timing && (rc = stamp(m)))
         return rc;
 
-    // 1. row sums of lambda (lda.cpp:172) -- unless the kernel that wrote lambda left them
-    // behind (rs_valid).  Small tables: 64 blocks whose partials the consumers add up
-    // themselves (saves a launch).  Large ones: the streaming kernel, then one small kernel
-    // combines the block partials.
-    const bool big = KV >= ((size_t)1 << 22);
+    p.db = db; p.next = next;
+    p.K = K; p.V = V; p.B = B; p.max_iter = max_iter;
+    p.cus = device_cus(m->device);
+    p.atomic = atomic;
+    p.big = (size_t)K * V >= ((size_t)1 << 22);
+    p.carried = rowsums_carried(m);
     const bool trust = !m->lambda_exposed;
-    const bool carried = rowsums_carried(m);
-    int G = std::min(big ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks, std::max(1, V / 32));
-    const double *partial_in = m->partial;
+    const bool auto_docs = m->sw.doc_threads == 0 && m->sw.doc_kernel == TRLDA_DOCS_AUTO;
     // Small table and every document in the register-resident kernel's range: kernels 1 and
     // 2 become one launch and the topic factors exp(-psiSum) are applied by the document
     // kernel (estep_kernels.h, 2b) -- as long as no row sum can be so small that exp(-psi(sum))
@@ -1651,175 +1738,182 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
     // (data-parallel: a property of the WHOLE mini-batch, which every rank holds -- the ranks must
     // agree on what the gathered factors mean: with the fused preamble a rank publishes c_k
     // expElogtheta and keeps exp(psi(lambda)) unnormalised, without it plain expElogtheta)
-    const bool fused = fused_preamble_possible(m, b) && trust && m->rs_floor >= kFusedRowsumFloor;
+    p.fused = fused_preamble_possible(m, b) && trust && m->rs_floor >= kFusedRowsumFloor;
     // Big table, single-orientation document kernel: the previous trust-region iteration's M-step
     // left exp(psi(lambda)) of THIS batch's words behind and the row sums came with it (carried):
     // no exp_elog_beta_kernel -- the document kernel applies the K topic factors
-    const bool fused_big = !fused && big && carried && trust && !dp && !atomic && B > 0 && m->big_emit &&
-                           m->u_left.valid && m->u_left.batch_id == b->id &&
-                           m->u_left.version == m->lambda_version && m->rs_floor >= kFusedRowsumFloor &&
-                           K > kRegMaxK && K <= kWideMaxK && m->doc_threads == 0 &&
-                           m->doc_kernel == TRLDA_DOCS_AUTO && !m->dense_preamble;
-    m->u_left.valid = false;
-    m->last_preamble_fused = fused || fused_big;
-    if (!fused && carried && (rc = resolve_carry(m)))   // everything else wants one row of sums
-        return rc;
-    m->eeb_cur = m->eeb;
-    // this batch's preamble may have been left behind by the kernel that wrote lambda (the
-    // M-step inside the statistics kernel: UpdateOut::u_out / group_rows) ...
-    // Merged launch (estep_merged.h): how many workgroups the documents of this launch take, and
-    // whether helper workgroups ride on it
-    const size_t xcount_m = (size_t)db->n_xrows * (size_t)(max_iter + 1) * (size_t)K;
-    const bool will_split = db->max_n > 128 && m->split_docs && db->n_wg > 0 && db->split_pays &&
-                            max_iter > 0 && xcount_m * sizeof(double) <= ((size_t)256 << 20);
-    // K <= 32: a wave per document, eight documents per workgroup (estep_kernels.h, estep_docs_small_body).
-    // A throughput form: a lone wave takes 46-55 us for a document the eight-wave body finishes in 30, but a
-    // CU holds eight such documents -- taken where the documents would not fit the chip one per CU
-    // (K = 10: 512 documents 15.4 against 8.4 M docs/s, 6400 documents 38.5 against 9.7 M; 100
-    // documents 3.7 against 5.6 M: profiles/r06_small_k.txt), or when asked for
-    int cus_now = 256;
-    (void)hipDeviceGetAttribute(&cus_now, hipDeviceAttributeMultiprocessorCount, m->device);
-    // Documents of more than 128 words -- they lead the batch's sorted order -- keep a workgroup each, in
-    // front of the waves' workgroups of the same (tiered) launch: a batch does not lose the form to its
-    // long documents (CU-time: a long one 27-50 us, a short one 46 / 8 -- the form pays as long as most
-    // are short; split documents keep their segments' workgroups, and the waves find their documents
-    // through the batch's order and CSR arrays instead of the padded rows)
-    int n_long = 0, n_long_wgs = 0;                  // ... and the workgroups they take (split: a segment each)
+    p.fused_big = !p.fused && p.big && p.carried && trust && !dp && !atomic && B > 0 && m->sw.big_emit &&
+                  m->u_left.valid && m->u_left.batch_id == b->id &&
+                  m->u_left.version == m->lambda_version && m->rs_floor >= kFusedRowsumFloor &&
+                  K > kRegMaxK && K <= kWideMaxK && auto_docs && !m->sw.dense_preamble;
+    // Documents of more than 192 words: split over several workgroups that exchange K sums per
+    // iteration (estep_docs_reg_body<0, true>) -- the batch brought the per-workgroup layout; one
+    // row of K doubles per (segment, iteration), NaN before the launch.  Not with an exchange
+    // buffer beyond 256 MB (max_iter in the thousands): those batches keep one workgroup per document.
+    p.xcount = (size_t)db->n_xrows * (size_t)(max_iter + 1) * (size_t)K;
+    p.split = db->max_n > 128 && m->sw.split_docs && db->n_wg > 0 && db->split_pays && max_iter > 0 &&
+              p.xcount * sizeof(double) <= ((size_t)256 << 20);
+    // K <= 32: a wave per document, eight documents per workgroup (estep_docs_small_body), a throughput
+    // form taken where the documents would not fit the chip one per CU, or when asked for
+    // (profiles/r06_small_k.txt).  Documents of more than 128 words -- they lead the batch's sorted order
+    // -- keep a workgroup (split: their segments' workgroups) each, in front of the waves' workgroups
+    // of the same launch: the form pays as long as most documents are short
     if (db->max_n > 128)
-        for (; n_long < B && db->sorted_len[(size_t)n_long] > 128; ++n_long) {
-            const int n = db->sorted_len[(size_t)n_long];
-            const int c = (n + trlda::kSplitSegN - 1) / trlda::kSplitSegN;
-            n_long_wgs += (will_split && n > trlda::kSplitMinN && c <= trlda::kSplitMaxSeg) ? c : 1;   // (batch_index.cpp)
+        for (; p.n_long < B && db->sorted_len[(size_t)p.n_long] > 128; ++p.n_long) {
+            const int n = db->sorted_len[(size_t)p.n_long];
+            const int c = (n + kSplitSegN - 1) / kSplitSegN;
+            p.n_long_wgs += (p.split && n > kSplitMinN && c <= kSplitMaxSeg) ? c : 1;   // (batch_index.cpp)
         }
-    const bool small = (m->small_k > 0 || (m->small_k < 0 && B - n_long > cus_now)) && K <= 32 && B > 0 &&
-                       (n_long == 0 || n_long * 2 <= B) && !atomic && m->doc_threads == 0 &&
-                       m->doc_kernel == TRLDA_DOCS_AUTO;
-    const int small_wgs = n_long_wgs + (B - n_long + 7) / 8;
-    const int doc_wgs = small ? small_wgs : will_split ? db->n_wg : B;
-    // (... a matter of speed: the helpers run UNDER the documents only when the documents leave
-    // CUs free -- a document workgroup fills one.  Safety does not depend on it: estep_merged.h)
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device);
-    const bool merged_capable = m->merged_launch > 0 && fused && !atomic && !dp && B > 0 &&
-                                doc_wgs <= std::min(trlda::kMergedMaxDocWgs, cus - 32);
-    bool handed = fused && carried && m->carry_pending && m->next_pre.valid &&
-                  m->next_pre.version == m->lambda_version &&
-                  (m->next_pre.all || m->next_pre.batch_id == b->id);
-    // (block rows still to be added up need this launch's combine workgroups: without them the
-    // preamble launch below adds them up -- and fills exp(psi(lambda)) once more)
-    if (handed && m->next_pre.raw && !merged_capable)
-        handed = false;
-    const bool comb = handed && m->next_pre.raw;
-    if (handed) {
-        partial_in = comb ? m->carry_rows : m->upd_groups;
-        G = comb ? m->carry_n : m->next_pre.n;
-        if (m->timing && ((rc = stamp(m)) || (rc = stamp(m))))
-            return rc;
-    }
+    p.small = (m->sw.small_k > 0 || (m->sw.small_k < 0 && B - p.n_long > p.cus)) && K <= 32 && B > 0 &&
+              (p.n_long == 0 || p.n_long * 2 <= B) && !atomic && auto_docs;
+    p.doc_wgs = p.small ? p.n_long_wgs + (B - p.n_long + 7) / 8 : p.split ? db->n_wg : B;
+    // Merged launch (estep_merged.h): whether helper workgroups ride on the document launch --
+    // a matter of speed: the helpers run UNDER the documents only when the documents leave CUs
+    // free (a document workgroup fills one).  Safety does not depend on it: estep_merged.h
+    p.merged_capable = m->sw.merged_launch > 0 && p.fused && !atomic && !dp && B > 0 &&
+                       p.doc_wgs <= std::min(kMergedMaxDocWgs, p.cus - 32);
+    // K <= 128: ONE launch for all documents, ordered by decreasing length -- the register
+    // kernel when none has more than 128 words, else the tiered kernel, whose workgroups
+    // take the variant their own document needs (estep_wide.h)
+    p.reg = K <= kRegMaxK && auto_docs;
+    p.tiered = db->max_n > 128;
+    p.KS = (K + kWave - 1) / kWave;
+    // this batch's preamble may have been left behind by the kernel that wrote lambda (the
+    // M-step inside the statistics kernel: UpdateOut::u_out / group_rows) ... (block rows still
+    // to be added up need the document launch's combine workgroups: without them the preamble
+    // launch adds them up -- and fills exp(psi(lambda)) once more)
+    p.handed = p.fused && p.carried && m->carry_pending && m->next_pre.valid &&
+               m->next_pre.version == m->lambda_version && (m->next_pre.all || m->next_pre.batch_id == b->id) &&
+               !(m->next_pre.raw && !p.merged_capable);
+    p.comb = p.handed && m->next_pre.raw;
     // ... or prepared under the previous call's document kernel
-    const bool prefetched = fused && !carried && m->prefetch.valid && m->prefetch.batch_id == b->id &&
-                            m->prefetch.version == m->lambda_version &&
-                            m->prefetch.dense == m->dense_preamble;
-    int cur_buf = -1;
-    if (prefetched) {
-        cur_buf = m->prefetch.buf;
-        m->eeb_cur = m->eeb_pp[cur_buf];
-        partial_in = m->partial_pp[cur_buf];
-        G = m->prefetch.G;
-        if (m->timing && ((rc = stamp(m)) || (rc = stamp(m))))
-            return rc;
-    }
-    m->prefetch.valid = false;
-
+    p.prefetched = p.fused && !p.carried && m->prefetch.valid && m->prefetch.batch_id == b->id &&
+                   m->prefetch.version == m->lambda_version && m->prefetch.dense == m->sw.dense_preamble;
+    // the next batch's preamble as extra workgroups of the document launch (PreArgs): when the
+    // caller announced it, it fits the same path, and lambda is not about to change
+    p.pre_next = next && p.fused && p.reg && !out.upd.lambda && !atomic && next->V == V &&
+                 next->device == m->device && next->B > 0 && !m->lambda_exposed && m->sw.prefetch_next;
     // Deferred statistics (trlda_model::pending).  launch_ok: this call is a plain E-step whose one
     // document launch can take helper workgroups; defer_self: its own statistics wait for the next
     // call; carry: its launch forms the statistics the call before left pending.  What cannot be
-    // carried is launched as the kernel of its own, now -- before anything of this call overwrites
-    // what it reads (the exp(psi(lambda)) buffer m->eeb, when this call fills it).
-    auto stage_fits = [&](const trlda_batch *x) {
-        return K % 2 == 0 && m->pair_gathers && x->long_len == trlda::kLongWord && x->B <= 256 &&
-               x->max_list <= 256 && x->n_active > 0 && x->V == V && x->device == m->device;
-    };
-    const bool launch_ok = m->deferred_stats && fused && !dp && !atomic && !out.upd.lambda && sstats_dev &&
-                           B > 0 && m->doc_threads == 0 && K <= kRegMaxK && m->doc_kernel == TRLDA_DOCS_AUTO &&
-                           fused_update_available(m) && !comb;
-    const bool defer_self = launch_ok && stage_fits(b);
-    const bool writes_eeb = !(prefetched || handed);
-    bool carry = false;
-    if (m->pending.valid) {
-        carry = launch_ok && stage_fits(m->pending.batch) && !(m->pending.eeb_buf < 0 && writes_eeb);
-        if (!carry && (rc = flush_pending(m)))
-            return rc;
-    }
-    m->last_deferred = false;
-    m->last_carried = carry;
+    // carried is launched as the kernel of its own before anything of this call overwrites what it
+    // reads (the exp(psi(lambda)) buffer m->eeb, when this call fills it: estep_preamble)
+    const double *sstats_dev = out.upd.sstats;
+    p.launch_ok = m->sw.deferred_stats && p.fused && !dp && !atomic && !out.upd.lambda && sstats_dev &&
+                  B > 0 && K <= kRegMaxK && auto_docs && fused_update_available(m) && !p.comb;
+    p.defer_self = p.launch_ok && stats_stage_fits(m, b);
+    const bool writes_eeb = !(p.prefetched || p.handed);
+    p.carry = m->pending.valid && p.launch_ok && stats_stage_fits(m, m->pending.batch) &&
+              !(m->pending.eeb_buf < 0 && writes_eeb);
+    // The statistics (and what rides on them: M-step, row sums, the next preamble) as workgroups
+    // of the document launch (estep_merged.h)
+    p.merged = !p.launch_ok && p.merged_capable && stats_stage_fits(m, b) && fused_update_available(m) &&
+               (out.upd.lambda ? out.active_only : sstats_dev != nullptr && m->sw.merged_launch >= 2);
+    return TRLDA_OK;
+}
 
-    if (fused && !prefetched && !handed) {
+// where the document launch finds the row sums (G rows of K; cur_buf: the prefetch buffer or -1)
+struct Preamble {
+    const double *partial_in = nullptr;
+    int G = 0, cur_buf = -1;
+};
+
+// Stage 2: the row sums of lambda and exp E[log beta] (lda.cpp:172-173) -- or the hand-over of
+// what an earlier launch left behind
+int estep_preamble(trlda_model *m, const trlda_batch *b, const EstepPlan &p, Preamble &pr)
+{
+    using namespace trlda;
+    const int K = p.K, V = p.V;
+    const bool dense = m->sw.dense_preamble;
+    const size_t total = dense ? (size_t)K * V : (size_t)K * (size_t)b->n_active;
+    const int *active = dense ? nullptr : b->active;
+    int rc = 0;
+    m->u_left.valid = false;
+    m->last_preamble_fused = p.fused || p.fused_big;
+    if (!p.fused && p.carried && (rc = resolve_carry(m)))   // everything else wants one row of sums
+        return rc;
+    m->eeb_cur = m->eeb;
+    pr.partial_in = m->partial;
+    if (p.handed) {
+        pr.partial_in = p.comb ? m->carry_rows : m->upd_groups;
+        pr.G = p.comb ? m->carry_n : m->next_pre.n;
+    } else if (p.prefetched) {
+        pr.cur_buf = m->prefetch.buf;
+        m->eeb_cur = m->eeb_pp[pr.cur_buf];
+        pr.partial_in = m->partial_pp[pr.cur_buf];
+        pr.G = m->prefetch.G;
+    }
+    if ((p.handed || p.prefetched) && m->timing && ((rc = stamp(m)) || (rc = stamp(m))))
+        return rc;
+    m->prefetch.valid = false;
+    // pending statistics this call's launch does not carry: now, before m->eeb is filled again
+    if (!p.carry && (rc = flush_pending(m)))
+        return rc;
+    m->last_deferred = false;
+    m->last_carried = p.carry;
+
+    if (p.fused && !p.prefetched && !p.handed) {
         constexpr int TP = 512;
-        int wpb = 0, GC = 0;
+        int G = 0, wpb = 0, GC = 0;
         const double *carry_rows = nullptr, *carry_base = nullptr;
         int carry_n = 0;
-        if (carried && m->carry_pending && (m->carry_n > trlda::kRowsumBlocks || m->carry_base)) {
+        if (p.carried && m->carry_pending && (m->carry_n > kRowsumBlocks || m->carry_base)) {
             // block partials left by the statistics kernel: kCarryBlocks workgroups of this
             // launch add them up (with the inactive words' share) into carry_out
-            G = 0;
             GC = kCarryBlocks;
             carry_rows = m->carry_rows; carry_base = m->carry_base; carry_n = m->carry_n;
-        } else if (carried) {
-            G = 0;                                   // no row-sum workgroups: all of them fill
-        } else {
-            G = std::min(trlda::kRowsumBlocks, std::max(1, V / 32));
-            wpb = (V + G - 1) / G;
-            G = (V + wpb - 1) / wpb;
+        } else if (!p.carried) {                     // (carried: no row-sum workgroups, all of them fill)
+            G = rowsum_blocks(V, kRowsumBlocks, wpb);
         }
-        const bool dense = m->dense_preamble;
-        const size_t total = dense ? KV : (size_t)K * (size_t)b->n_active;
         // G workgroups add up the row sums, the others fill exp(psi(lambda)): 256 in all, one
         // per CU (a 1024-thread workgroup of this kernel fills a CU's registers)
         const int lead = G + GC;
         const int GP = lead + (int)std::max<size_t>(1, std::min<size_t>((total + TP - 1) / TP, (size_t)(256 * (1024 / TP) - lead)));
         hipLaunchKernelGGL(preamble_fused_kernel<TP>, dim3(GP), dim3(TP), 0, m->stream, K, V, G, wpb,
-                           total, m->lambda, m->partial, m->eeb_cur, dense ? nullptr : b->active, GC,
+                           total, m->lambda, m->partial, m->eeb_cur, active, GC,
                            carry_rows, carry_n, carry_base, m->carry_out);
         HIP_TRY(hipGetLastError());
+        pr.G = G;
         if (GC > 0) {
-            partial_in = m->carry_out;
-            G = kCarryBlocks;
+            pr.partial_in = m->carry_out;
+            pr.G = kCarryBlocks;
             // lambda has not changed: its row sums are now these eight rows
             m->carry_rows = m->carry_out; m->carry_n = kCarryBlocks; m->carry_base = nullptr;
-        } else if (carried && m->carry_pending) {
-            partial_in = m->carry_rows;              // few enough rows for the document kernel
-            G = m->carry_n;
-        } else if (carried) {
-            partial_in = m->rs_full;
-            G = 1;
+        } else if (p.carried && m->carry_pending) {
+            pr.partial_in = m->carry_rows;           // few enough rows for the document kernel
+            pr.G = m->carry_n;
+        } else if (p.carried) {
+            pr.partial_in = m->rs_full;
+            pr.G = 1;
         }
-        if (m->timing && ((rc = stamp(m)) || (rc = stamp(m))))
+        return m->timing && ((rc = stamp(m)) || (rc = stamp(m))) ? rc : TRLDA_OK;
+    }
+    if (p.fused)
+        return TRLDA_OK;
+
+    // 1. row sums of lambda (lda.cpp:172) -- unless the kernel that wrote lambda left them
+    // behind (rs_valid).  Small tables: 64 blocks whose partials the consumers add up
+    // themselves (saves a launch).  Large ones: the streaming kernel, then one small kernel
+    // combines the block partials.
+    if (p.carried || (p.big && stream_available(m))) {   // (carried: resolved above)
+        if (!p.carried && (rc = rowsums_from_scratch(m)))
             return rc;
-    } else if (!fused) {
-    if (carried) {                                   // (resolved above)
-        partial_in = m->rs_full;
-        G = 1;
-    } else if (big && stream_available(m)) {
-        rc = rowsums_from_scratch(m);
-        if (rc)
-            return rc;
-        partial_in = m->rs_full;
-        G = 1;
+        pr.partial_in = m->rs_full;
+        pr.G = 1;
     } else {
-        int wpb = (V + G - 1) / G;
-        G = (V + wpb - 1) / wpb;
+        int wpb = 0;
+        const int G = pr.G = rowsum_blocks(V, p.big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, wpb);
         hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0,
                            m->stream, K, V, wpb, m->lambda, m->partial);
         HIP_TRY(hipGetLastError());
-        if (G > trlda::kRowsumBlocks) {
+        if (G > kRowsumBlocks) {
             double *combined = m->partial + (size_t)G * K;       // row G of the same buffer
             hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>,
                                dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
                                dim3(kDenseThreads), 0, m->stream, K, G, m->partial, combined);
             HIP_TRY(hipGetLastError());
-            partial_in = combined;
-            G = 1;
+            pr.partial_in = combined;
+            pr.G = 1;
         }
     }
     if (m->timing && (rc = stamp(m)))
@@ -1828,38 +1922,432 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
     // 2. psiSum + exp E[log beta] (lda.cpp:172-173), on the batch's active words unless the
     // dense preamble was asked for -- or, with exp(psi(lambda)) left behind by the M-step, the K
     // topic factors only (psi_sum: psi of the row sums, the sums, exp(-psi))
-    if (fused_big) {
-        hipLaunchKernelGGL(trlda::topic_factors_kernel<256>, dim3((K + 255) / 256), dim3(256), 0, m->stream, K,
-                           partial_in, m->psi_sum);
+    if (p.fused_big) {
+        hipLaunchKernelGGL(topic_factors_kernel<256>, dim3((K + 255) / 256), dim3(256), 0, m->stream, K,
+                           pr.partial_in, m->psi_sum);
         HIP_TRY(hipGetLastError());
     } else {
         constexpr int TE = 1024;
-        const bool dense = m->dense_preamble;
-        const size_t total = dense ? KV : (size_t)K * (size_t)b->n_active;
-        size_t blocks = (total + TE - 1) / TE;
-        int GE = (int)std::max<size_t>(1, std::min<size_t>(blocks, 256));
-        size_t lds = (size_t)K * 9 * sizeof(double);
-        rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds);
-        if (rc)
+        const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
+        const size_t lds = (size_t)K * 9 * sizeof(double);
+        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds)))
             return rc;
-        hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, G,
-                           m->lambda, partial_in, m->psi_sum, m->eeb_cur,
-                           dense ? nullptr : b->active);
+        hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, pr.G,
+                           m->lambda, pr.partial_in, m->psi_sum, m->eeb_cur, active);
         HIP_TRY(hipGetLastError());
     }
-    if (m->timing && (rc = stamp(m)))
+    return m->timing && (rc = stamp(m)) ? rc : TRLDA_OK;
+}
+
+// K > 128 (or a document kernel asked for): up to 512 topics registers in one orientation
+// (estep_wide.h), the words past the registers in LDS rows; beyond (or on request) the general
+// kernel, slice in LDS when it fits, else streamed
+int launch_wide_or_general(trlda_model *m, const EstepPlan &p, bool wide, trlda::DocKernelArgs &a)
+{
+    using namespace trlda;
+    const int K = p.K, Kp = K | 1;
+    if (wide) {
+        const int lds_rows = wide_lds_rows(p.KS, p.db->max_n);
+        const size_t lds_bytes = wide_lds_doubles(p.KS, lds_rows) * sizeof(double);
+        a.n_cap = 0;
+        a.Kp = 64 * p.KS;
+        if (int rc = ks_dispatch(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                auto kern = p.fused_big ? estep_docs_wide_kernel<KS, true> : estep_docs_wide_kernel<KS, false>;
+                if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes))
+                    return rc;
+                hipLaunchKernelGGL(kern, dim3(p.B), dim3(kWideThreads), lds_bytes, m->stream, a, lds_rows);
+                return (int)TRLDA_OK;
+            }))
+            return rc;
+        HIP_TRY(hipGetLastError());
+        return TRLDA_OK;
+    }
+    const int T = m->sw.doc_threads > 0 ? m->sw.doc_threads : 256;
+    const size_t fixed = docs_lds_bytes(K, Kp, 0, T);
+    const int n_fit = fixed >= (size_t)kLdsDynBytes ? 0 : (int)(((size_t)kLdsDynBytes - fixed) /
+                                                                ((size_t)(Kp + 2) * sizeof(double)));
+    const int gen_cap = std::min(p.db->max_n, n_fit);
+    const size_t lds_bytes = docs_lds_bytes(K, Kp, gen_cap, T);
+    if (lds_bytes > (size_t)kLdsDynBytes)
+        return fail(TRLDA_ERR_ARG, "num_topics too large for the document kernel's LDS layout");
+    a.n_cap = gen_cap;
+    a.Kp = Kp;
+    switch (T) {
+    case 64: return launch_docs<64>(m, a, p.B, lds_bytes);
+    case 128: return launch_docs<128>(m, a, p.B, lds_bytes);
+    case 256: return launch_docs<256>(m, a, p.B, lds_bytes);
+    case 512: return launch_docs<512>(m, a, p.B, lds_bytes);
+    case 1024: return launch_docs<1024>(m, a, p.B, lds_bytes);
+    default: return fail(TRLDA_ERR_ARG, "doc_threads must be 64, 128, 256, 512 or 1024");
+    }
+}
+
+// The K <= 128 document kernels by variant V -- 0: the register kernel, 1 / 2: the tiered kernel
+// with V wave-slices of topics (estep_wide.h) -- and form F -- 0: plain, 1: deferred, 2: merged
+template <int V, int F>
+auto reg_doc_kernel()
+{
+    using namespace trlda;
+    if constexpr (V == 0 && F == 0) return estep_docs_reg_kernel<0>;
+    else if constexpr (V == 0 && F == 1) return estep_docs_reg_deferred_kernel<0>;
+    else if constexpr (V == 0) return estep_docs_reg_merged_kernel<0>;
+    else if constexpr (F == 0) return estep_docs_tiered_kernel<V>;
+    else if constexpr (F == 1) return estep_docs_tiered_deferred_kernel<V>;
+    else return estep_docs_tiered_merged_kernel<V>;
+}
+
+// The K <= 128 document launch of `grid` workgroups in the variant the batch needs, the form told
+// by the extra arguments: none, the deferred statistics' (dg) or the merged launch's (mg, aux).
+// LDS rows only for what the single-orientation body cannot hold in registers (with split
+// documents that is a document beyond the split range).
+template <class... X>
+int launch_reg_docs(trlda_model *m, const EstepPlan &p, unsigned grid, const trlda::DocKernelArgs &a,
+                    const trlda::PreArgs &pre, const X &...x)
+{
+    using namespace trlda;
+    int lds_rows = 0;
+    size_t lds_bytes = kRegLdsBytes;
+    if (p.tiered && p.db->max_n > (p.split ? kSplitSegN * kSplitMaxSeg : kRegMaxN)) {
+        lds_rows = wide_lds_rows(p.KS, p.db->max_n);
+        lds_bytes = std::max(lds_bytes, wide_lds_doubles(p.KS, lds_rows) * sizeof(double));
+    }
+    auto launch = [&](auto kern, auto... rows) {
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes))
+            return rc;
+        CallClock launch_clock;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kRegThreads), lds_bytes, m->stream, a, pre, rows..., x...);
+        if (sizeof...(X) == 1)
+            launch_clock.to(5);                  // (the deferred launch)
+        return (int)TRLDA_OK;
+    };
+    constexpr int F = sizeof...(X);
+    if (!p.tiered)
+        return launch(reg_doc_kernel<0, F>());
+    return p.KS == 1 ? launch(reg_doc_kernel<1, F>(), lds_rows) : launch(reg_doc_kernel<2, F>(), lds_rows);
+}
+
+// the next batch's preamble as workgroups of the document launch (PreArgs), into the prefetch
+// buffer neither this batch nor the carried statistics read
+int next_preamble_args(trlda_model *m, const EstepPlan &p, int cur_buf, trlda::PreArgs &pre)
+{
+    using namespace trlda;
+    const int K = p.K, V = p.V;
+    const size_t KV = (size_t)K * V;
+    int rc = 0;
+    if (!m->eeb_pp[0]) {
+        for (int i = 0; i < 3 && !rc; ++i) {
+            rc = dev_alloc(&m->eeb_pp[i], KV);
+            if (!rc) rc = dev_alloc(&m->partial_pp[i], (size_t)kRowsumBlocks * K);
+            if (!rc) rc = dev_alloc(&m->scale_pp[i], 3 * (size_t)K);
+            if (!rc && hipMemsetAsync(m->eeb_pp[i], 0, KV * sizeof(double), m->stream) != hipSuccess)
+                rc = fail(TRLDA_ERR_HIP, "hipMemsetAsync failed");
+        }
+        if (rc)
+            return rc;
+    }
+    if ((rc = batch_begin(m, p.next)))
+        return rc;
+    int nbuf = 0;
+    while (nbuf == cur_buf || (p.carry && nbuf == m->pending.eeb_buf))
+        ++nbuf;
+    const bool dense = m->sw.dense_preamble;
+    pre.K = K; pre.V = V;
+    pre.G = rowsum_blocks(V, kRowsumBlocks, pre.wpb);
+    pre.total = dense ? KV : (size_t)K * (size_t)p.next->n_active;
+    // ~8 elements per thread: at K = 100, B = 200 about 100 fill workgroups beside the 64
+    // that add up the rows -- three rounds on the 56 CUs the documents leave free.
+    // (Letting them start a few microseconds late, so as not to disturb the documents'
+    // staging, was measured: every s_sleep step made the launch longer.)
+    // (a deferred launch's helpers: 16 per thread, all loads in flight -- estep_kernels.h, FAT)
+    const size_t per = (size_t)kRegThreads * (p.carry ? 16 : 8);
+    pre.nb = pre.G + (int)std::max<size_t>(1, std::min<size_t>((pre.total + per - 1) / per, 448));
+    pre.lambda = m->lambda;
+    pre.partial = m->partial_pp[nbuf];
+    pre.u = m->eeb_pp[nbuf];
+    pre.active = dense ? nullptr : p.next->active;
+    pre.c_out = m->scale_pp[nbuf];
+    pre.c_counter = m->group_counter + kUpdGroups;
+    m->prefetch.valid = true;
+    m->prefetch.batch_id = p.next->id;
+    m->prefetch.version = m->lambda_version;
+    m->prefetch.buf = nbuf;
+    m->prefetch.G = pre.G;
+    m->prefetch.dense = dense;
+    return TRLDA_OK;
+}
+
+// The merged launch's helpers (estep_merged.h, MergedArgs): the topic factors finished in the
+// launch (comb) and the statistics stage (p.merged) -- with what the stage writes into `out`
+trlda::MergedArgs merged_args(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const trlda::PreArgs &pre,
+                              trlda::DocKernelArgs &a, EstepOut &out)
+{
+    using namespace trlda;
+    MergedArgs mg{};
+    mg.first = p.doc_wgs + pre.nb;
+    if (p.comb) {
+        mg.n_comb = kMergedComb;
+        mg.c_rows = m->carry_rows; mg.c_n = m->carry_n; mg.c_base = m->carry_base;
+        mg.c_out = m->scale_comb; mg.c_ready = m->sync_counters + 1;
+        mg.c_target = m->c_ready_total + (unsigned int)kMergedComb;
+        mg.c_flags = m->sync_flags + (size_t)kMergedMaxHelpers * kMergedFlagStride;
+    }
+    mg.epoch = a.epoch; mg.n_docs = p.doc_wgs;
+    mg.tstamps = launch_stamps(m->merged_stamps, 3 * 1024);
+    mg.go_flags = m->sync_flags;
+    mg.K = p.K; mg.V = p.V;
+    if (!p.merged)
+        return mg;
+    mg.N_short = b->n_short; mg.N_long = b->n_long;
+    const int room = std::min(p.cus, kMergedMaxHelpers);
+    mg.n_long = std::min(mg.N_long, room / 2);
+    mg.n_short = mg.N_short > 0
+                     ? std::max(1, std::min((mg.N_short + 8 * kMergedNW - 1) / (8 * kMergedNW), room - mg.n_long))
+                     : 0;
+    // the stage in its 16-slot form (estep_merged.h, merged_stats_slots): a workgroup per
+    // item of a length class, when the batch's items fit the stage's flags
+    static const bool slots_off = [] {
+        const char *e = std::getenv("TRLDA_MERGED_SLOTS");
+        return e && std::atoi(e) == 0;
+    }();
+    std::copy(b->cls_short, b->cls_short + 4, mg.cls_short);
+    std::copy(b->cls_long, b->cls_long + 4, mg.cls_long);
+    const int s_short = merged_slot_short_items(mg.cls_short);
+    const int s_long = deferred_long_items(mg.cls_long);
+    mg.slots = !slots_off && s_short + s_long <= kMergedMaxHelpers;
+    if (mg.slots) {
+        mg.n_short = s_short;
+        mg.n_long = s_long;
+    }
+    mg.desc = reinterpret_cast<const int4 *>(b->mdesc);
+    mg.wdoc = b->wdoc; mg.tw_word = m->tw_word; mg.epg = m->epg; mg.eeb = m->eeb_cur;
+    mg.active_flag = (!out.upd.lambda && !out.active_only) ? b->active_flag : nullptr;
+    mg.docs_done = m->sync_counters;
+    mg.docs_target = m->docs_done_total + (unsigned int)p.doc_wgs;
+    a.done_counter = m->sync_counters;
+    a.done_target = mg.docs_target;
+    a.go_flags = m->sync_flags;
+    a.n_go = mg.n_short + mg.n_long;
+    // what the stage writes: as launch_sstats_update decides it for the kernel of its own
+    const bool positive = out.upd.lambda && mstep_keeps_positive(m, out.upd, b);
+    const bool emit = out.emit_next && out.upd.lambda && out.upd.partial && positive;
+    if (out.upd.lambda)
+        m->lambda_positive = positive;
+    out.upd.u_out = emit ? m->eeb : nullptr;
+    out.upd.group_rows = nullptr; out.upd.group_base = nullptr;
+    out.upd.group_counter = nullptr; out.upd.group_size = 1;
+    out.groups = emit ? mg.n_short + mg.n_long : 0;
+    out.raw_rows = emit;
+    out.partial_rows = mg.n_short + mg.n_long;
+    mg.o = out.upd;
+    return mg;
+}
+
+// The statistics of the call before as workgroups of this launch (estep_merged.h, deferred
+// statistics): from the buffers that call kept apart, into its caller's array.  Returns the
+// helper workgroups: one per item, at most one per CU (deferred_helper: they take their items
+// from a counter)
+int deferred_args(trlda_model *m, const EstepPlan &p, const trlda::PreArgs &pre, trlda::MergedArgs &dg)
+{
+    using namespace trlda;
+    const trlda_batch *pb = m->pending.batch;
+    dg.first = p.doc_wgs + pre.nb;
+    dg.K = p.K; dg.V = p.V;
+    dg.N_short = pb->n_short; dg.N_long = pb->n_long;
+    std::copy(pb->cls_short, pb->cls_short + 4, dg.cls_short);
+    std::copy(pb->cls_long, pb->cls_long + 4, dg.cls_long);
+    dg.n_short = deferred_short_items(dg.cls_short);    // a workgroup per item
+    dg.n_long = deferred_long_items(dg.cls_long);
+    dg.desc = reinterpret_cast<const int4 *>(pb->mdesc);
+    dg.wdoc = pb->wdoc; dg.tw_word = m->pending.tw_word; dg.epg = m->pending.epg;
+    dg.eeb = m->pending.eeb;
+    dg.active_flag = pb->active_flag;
+    dg.o = UpdateOut{};
+    dg.o.sstats = m->pending.sstats;
+    dg.tstamps = launch_stamps(m->deferred_stamps, 3 * 3072);
+    static const int helpers_env = [] {
+        const char *e = std::getenv("TRLDA_DEFER_HELPERS");
+        return e ? std::max(1, std::atoi(e)) : 0;
+    }();
+    const int n_items = pre.nb + dg.n_short + dg.n_long;
+    // As many helpers as the documents leave CUs free: a helper that is only dispatched when
+    // the documents end finds the list empty after a round trip to the counter, and the
+    // launch waits for it (32.1 us per step with one helper per CU, 31.1 with 56:
+    // profiles/r05_deferred_ab.txt) -- more of them only where the list is long for the free
+    // CUs, and one per CU when the documents fill the chip (then everything runs behind them)
+    const int free_cus = p.cus - p.doc_wgs;
+    const int wanted = free_cus >= 32 ? std::max(free_cus, (n_items + 5) / 6) : p.cus;
+    const int H = std::min(n_items, helpers_env > 0 ? helpers_env : wanted);
+    dg.work_counter = m->sync_counters + 32;        // (a cache line of its own)
+    dg.work_base = m->defer_work_total;
+    // every helper resident from the start: its first item is its own index, the counter
+    // hands out the items from H on (one fetch per item in all: each helper's last one finds
+    // nothing); else every item comes from the counter (n_items + H fetches)
+    dg.first_static = (free_cus >= 32 && H <= free_cus) ? H : 0;
+    m->defer_work_total += (unsigned int)(dg.first_static ? n_items : n_items + H);
+    return H;
+}
+
+// Auxiliary workgroups of a merged launch (estep_merged.h, AuxArgs): the next fresh gamma0, when
+// this call's draw asked for it and the CUs the documents leave free take the workgroups in ONE
+// round of at most kAuxMaxChunks chunks each (~2 us a chunk under ~33 us of documents) ...
+int aux_args(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const trlda::DocKernelArgs &a,
+             const trlda::MergedArgs &mg, const trlda::PreArgs &pre, EstepOut &out, trlda::AuxArgs &aux)
+{
+    using namespace trlda;
+    constexpr int kAuxMaxChunks = 6;
+    const int aux_room = p.cus - p.doc_wgs - mg.n_comb - pre.nb;
+    if (m->aux_draw_req.valid && aux_room >= 24 && p.merged) {
+        const long long total = m->aux_draw_req.total;
+        const long long chunks = (total + kAuxChunk - 1) / kAuxChunk;
+        const int cpw = (int)((chunks + aux_room - 1) / aux_room);
+        const int n_draw = (int)((chunks + cpw - 1) / cpw);
+        // (which buffer: not the one this call's E-steps read their gamma0 from)
+        const int which = (a.gamma_in == m->gspec[0] && m->gspec[0]) ? 1 : 0;
+        const uint32_t *mt_stride = nullptr, *mt_total = nullptr;
+        int rc = 0;
+        if (cpw <= kAuxMaxChunks && n_draw < 256 &&
+            !(rc = rng_aux_matrices(m->device, (long long)cpw * kAuxChunk, &mt_stride)) &&
+            !(rc = rng_aux_matrices(m->device, total, &mt_total)) && mt_stride && mt_total &&
+            !(rc = grow(&m->gspec[which], &m->cap_gspec[which], (size_t)total))) {
+            aux.draw.n = n_draw;
+            aux.draw.passes = 100; aux.draw.cpw = cpw;
+            aux.draw.total = total; aux.draw.divisor = 100.;
+            aux.draw.out = m->gspec[which];
+            aux.draw.mt_stride = mt_stride; aux.draw.mt_total = mt_total;
+            // the host stream moves on ahead of its turn (host_rng.cpp: whoever touches the
+            // generator before the claim puts it back, and the draw is repeated in its turn)
+            const uint64_t token = trlda_host::rng_speculate_begin();
+            trlda_host::rng_current_window(aux.draw.w0.w);
+            trlda_host::rng_advance((uint64_t)(100 * total));
+            m->spec.valid = true; m->spec.token = token; m->spec.which = which;
+            m->spec.total = total; m->spec.lo = 0; m->spec.hi = total;
+            m->spec.in_launch = true;
+            ++m->inlaunch_draws;
+        }
+        if (rc)
+            return rc;
+    }
+    m->aux_draw_req.valid = false;
+    // ... and the decay of the words outside the batch (K even: p.merged), which the caller
+    // would otherwise launch behind this kernel
+    if (out.inact_wanted && m->aux_decay && p.merged && aux_room >= 24 && out.inact_a != 0.0 &&
+        b->n_active < p.V) {
+        const StreamGeom g = stream_geometry(p.K, p.V);
+        if (g.vec == 2 && g.P <= 64) {
+            aux.inact.n_vb = g.G;
+            aux.inact.K = p.K; aux.inact.V = p.V; aux.inact.P = g.P; aux.inact.cpb = g.cpb;
+            aux.inact.a = out.inact_a; aux.inact.b = out.inact_b;
+            aux.inact.active_flag = b->active_flag;
+            aux.inact.lambda = m->lambda;
+            // (not rows [0, 64) of m->partial: this launch's documents may be adding up the
+            // row sums its preamble left there)
+            aux.inact.part_static = m->partial + (size_t)kStreamMaxBlocks * p.K;
+            out.inact_rows = g.G;
+            out.inact_part = aux.inact.part_static;
+            ++m->inlaunch_decays;
+        }
+    }
+    aux.n_items = aux.draw.n + aux.inact.n_vb;
+    aux.n = std::min(aux.n_items, std::max(aux_room, 0));
+    aux.work_counter = m->sync_counters + 48;        // (a cache line of its own)
+    aux.work_base = m->aux_work_total;
+    m->aux_work_total += (unsigned int)aux.n_items;  // (one fetch per item in all: each
+                                                     //  workgroup's last one finds nothing)
+    return TRLDA_OK;
+}
+
+// K <= 128: one launch for every document (estep_wide.h), plain, merged or deferred.  Per
+// workgroup up to 128 / 144 / 192 words in registers, beyond that one orientation with the rest
+// in LDS rows or streamed from L2.  (Two variants on two streams, or one behind the other, lost.)
+int launch_reg_family(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const Preamble &pr,
+                      trlda::DocKernelArgs &a, EstepOut &out)
+{
+    using namespace trlda;
+    const trlda_batch *db = p.db;
+    int rc = 0;
+    a.n_cap = 0;
+    a.Kp = p.K;
+    a.pad_meta = db->pad_meta;
+    a.pad_ids = db->pad_ids;
+    if (p.split) {
+        if ((rc = grow(&m->xbuf, &m->cap_xbuf, p.xcount)))
+            return rc;
+        if ((rc = ensure_xerr(m)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(m->xbuf, 0xFF, p.xcount * sizeof(double), m->stream));   // NaN
+        a.pad_meta = db->seg_meta;
+        a.pad_ids = db->seg_ids;
+        a.meta_i4 = 2;
+        a.xbuf = m->xbuf;
+        a.xerr = m->xerr;
+    }
+    // (small: the waves' workgroups behind the long documents' segments)
+    const int n_wgs = p.doc_wgs;
+    m->last_split_wgs = p.small ? p.n_long_wgs - p.n_long : n_wgs - p.B;
+    if (p.small)
+        m->last_doc_kernel = "estep_docs_small_body";
+    PreArgs pre{};
+    pre.n_docs = n_wgs;
+    if (p.pre_next && (rc = next_preamble_args(m, p, pr.cur_buf, pre)))
+        return rc;
+    m->last_merged = p.merged;
+    MergedArgs mg = merged_args(m, b, p, pre, a, out);
+    const int n_help = mg.n_comb + mg.n_short + mg.n_long;
+    if (p.carry) {
+        const trlda_batch *pb = m->pending.batch;
+        MergedArgs dg{};
+        const int H = deferred_args(m, p, pre, dg);
+        if ((rc = launch_reg_docs(m, p, (unsigned)(n_wgs + H), a, pre, dg)))
+            return rc;
+        m->pending.valid = false;
+        const_cast<trlda_batch *>(pb)->pending_in = nullptr;
+        if ((rc = batch_end(m, pb)))
+            return rc;
+    } else if (n_help > 0) {
+        if ((rc = ensure_xerr(m)))
+            return rc;
+        mg.xerr = m->xerr;
+        a.xerr = m->xerr;
+        AuxArgs aux{};
+        if ((rc = aux_args(m, b, p, a, mg, pre, out, aux)))
+            return rc;
+        mg.first += aux.n;
+        a.block0 = mg.n_comb;                // the topic-factor workgroups come first
+        if ((rc = launch_reg_docs(m, p, (unsigned)(mg.first + n_help), a, pre, mg, aux)))
+            return rc;
+        if (p.merged)
+            m->docs_done_total += (unsigned int)n_wgs;
+        m->c_ready_total += (unsigned int)mg.n_comb;
+        ++m->merged_epoch;
+    } else if ((rc = launch_reg_docs(m, p, (unsigned)(n_wgs + pre.nb), a, pre))) {
         return rc;
     }
+    if (pre.nb > 0 && (rc = batch_end(m, p.next)))
+        return rc;
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
 
-    // 3. per-document fixed point (lda.cpp:174-204)
-    if (atomic) {
+// Stage 3: the per-document fixed point (lda.cpp:174-204)
+int estep_documents(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const Preamble &pr,
+                    double *gamma_dev, const double *gamma_in_dev, double threshold, int32_t *iters_dev,
+                    EstepOut &out)
+{
+    using namespace trlda;
+    double *sstats_dev = out.upd.sstats;
+    int rc = 0;
+    if (p.atomic) {
         if (!sstats_dev)
             return fail(TRLDA_ERR_ARG, "internal: atomic statistics need an sstats buffer");
-        HIP_TRY(hipMemsetAsync(sstats_dev, 0, KV * sizeof(double), m->stream));  // lda.cpp:169
+        HIP_TRY(hipMemsetAsync(sstats_dev, 0, (size_t)p.K * p.V * sizeof(double), m->stream));  // lda.cpp:169
     }
-    if (B > 0) {
+    if (p.B > 0) {
+        const trlda_batch *db = p.db;
+        DpContext *dp = m->dp;
+        const int K = p.K;
         DocKernelArgs a;
-        a.K = K; a.B = B;
+        a.K = K; a.B = p.B;
         a.stamps = nullptr;
         a.meta_i4 = 1; a.xbuf = nullptr; a.xerr = nullptr;
 #ifdef TRLDA_STAMPS
@@ -1873,7 +2361,7 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
             g_stamp_buf = stamp_buf;
         }
 #endif
-        a.indptr = db->indptr; a.ids = db->ids; a.cnts = db->cnts;
+        a.indptr = db->indptr; a.ids = db->ids; a.cnts = db->cnts; a.order = db->order;
         a.eeb = m->eeb_cur; a.alpha = m->alpha;
         a.gamma = gamma_dev; a.gamma_in = gamma_in_dev ? gamma_in_dev : gamma_dev;
         if (!gamma_in_dev && gamma_dev == m->gamma && m->gamma0_src) {
@@ -1889,7 +2377,7 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
             a.tw_word = a.epg + dp->tw_off;
             a.wrank = nullptr;
         }
-        if (defer_self) {
+        if (p.defer_self) {
             // kept apart from what the next call writes: its launch reads them (estep_merged.h)
             const int which = 1 - m->dfr_cur;
             if ((rc = ensure_deferred_workspace(m, db, which)))
@@ -1898,483 +2386,71 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
             a.epg = m->dfr_epg_base[which] + K;
             a.tw_word = m->dfr_tw[which];
         }
-        a.sstats_acc = atomic ? sstats_dev : nullptr;
-        a.max_iter = max_iter; a.threshold = threshold; a.iters_out = iters_dev;
-        a.partial = (fused || fused_big) ? partial_in : nullptr;
-        a.scale_in = fused_big ? m->psi_sum : prefetched ? m->scale_pp[cur_buf] : nullptr;
+        a.sstats_acc = p.atomic ? sstats_dev : nullptr;
+        a.max_iter = p.max_iter; a.threshold = threshold; a.iters_out = iters_dev;
+        a.partial = (p.fused || p.fused_big) ? pr.partial_in : nullptr;
+        a.scale_in = p.fused_big ? m->psi_sum : p.prefetched ? m->scale_pp[pr.cur_buf] : nullptr;
         a.done_counter = nullptr; a.scale_wait = nullptr; a.done_target = 0;
         a.go_flags = nullptr; a.n_go = 0; a.block0 = 0;
-        a.docs_per_wg = small ? 8 : 1;
-        a.small_block0 = small ? n_long_wgs : 0;
-        a.small_first = small ? n_long : 0;
+        a.docs_per_wg = p.small ? 8 : 1;
+        a.small_block0 = p.small ? p.n_long_wgs : 0;
+        a.small_first = p.small ? p.n_long : 0;
         a.epoch = m->merged_epoch + 1u;              // (of this launch, if it turns out to be merged)
-        if (comb) {                                  // finished by workgroups of this launch
+        if (p.comb) {                                // finished by workgroups of this launch
             a.scale_in = m->scale_comb;
             a.scale_wait = m->sync_flags + (size_t)trlda::kMergedMaxHelpers * trlda::kMergedFlagStride;
         }
-        a.G = G;
-        a.scale_out = fused ? m->psi_sum : nullptr;
-        const int Kp = K | 1;
-
-        // K <= 128: ONE launch for all documents, ordered by decreasing length -- the register
-        // kernel when none has more than 128 words, else the tiered kernel, whose workgroups
-        // take the variant their own document needs (estep_wide.h).  Everything else: below.
-        int n_reg = 0;
-        if (m->doc_threads == 0 && K <= kRegMaxK && m->doc_kernel == TRLDA_DOCS_AUTO)
-            n_reg = B;
-
-        // 128 < K <= 512, or K <= 128 with more than 192 words: registers in one orientation
-        // (estep_wide.h); it takes every document the register tier does not.  Beyond 512
-        // topics (or on request): the general kernel, slice in LDS when it fits, else streamed.
-        const bool wide = m->doc_threads == 0 && K <= kWideMaxK && m->doc_kernel != TRLDA_DOCS_GENERAL;
-        const int n_stream = B - n_reg;
-
-        if (B - n_reg >= n_reg)
-            m->last_doc_kernel = wide ? "estep_docs_wide_kernel" : "estep_docs_kernel";
+        a.G = pr.G;
+        a.scale_out = p.fused ? m->psi_sum : nullptr;
+        const bool wide = m->sw.doc_threads == 0 && p.K <= kWideMaxK && m->sw.doc_kernel != TRLDA_DOCS_GENERAL;
+        if (p.reg)
+            m->last_doc_kernel = p.tiered ? "estep_docs_tiered_kernel" : "estep_docs_reg_kernel";
         else
-            m->last_doc_kernel = db->max_n <= 128 ? "estep_docs_reg_kernel" : "estep_docs_tiered_kernel";
-        if (wide && B - n_reg > 0) {
-            const int n_wide = B - n_reg;
-            const int KS = (K + kWave - 1) / kWave;
-            int jw = 0;
-            switch (KS) {
-            case 1: jw = wide_cfg<1>::JW; break;
-            case 2: jw = wide_cfg<2>::JW; break;
-            case 3: jw = wide_cfg<3>::JW; break;
-            case 4: jw = wide_cfg<4>::JW; break;
-            case 5: jw = wide_cfg<5>::JW; break;
-            case 6: jw = wide_cfg<6>::JW; break;
-            case 7: jw = wide_cfg<7>::JW; break;
-            default: jw = wide_cfg<8>::JW; break;
-            }
-            // LDS rows for the words past the registers, as many as the longest document needs
-            const size_t fixed = wide_lds_doubles(KS, 0) * sizeof(double);
-            const int fit = (int)(((size_t)kLdsDynBytes - fixed) / ((size_t)(64 * KS + 1) * sizeof(double)));
-            const int lds_rows = std::max(0, std::min(fit, db->max_n - kWideWaves * jw));
-            const size_t lds_bytes = wide_lds_doubles(KS, lds_rows) * sizeof(double);
-            a.n_cap = 0;
-            a.Kp = 64 * KS;
-            a.order = db->order;
-#define TRLDA_LAUNCH_WIDE(KSV)                                                             \
-    do {                                                                                   \
-        auto kern = fused_big ? estep_docs_wide_kernel<KSV, true> : estep_docs_wide_kernel<KSV, false>; \
-        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes)))     \
-            return rc;                                                                     \
-        hipLaunchKernelGGL(kern, dim3(n_wide), dim3(kWideThreads), lds_bytes, m->stream, a, \
-                           lds_rows);                                                      \
-    } while (0)
-            switch (KS) {
-            case 1: TRLDA_LAUNCH_WIDE(1); break;
-            case 2: TRLDA_LAUNCH_WIDE(2); break;
-            case 3: TRLDA_LAUNCH_WIDE(3); break;
-            case 4: TRLDA_LAUNCH_WIDE(4); break;
-            case 5: TRLDA_LAUNCH_WIDE(5); break;
-            case 6: TRLDA_LAUNCH_WIDE(6); break;
-            case 7: TRLDA_LAUNCH_WIDE(7); break;
-            default: TRLDA_LAUNCH_WIDE(8); break;
-            }
-#undef TRLDA_LAUNCH_WIDE
-            HIP_TRY(hipGetLastError());
-        } else if (n_stream > 0) {
-            int T = m->doc_threads > 0 ? m->doc_threads : 256;
-            size_t fixed = docs_lds_bytes(K, Kp, 0, T);
-            int n_fit = fixed >= (size_t)kLdsDynBytes
-                            ? 0
-                            : (int)(((size_t)kLdsDynBytes - fixed) /
-                                    ((size_t)(Kp + 2) * sizeof(double)));
-            int gen_cap = std::min(db->max_n, n_fit);
-            size_t lds_bytes = docs_lds_bytes(K, Kp, gen_cap, T);
-            if (lds_bytes > (size_t)kLdsDynBytes)
-                return fail(TRLDA_ERR_ARG,
-                            "num_topics too large for the document kernel's LDS layout");
-            a.n_cap = gen_cap;
-            a.Kp = Kp;
-            a.order = db->order;
-            switch (T) {
-            case 64: rc = launch_docs<64>(m, a, n_stream, lds_bytes); break;
-            case 128: rc = launch_docs<128>(m, a, n_stream, lds_bytes); break;
-            case 256: rc = launch_docs<256>(m, a, n_stream, lds_bytes); break;
-            case 512: rc = launch_docs<512>(m, a, n_stream, lds_bytes); break;
-            case 1024: rc = launch_docs<1024>(m, a, n_stream, lds_bytes); break;
-            default: return fail(TRLDA_ERR_ARG, "doc_threads must be 64, 128, 256, 512 or 1024");
-            }
-            if (rc)
-                return rc;
-        }
-        if (n_reg > 0) {
-            a.n_cap = 0;
-            a.Kp = K;
-            // One launch.  No document over 128 words: the register kernel.  Else the tiered
-            // kernel: per workgroup up to 128 / 144 / 192 words in the register variants, beyond
-            // that one orientation with the words past the registers in LDS rows (as many as fit)
-            // or streamed from L2.  (Running two variants on two streams was measured and lost:
-            // the event fork/join costs ~12 us; one launch per variant one behind the other made
-            // a batch with a single 193-word document 2.5 times slower.)
-            a.order = db->order;
-            a.pad_meta = db->pad_meta;
-            a.pad_ids = db->pad_ids;
-            const bool tiered = db->max_n > 128;
-            const int KS = (K + kWave - 1) / kWave;              // 1 or 2
-            // Documents of more than 192 words: split over several workgroups that exchange K
-            // sums per iteration (estep_docs_reg_body<0, true>) -- the batch brought the
-            // per-workgroup layout; one row of K doubles per (segment, iteration), NaN before
-            // the launch.  Not with an exchange buffer beyond 256 MB (max_iter in the thousands):
-            // those batches keep one workgroup per document.
-            int n_wgs = small ? small_wgs : n_reg;              // document workgroups of the launch
-            const size_t xcount = (size_t)db->n_xrows * (size_t)(max_iter + 1) * (size_t)K;
-            if (tiered && m->split_docs && db->n_wg > 0 && db->split_pays && max_iter > 0 &&
-                xcount * sizeof(double) <= ((size_t)256 << 20)) {
-                if ((rc = grow(&m->xbuf, &m->cap_xbuf, xcount)))
-                    return rc;
-                if ((rc = ensure_xerr(m)))
-                    return rc;
-                HIP_TRY(hipMemsetAsync(m->xbuf, 0xFF, xcount * sizeof(double), m->stream));   // NaN
-                a.pad_meta = db->seg_meta;
-                a.pad_ids = db->seg_ids;
-                a.meta_i4 = 2;
-                a.xbuf = m->xbuf;
-                a.xerr = m->xerr;
-                n_wgs = small ? small_wgs : db->n_wg;   // (the waves' workgroups behind the long documents' segments)
-            }
-            const bool split = a.meta_i4 == 2;
-            m->last_split_wgs = small ? n_long_wgs - n_long : n_wgs - n_reg;
-            if (small)
-                m->last_doc_kernel = "estep_docs_small_body";
-            int lds_rows = 0;
-            size_t lds_bytes = kRegLdsBytes;
-            // (LDS rows only for what the single-orientation body cannot hold in registers:
-            // with split documents that is a document beyond the split range)
-            if (tiered && db->max_n > (split ? kSplitSegN * kSplitMaxSeg : kRegMaxN)) {
-                const int jw = KS == 1 ? wide_cfg<1>::JW : wide_cfg<2>::JW;
-                const size_t fixed = wide_lds_doubles(KS, 0) * sizeof(double);
-                const int fit = (int)(((size_t)kLdsDynBytes - fixed) / ((size_t)(64 * KS + 1) * sizeof(double)));
-                lds_rows = std::max(0, std::min(fit, db->max_n - kWideWaves * jw));
-                lds_bytes = std::max(lds_bytes, wide_lds_doubles(KS, lds_rows) * sizeof(double));
-            }
-            const void *kern_ptr = !tiered ? reinterpret_cast<const void *>(estep_docs_reg_kernel<0>)
-                                   : KS == 1 ? reinterpret_cast<const void *>(estep_docs_tiered_kernel<1>)
-                                             : reinterpret_cast<const void *>(estep_docs_tiered_kernel<2>);
-            if ((rc = ensure_dynamic_lds(kern_ptr, lds_bytes)))
-                return rc;
-            // the next batch's preamble as extra workgroups of this launch (PreArgs): when the
-            // caller announced it, it fits the same path, and lambda is not about to change
-            PreArgs pre{};
-            pre.n_docs = n_wgs;
-            if (next && fused && n_reg == B && !out.upd.lambda && !atomic && next->V == V &&
-                next->device == m->device && next->B > 0 && !m->lambda_exposed && m->prefetch_next) {
-                if (!m->eeb_pp[0]) {
-                    for (int i = 0; i < 3 && !rc; ++i) {
-                        rc = dev_alloc(&m->eeb_pp[i], KV);
-                        if (!rc) rc = dev_alloc(&m->partial_pp[i], (size_t)kRowsumBlocks * K);
-                        if (!rc) rc = dev_alloc(&m->scale_pp[i], 3 * (size_t)K);
-                        if (!rc && hipMemsetAsync(m->eeb_pp[i], 0, KV * sizeof(double), m->stream) != hipSuccess)
-                            rc = fail(TRLDA_ERR_HIP, "hipMemsetAsync failed");
-                    }
-                    if (rc)
-                        return rc;
-                }
-                if ((rc = batch_begin(m, next)))
-                    return rc;
-                // (not the buffer this batch reads, nor the one the carried statistics read)
-                int nbuf = 0;
-                while (nbuf == cur_buf || (carry && nbuf == m->pending.eeb_buf))
-                    ++nbuf;
-                const bool dense = m->dense_preamble;
-                pre.K = K; pre.V = V;
-                pre.G = std::min(kRowsumBlocks, std::max(1, V / 32));
-                pre.wpb = (V + pre.G - 1) / pre.G;
-                pre.G = (V + pre.wpb - 1) / pre.wpb;
-                pre.total = dense ? KV : (size_t)K * (size_t)next->n_active;
-                // ~8 elements per thread: at K = 100, B = 200 about 100 fill workgroups beside the 64
-                // that add up the rows -- three rounds on the 56 CUs the documents leave free.
-                // (Letting them start a few microseconds late, so as not to disturb the documents'
-                // staging, was measured: every s_sleep step made the launch longer.)
-                // (a deferred launch's helpers: 16 per thread, all loads in flight -- estep_kernels.h, FAT)
-                const size_t per = (size_t)kRegThreads * (carry ? 16 : 8);
-                pre.nb = pre.G + (int)std::max<size_t>(1, std::min<size_t>((pre.total + per - 1) / per, 448));
-                pre.lambda = m->lambda;
-                pre.partial = m->partial_pp[nbuf];
-                pre.u = m->eeb_pp[nbuf];
-                pre.active = dense ? nullptr : next->active;
-                pre.c_out = m->scale_pp[nbuf];
-                pre.c_counter = m->group_counter + kUpdGroups;
-                m->prefetch.valid = true;
-                m->prefetch.batch_id = next->id;
-                m->prefetch.version = m->lambda_version;
-                m->prefetch.buf = nbuf;
-                m->prefetch.G = pre.G;
-                m->prefetch.dense = dense;
-            }
-            // The statistics (and what rides on them: M-step, row sums, the next preamble) as
-            // workgroups of this launch (estep_merged.h): small batches whose words' lists the
-            // stage's waves hold in one piece, pairs of topics per lane
-            // (a long list goes to the stage's sixteen chunks of at most 16 entries: 256 entries --
-            // a list can be longer than B when ids repeat within documents)
-            const bool merged_stats = !launch_ok &&
-                                      merged_capable && n_wgs == doc_wgs && K % 2 == 0 && m->pair_gathers &&
-                                      b->long_len == trlda::kLongWord && b->B <= 256 && b->max_list <= 256 &&
-                                      b->n_active > 0 &&
-                                      fused_update_available(m) &&
-                                      (out.upd.lambda ? out.active_only
-                                                      : sstats_dev != nullptr && m->merged_launch >= 2);
-            m->last_merged = merged_stats;
-            MergedArgs mg{};
-            mg.first = n_wgs + pre.nb;
-            if (comb) {
-                mg.n_comb = trlda::kMergedComb;
-                mg.c_rows = m->carry_rows; mg.c_n = m->carry_n; mg.c_base = m->carry_base;
-                mg.c_out = m->scale_comb; mg.c_ready = m->sync_counters + 1;
-                mg.c_target = m->c_ready_total + (unsigned int)trlda::kMergedComb;
-                mg.c_flags = m->sync_flags + (size_t)trlda::kMergedMaxHelpers * trlda::kMergedFlagStride;
-            }
-            mg.epoch = a.epoch; mg.n_docs = n_wgs;
-
-            {
-                static const bool want_stamps = std::getenv("TRLDA_MERGED_STAMPS") != nullptr;
-                if (want_stamps && !m->merged_stamps && dev_alloc(&m->merged_stamps, 3 * 1024) == TRLDA_OK)
-                    (void)hipMemset(m->merged_stamps, 0, 3 * 1024 * sizeof(unsigned long long));
-                mg.tstamps = want_stamps ? m->merged_stamps : nullptr;
-            }
-            mg.go_flags = m->sync_flags;
-            mg.K = K; mg.V = V;
-            if (merged_stats) {
-                mg.N_short = b->n_short; mg.N_long = b->n_long;
-                const int room = std::min(cus, trlda::kMergedMaxHelpers);
-                mg.n_long = std::min(mg.N_long, room / 2);
-                mg.n_short = mg.N_short > 0
-                                 ? std::max(1, std::min((mg.N_short + 8 * trlda::kMergedNW - 1) / (8 * trlda::kMergedNW),
-                                                        room - mg.n_long))
-                                 : 0;
-                // the stage in its 16-slot form (estep_merged.h, merged_stats_slots): a workgroup per
-                // item of a length class, when the batch's items fit the stage's flags
-                static const bool slots_off = [] {
-                    const char *e = std::getenv("TRLDA_MERGED_SLOTS");
-                    return e && std::atoi(e) == 0;
-                }();
-                for (int c = 0; c < 4; ++c) {
-                    mg.cls_short[c] = b->cls_short[c];
-                    mg.cls_long[c] = b->cls_long[c];
-                }
-                const int s_short = trlda::merged_slot_short_items(mg.cls_short);
-                const int s_long = trlda::deferred_long_items(mg.cls_long);
-                mg.slots = !slots_off && s_short + s_long <= trlda::kMergedMaxHelpers;
-                if (mg.slots) {
-                    mg.n_short = s_short;
-                    mg.n_long = s_long;
-                }
-                mg.desc = reinterpret_cast<const int4 *>(b->mdesc);
-                mg.wdoc = b->wdoc; mg.tw_word = m->tw_word; mg.epg = m->epg; mg.eeb = m->eeb_cur;
-                mg.active_flag = (!out.upd.lambda && !out.active_only) ? b->active_flag : nullptr;
-                mg.docs_done = m->sync_counters;
-                mg.docs_target = m->docs_done_total + (unsigned int)n_wgs;
-                a.done_counter = m->sync_counters;
-                a.done_target = mg.docs_target;
-                a.go_flags = m->sync_flags;
-                a.n_go = mg.n_short + mg.n_long;
-                // what the stage writes: as launch_sstats_update decides it for the kernel of its own
-                const bool positive = out.upd.lambda && mstep_keeps_positive(m, out.upd, b);
-                const bool emit = out.emit_next && out.upd.lambda && out.upd.partial && positive;
-                if (out.upd.lambda)
-                    m->lambda_positive = positive;
-                out.upd.u_out = emit ? m->eeb : nullptr;
-                out.upd.group_rows = nullptr; out.upd.group_base = nullptr;
-                out.upd.group_counter = nullptr; out.upd.group_size = 1;
-                out.groups = emit ? mg.n_short + mg.n_long : 0;
-                out.raw_rows = emit;
-                out.partial_rows = mg.n_short + mg.n_long;
-                mg.o = out.upd;
-            }
-            const int n_help = mg.n_comb + mg.n_short + mg.n_long;
-            if (carry) {
-                // the statistics of the call before as workgroups of this launch (estep_merged.h,
-                // deferred statistics): from the buffers that call kept apart, into its caller's array
-                const trlda_batch *pb = m->pending.batch;
-                MergedArgs dg{};
-                dg.first = n_wgs + pre.nb;
-                dg.K = K; dg.V = V;
-                dg.N_short = pb->n_short; dg.N_long = pb->n_long;
-                for (int c = 0; c < 4; ++c) {
-                    dg.cls_short[c] = pb->cls_short[c];
-                    dg.cls_long[c] = pb->cls_long[c];
-                }
-                dg.n_short = trlda::deferred_short_items(dg.cls_short);    // a workgroup per item
-                dg.n_long = trlda::deferred_long_items(dg.cls_long);
-                dg.desc = reinterpret_cast<const int4 *>(pb->mdesc);
-                dg.wdoc = pb->wdoc; dg.tw_word = m->pending.tw_word; dg.epg = m->pending.epg;
-                dg.eeb = m->pending.eeb;
-                dg.active_flag = pb->active_flag;
-                dg.o = trlda::UpdateOut{};
-                dg.o.sstats = m->pending.sstats;
-                {
-                    static const bool want_stamps = std::getenv("TRLDA_MERGED_STAMPS") != nullptr;
-                    if (want_stamps && !m->deferred_stamps && dev_alloc(&m->deferred_stamps, 3 * 3072) == TRLDA_OK)
-                        (void)hipMemset(m->deferred_stamps, 0, 3 * 3072 * sizeof(unsigned long long));
-                    dg.tstamps = want_stamps ? m->deferred_stamps : nullptr;
-                }
-                const void *dk = !tiered ? reinterpret_cast<const void *>(estep_docs_reg_deferred_kernel<0>)
-                                 : KS == 1 ? reinterpret_cast<const void *>(estep_docs_tiered_deferred_kernel<1>)
-                                           : reinterpret_cast<const void *>(estep_docs_tiered_deferred_kernel<2>);
-                if ((rc = ensure_dynamic_lds(dk, lds_bytes)))
-                    return rc;
-                // helper workgroups: one per item, at most one per CU (estep_merged.h, deferred_helper:
-                // they take their items from a counter)
-                static const int helpers_env = [] {
-                    const char *e = std::getenv("TRLDA_DEFER_HELPERS");
-                    return e ? std::max(1, std::atoi(e)) : 0;
-                }();
-                const int n_items = pre.nb + dg.n_short + dg.n_long;
-                // As many helpers as the documents leave CUs free: a helper that is only dispatched when
-                // the documents end finds the list empty after a round trip to the counter, and the
-                // launch waits for it (32.1 us per step with one helper per CU, 31.1 with 56:
-                // profiles/r05_deferred_ab.txt) -- more of them only where the list is long for the free
-                // CUs, and one per CU when the documents fill the chip (then everything runs behind them)
-                const int free_cus = cus - n_wgs;
-                const int wanted = free_cus >= 32 ? std::max(free_cus, (n_items + 5) / 6) : cus;
-                const int H = std::min(n_items, helpers_env > 0 ? helpers_env : wanted);
-                dg.work_counter = m->sync_counters + 32;        // (a cache line of its own)
-                dg.work_base = m->defer_work_total;
-                // every helper resident from the start: its first item is its own index, the counter
-                // hands out the items from H on (one fetch per item in all: each helper's last one finds
-                // nothing); else every item comes from the counter (n_items + H fetches)
-                static const bool no_static = std::getenv("TRLDA_DEFER_STATIC0") != nullptr;   // (A/B)
-                dg.first_static = (!no_static && free_cus >= 32 && H <= free_cus) ? H : 0;
-                m->defer_work_total += (unsigned int)(dg.first_static ? n_items : n_items + H);
-                const dim3 grid((unsigned)(n_wgs + H));
-                CallClock launch_clock;
-                if (!tiered)
-                    hipLaunchKernelGGL(estep_docs_reg_deferred_kernel<0>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, dg);
-                else if (KS == 1)
-                    hipLaunchKernelGGL(estep_docs_tiered_deferred_kernel<1>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, lds_rows, dg);
-                else
-                    hipLaunchKernelGGL(estep_docs_tiered_deferred_kernel<2>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, lds_rows, dg);
-                launch_clock.to(5);
-                m->pending.valid = false;
-                const_cast<trlda_batch *>(pb)->pending_in = nullptr;
-                if ((rc = batch_end(m, pb)))
-                    return rc;
-            } else if (n_help > 0) {
-                if ((rc = ensure_xerr(m)))
-                    return rc;
-                mg.xerr = m->xerr;
-                a.xerr = m->xerr;
-                // auxiliary workgroups (estep_merged.h, AuxArgs): the next fresh gamma0, when this call's
-                // draw asked for it and the CUs the documents leave free take the workgroups in ONE round
-                // of at most kAuxMaxChunks chunks each (~2 us a chunk under ~33 us of documents)
-                trlda::AuxArgs aux{};
-                constexpr int kAuxMaxChunks = 6;
-                const int aux_room = cus - n_wgs - mg.n_comb - pre.nb;
-                if (m->aux_draw_req.valid && aux_room >= 24 && merged_stats) {
-                    const long long total = m->aux_draw_req.total;
-                    const long long chunks = (total + trlda::kAuxChunk - 1) / trlda::kAuxChunk;
-                    const int cpw = (int)((chunks + aux_room - 1) / aux_room);
-                    const int n_draw = (int)((chunks + cpw - 1) / cpw);
-                    // (which buffer: not the one this call's E-steps read their gamma0 from)
-                    const int which = (a.gamma_in == m->gspec[0] && m->gspec[0]) ? 1 : 0;
-                    const uint32_t *mt_stride = nullptr, *mt_total = nullptr;
-                    if (cpw <= kAuxMaxChunks && n_draw < 256 &&
-                        !(rc = rng_aux_matrices(m->device, (long long)cpw * trlda::kAuxChunk, &mt_stride)) &&
-                        !(rc = rng_aux_matrices(m->device, total, &mt_total)) && mt_stride && mt_total &&
-                        !(rc = grow(&m->gspec[which], &m->cap_gspec[which], (size_t)total))) {
-                        aux.draw.n = n_draw;
-                        aux.draw.passes = 100; aux.draw.cpw = cpw;
-                        aux.draw.total = total; aux.draw.divisor = 100.;
-                        aux.draw.out = m->gspec[which];
-                        aux.draw.mt_stride = mt_stride; aux.draw.mt_total = mt_total;
-                        // the host stream moves on ahead of its turn (host_rng.cpp: whoever touches the
-                        // generator before the claim puts it back, and the draw is repeated in its turn)
-                        const uint64_t token = trlda_host::rng_speculate_begin();
-                        trlda_host::rng_current_window(aux.draw.w0.w);
-                        trlda_host::rng_advance((uint64_t)(100 * total));
-                        m->spec.valid = true; m->spec.token = token; m->spec.which = which;
-                        m->spec.total = total; m->spec.lo = 0; m->spec.hi = total;
-                        m->spec.in_launch = true;
-                        ++m->inlaunch_draws;
-                    }
-                    if (rc)
-                        return rc;
-                }
-                m->aux_draw_req.valid = false;
-                // ... and the decay of the words outside the batch (K even: merged_stats), which the
-                // caller would otherwise launch behind this kernel
-                if (out.inact_wanted && m->aux_decay && merged_stats && aux_room >= 24 && out.inact_a != 0.0 &&
-                    b->n_active < V) {
-                    const trlda::StreamGeom g = trlda::stream_geometry(K, V);
-                    if (g.vec == 2 && g.P <= 64) {
-                        aux.inact.n_vb = g.G;
-                        aux.inact.K = K; aux.inact.V = V; aux.inact.P = g.P; aux.inact.cpb = g.cpb;
-                        aux.inact.a = out.inact_a; aux.inact.b = out.inact_b;
-                        aux.inact.active_flag = b->active_flag;
-                        aux.inact.lambda = m->lambda;
-                        // (not rows [0, 64) of m->partial: this launch's documents may be adding up the
-                        // row sums its preamble left there)
-                        aux.inact.part_static = m->partial + (size_t)trlda::kStreamMaxBlocks * K;
-                        out.inact_rows = g.G;
-                        out.inact_part = aux.inact.part_static;
-                        ++m->inlaunch_decays;
-                    }
-                }
-                aux.n_items = aux.draw.n + aux.inact.n_vb;
-                aux.n = std::min(aux.n_items, std::max(aux_room, 0));
-                aux.work_counter = m->sync_counters + 48;        // (a cache line of its own)
-                aux.work_base = m->aux_work_total;
-                m->aux_work_total += (unsigned int)aux.n_items;  // (one fetch per item in all: each
-                                                                 //  workgroup's last one finds nothing)
-                mg.first += aux.n;
-                const void *mk = !tiered ? reinterpret_cast<const void *>(estep_docs_reg_merged_kernel<0>)
-                                 : KS == 1 ? reinterpret_cast<const void *>(estep_docs_tiered_merged_kernel<1>)
-                                           : reinterpret_cast<const void *>(estep_docs_tiered_merged_kernel<2>);
-                if ((rc = ensure_dynamic_lds(mk, lds_bytes)))
-                    return rc;
-                a.block0 = mg.n_comb;                // the topic-factor workgroups come first
-                const dim3 grid((unsigned)(mg.first + n_help));
-                if (!tiered)
-                    hipLaunchKernelGGL(estep_docs_reg_merged_kernel<0>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, mg, aux);
-                else if (KS == 1)
-                    hipLaunchKernelGGL(estep_docs_tiered_merged_kernel<1>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, lds_rows, mg, aux);
-                else
-                    hipLaunchKernelGGL(estep_docs_tiered_merged_kernel<2>, grid, dim3(kRegThreads), lds_bytes,
-                                       m->stream, a, pre, lds_rows, mg, aux);
-                if (merged_stats)
-                    m->docs_done_total += (unsigned int)n_wgs;
-                m->c_ready_total += (unsigned int)mg.n_comb;
-                ++m->merged_epoch;
-            } else if (!tiered)
-                hipLaunchKernelGGL(estep_docs_reg_kernel<0>, dim3(n_wgs + pre.nb), dim3(kRegThreads),
-                                   lds_bytes, m->stream, a, pre);
-            else if (KS == 1)
-                hipLaunchKernelGGL(estep_docs_tiered_kernel<1>, dim3(n_wgs + pre.nb), dim3(kRegThreads),
-                                   lds_bytes, m->stream, a, pre, lds_rows);
-            else
-                hipLaunchKernelGGL(estep_docs_tiered_kernel<2>, dim3(n_wgs + pre.nb), dim3(kRegThreads),
-                                   lds_bytes, m->stream, a, pre, lds_rows);
-            if (pre.nb > 0 && (rc = batch_end(m, next)))
-                return rc;
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (m->timing && (rc = stamp(m)))
-        return rc;
-
-    if (dp) {                                        // dp_kernels.h
-        if ((rc = batch_end(m, db)) || (rc = dp_exchange(m, b)))
+            m->last_doc_kernel = wide ? "estep_docs_wide_kernel" : "estep_docs_kernel";
+        rc = p.reg ? launch_reg_family(m, b, p, pr, a, out) : launch_wide_or_general(m, p, wide, a);
+        if (rc)
             return rc;
     }
+    return m->timing && (rc = stamp(m)) ? rc : TRLDA_OK;
+}
 
-    // 4. sufficient statistics (lda.cpp:207-217), with the M-step and the next row sums where
-    // the caller asked for them
-    if (atomic) {
-        size_t blocks = (KV / 2 + kDenseThreads * 4 - 1) / (kDenseThreads * 4);
-        int GF = (int)std::max<size_t>(1, std::min<size_t>(blocks, 256 * 8));
-        hipLaunchKernelGGL((elementwise_stream_kernel<kDenseThreads, FinishOp>), dim3(GF),
-                           dim3(kDenseThreads), 0, m->stream, KV, FinishOp{m->eeb_cur, sstats_dev});
-    } else if (m->last_merged && !dp) {
-        // (statistics: workgroups of the document launch above)
-    } else if (defer_self) {
+// one wavefront per word; 16 words per workgroup for small K, 8 from K = 256 on
+template <int TS>
+int launch_sstats_words(trlda_model *m, const trlda_batch *b, double *sstats_dev)
+{
+    using namespace trlda;
+    DpContext *dp = m->dp;
+    const int K = m->K, V = m->V;
+    constexpr int wpb = TS / kWave;
+    const int G_short = (V + wpb - 1) / wpb;
+    const size_t lds = (size_t)wpb * K * sizeof(double);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(sstats_words_kernel<TS>), lds))
+        return rc;
+    hipLaunchKernelGGL(sstats_words_kernel<TS>, dim3(G_short + b->n_long), dim3(TS), lds, m->stream, K, V,
+                       G_short, b->long_len, b->wptr, dp ? b->dp_wrow : b->wdoc, b->long_words,
+                       dp ? TwView{m->dp_gather, b->dp_wsrc} : TwView{m->tw_word, nullptr},
+                       dp ? m->dp_gather : m->epg, m->eeb_cur, sstats_dev);
+    return TRLDA_OK;
+}
+
+// Stage 4: the sufficient statistics (lda.cpp:207-217), with the M-step and the next row sums
+// where the caller asked for them
+int estep_statistics(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const Preamble &pr, EstepOut &out)
+{
+    using namespace trlda;
+    DpContext *dp = m->dp;
+    double *sstats_dev = out.upd.sstats;
+    int rc = 0;
+    if (dp) {                                        // dp_kernels.h
+        if ((rc = batch_end(m, p.db)) || (rc = dp_exchange(m, b)))
+            return rc;
+    }
+    if (p.atomic) {
+        if ((rc = launch_elementwise(m, (size_t)p.K * p.V, FinishOp{m->eeb_cur, sstats_dev})))
+            return rc;
+    } else if (p.merged) {
+        // (statistics: workgroups of the document launch)
+    } else if (p.defer_self) {
         // (statistics: workgroups of the NEXT call's document launch, or flush_pending)
         // (a batch remembers ONE model whose pending statistics read it: another model's go first)
         if (b->pending_in && b->pending_in != m && (rc = flush_pending(b->pending_in)))
@@ -2382,10 +2458,10 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
         m->pending.valid = true;
         m->pending.batch = b;
         m->pending.sstats = sstats_dev;
-        m->pending.epg = m->dfr_epg_base[m->dfr_cur] + K;
+        m->pending.epg = m->dfr_epg_base[m->dfr_cur] + p.K;
         m->pending.tw_word = m->dfr_tw[m->dfr_cur];
         m->pending.eeb = m->eeb_cur;
-        m->pending.eeb_buf = prefetched ? cur_buf : -1;
+        m->pending.eeb_buf = p.prefetched ? pr.cur_buf : -1;
         const_cast<trlda_batch *>(b)->pending_in = m;
         m->last_deferred = true;
     } else if (dp && dp->word_sharded && out.upd.lambda && !out.upd.sstats) {
@@ -2399,13 +2475,9 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
         part.upd.partial = nullptr;
         part.emit_next = false;
         const int r = dp->rank;
-        if (out.active_only) {
-            part.slice_lo = b->ws_acuts[(size_t)r];
-            part.slice_n = b->ws_acuts[(size_t)r + 1] - part.slice_lo;
-        } else {
-            part.slice_lo = b->ws_wcuts[(size_t)r];
-            part.slice_n = b->ws_wcuts[(size_t)r + 1] - part.slice_lo;
-        }
+        const std::vector<int32_t> &cuts = out.active_only ? b->ws_acuts : b->ws_wcuts;
+        part.slice_lo = cuts[(size_t)r];
+        part.slice_n = cuts[(size_t)r + 1] - part.slice_lo;
         part.long_lo = b->ws_lcuts[(size_t)r];
         part.long_n = b->ws_lcuts[(size_t)r + 1] - part.long_lo;
         part.vl_lo = b->ws_vcuts[(size_t)r];
@@ -2417,32 +2489,14 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
         out.partial_rows = 0;
         m->last_word_sharded = true;
     } else if (fused_update_available(m)) {
-        rc = sstats_update_device(m, b, out);
-        if (rc)
+        if ((rc = sstats_update_device(m, b, out)))
             return rc;
     } else {
         if (!sstats_dev)
             return fail(TRLDA_ERR_ARG, "internal: the statistics need an sstats buffer");
-        // one wavefront per word; 16 words per workgroup for small K, 8 from K = 256 on
-#define TRLDA_LAUNCH_SSTATS(TS)                                                            \
-    do {                                                                                   \
-        constexpr int wpb = TS / kWave;                                                    \
-        const int G_short = (V + wpb - 1) / wpb;                                           \
-        size_t lds = (size_t)wpb * K * sizeof(double);                                     \
-        auto kern = sstats_words_kernel<TS>;                                               \
-        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds)))           \
-            return rc;                                                                     \
-        hipLaunchKernelGGL(kern, dim3(G_short + b->n_long), dim3(TS), lds, m->stream, K, V, \
-                           G_short, b->long_len, b->wptr, dp ? b->dp_wrow : b->wdoc, b->long_words, \
-                           dp ? trlda::TwView{m->dp_gather, b->dp_wsrc}                    \
-                              : trlda::TwView{m->tw_word, nullptr},                        \
-                           dp ? m->dp_gather : m->epg, m->eeb_cur, sstats_dev);            \
-    } while (0)
-        if (K >= 256)
-            TRLDA_LAUNCH_SSTATS(512);
-        else
-            TRLDA_LAUNCH_SSTATS(1024);
-#undef TRLDA_LAUNCH_SSTATS
+        if ((rc = p.K >= 256 ? launch_sstats_words<512>(m, b, sstats_dev)
+                             : launch_sstats_words<1024>(m, b, sstats_dev)))
+            return rc;
     }
     HIP_TRY(hipGetLastError());
     // the sixth event follows the fifth at once: the interval between them is what two
@@ -2453,6 +2507,22 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepO
     return batch_end(m, b);
 }
 
+// The E-step launch sequence on the model's stream (no synchronisation).  `out` says what the
+// statistics stage writes; an M-step in it (out.upd.lambda) needs fused_update_available().
+int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, EstepOut &out,
+                 int max_iter, double threshold, int32_t *iters_dev,
+                 const double *gamma_in_dev = nullptr, const trlda_batch *next = nullptr)
+{
+    EstepPlan p;
+    Preamble pr;
+    int rc = estep_begin(m, b, out, max_iter, next, p);
+    if (!rc)
+        rc = estep_preamble(m, b, p, pr);
+    if (!rc)
+        rc = estep_documents(m, b, p, pr, gamma_dev, gamma_in_dev, threshold, iters_dev, out);
+    return rc ? rc : estep_statistics(m, b, p, pr, out);
+}
+
 // sstats-only form (the E-step entry points)
 int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, double *sstats_dev,
                  int max_iter, double threshold, int32_t *iters_dev,
@@ -2460,17 +2530,6 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, double
 {
     EstepOut out(sstats_dev);
     return estep_device(m, b, gamma_dev, out, max_iter, threshold, iters_dev, gamma_in_dev);
-}
-
-template <class Op>
-int launch_elementwise(trlda_model *m, size_t total, const Op &op)
-{
-    size_t blocks = (total / 2 + kDenseThreads * 4 - 1) / (kDenseThreads * 4);
-    int G = (int)std::max<size_t>(1, std::min<size_t>(blocks, 256 * 8));
-    hipLaunchKernelGGL((trlda::elementwise_stream_kernel<kDenseThreads, Op>), dim3(G),
-                       dim3(kDenseThreads), 0, m->stream, total, op);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
 }
 
 int blend_device(trlda_model *m, const double *lambda_prime, const double *sstats, double rho,
@@ -3440,17 +3499,7 @@ int trlda_batch_create(trlda_batch **out, int device, int V, int B, const int32_
         b->id = next_id.fetch_add(1);
     }
     b->device = device; b->V = V; b->B = B; b->nnz = nnz; b->max_n = max_n;
-    {
-        static std::atomic<int> cus_cache[64];
-        int cus = device < 64 ? cus_cache[device].load(std::memory_order_relaxed) : 0;
-        if (cus <= 0) {
-            cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-            if (device < 64)
-                cus_cache[device].store(cus, std::memory_order_relaxed);
-        }
-        b->cus = cus;
-    }
+    b->cus = device_cus(device);
     b->slot = st;
     trlda_host::WorkQueue &queue = index_queue();
     if (queue.threads() <= 0) {
@@ -3656,13 +3705,6 @@ int model_create(trlda_model **out, int device, int K, int V, int stream_priorit
         return rc;
     trlda_model *m = new trlda_model();
     m->device = device; m->K = K; m->V = V;
-    if (const char *env = std::getenv("TRLDA_PAIR_GATHERS"))   // measurements
-        m->pair_gathers = std::atoi(env) != 0;
-    if (const char *env = std::getenv("TRLDA_DOC_KERNEL")) {   // measurements: force a document kernel
-        const std::string v(env);
-        m->doc_kernel = v == "wide" ? TRLDA_DOCS_WIDE : v == "general" ? TRLDA_DOCS_GENERAL
-                                                                       : TRLDA_DOCS_AUTO;
-    }
     size_t KV = (size_t)K * V;
     if (lane_of) {
         // a stream lane: lambda and alpha are its owner's (no allocation of its own); what a
@@ -3686,7 +3728,7 @@ int model_create(trlda_model **out, int device, int K, int V, int stream_priorit
         LiveStreams &ls = live_own_streams();
         std::lock_guard<std::mutex> lock(ls.mu);
         ls.own.insert(m->own_stream);
-    } else if (!rc && !std::getenv("TRLDA_NULL_STREAM")) {
+    } else if (!rc) {
         hipError_t e = stream_priority != 0
                            ? hipStreamCreateWithPriority(&m->own_stream, hipStreamNonBlocking, stream_priority)
                            : hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);
@@ -3736,22 +3778,14 @@ int model_create(trlda_model **out, int device, int K, int V, int stream_priorit
         trlda_model_destroy(m);
         return rc;
     }
-    if (const char *env = std::getenv("TRLDA_SMALL_K"))          // 0: never a wave per document (A/B)
-        m->small_k = env[0] == '0' ? 0 : -1;
     if (const char *env = std::getenv("TRLDA_AUX_DECAY"))        // 0: the streaming kernel behind the launch
         m->aux_decay = env[0] != '0';
     if (const char *env = std::getenv("TRLDA_DRAW_AHEAD")) {     // 0 / 1 / 2: trlda_model_set_draw_ahead
         m->draw_ahead = env[0] == '1';
         m->draw_inlaunch = env[0] == '2';
     }
-    if (const char *env = std::getenv("TRLDA_SPLIT_LISTS"))
-        m->split_long_lists = env[0] != '0';
-    if (const char *env = std::getenv("TRLDA_TILED_TASKS"))
-        m->tiled_tasks = env[0] != '0';
     if (const char *env = std::getenv("TRLDA_BIG_EMIT"))
-        m->big_emit = env[0] != '0';
-    if (const char *env = std::getenv("TRLDA_MERGED"))           // 0 = statistics always a launch of their own
-        m->merged_launch = std::max(0, std::min(std::atoi(env), 2));
+        m->sw.big_emit = env[0] != '0';
     *out = m;
     return TRLDA_OK;
 }
@@ -3887,7 +3921,7 @@ int trlda_model_set_sstats_mode(trlda_model *m, int mode)
         return fail(TRLDA_ERR_ARG, "model is NULL");
     if (mode != TRLDA_SSTATS_SEGMENTED && mode != TRLDA_SSTATS_ATOMIC)
         return fail(TRLDA_ERR_ARG, "unknown sstats mode");
-    m->sstats_mode = mode;
+    m->sw.sstats_mode = mode;
     return TRLDA_OK;
 }
 
@@ -3895,7 +3929,7 @@ int trlda_model_set_dense_preamble(trlda_model *m, int dense)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->dense_preamble = dense != 0;
+    m->sw.dense_preamble = dense != 0;
     return TRLDA_OK;
 }
 
@@ -3907,7 +3941,7 @@ int trlda_model_set_split_preamble(trlda_model *m, int split)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "null model");
-    m->split_preamble = split != 0;
+    m->sw.split_preamble = split != 0;
     return TRLDA_OK;
 }
 
@@ -3918,15 +3952,15 @@ int trlda_model_set_doc_kernel(trlda_model *m, int kind)
     if (kind == TRLDA_DOCS_SMALL || kind == TRLDA_DOCS_REG) {
         // (the choice between the two bodies of the K <= 128 launch forms: everything around them --
         // fused preamble, merged / deferred statistics, lanes -- stays as it is)
-        m->small_k = kind == TRLDA_DOCS_SMALL ? 1 : 0;
-        m->doc_kernel = TRLDA_DOCS_AUTO;
+        m->sw.small_k = kind == TRLDA_DOCS_SMALL ? 1 : 0;
+        m->sw.doc_kernel = TRLDA_DOCS_AUTO;
         return TRLDA_OK;
     }
     if (kind != TRLDA_DOCS_AUTO && kind != TRLDA_DOCS_GENERAL && kind != TRLDA_DOCS_WIDE)
         return fail(TRLDA_ERR_ARG, "doc_kernel must be TRLDA_DOCS_AUTO, _GENERAL, _WIDE, _SMALL or _REG");
     if (kind == TRLDA_DOCS_AUTO)
-        m->small_k = -1;
-    m->doc_kernel = kind;
+        m->sw.small_k = -1;
+    m->sw.doc_kernel = kind;
     return TRLDA_OK;
 }
 
@@ -3937,7 +3971,7 @@ int trlda_model_set_doc_threads(trlda_model *m, int threads)
     if (threads != 0 && threads != 64 && threads != 128 && threads != 256 && threads != 512 &&
         threads != 1024)
         return fail(TRLDA_ERR_ARG, "doc_threads must be 0, 64, 128, 256, 512 or 1024");
-    m->doc_threads = threads;
+    m->sw.doc_threads = threads;
     return TRLDA_OK;
 }
 
@@ -3955,7 +3989,7 @@ int trlda_model_set_merged_launch(trlda_model *m, int enabled)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->merged_launch = enabled < 0 ? 0 : std::min(enabled, 2);
+    m->sw.merged_launch = enabled < 0 ? 0 : std::min(enabled, 2);
     return TRLDA_OK;
 }
 
@@ -3965,7 +3999,7 @@ int trlda_model_set_split_docs(trlda_model *m, int enabled)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->split_docs = enabled != 0;
+    m->sw.split_docs = enabled != 0;
     return TRLDA_OK;
 }
 
@@ -4105,7 +4139,7 @@ int trlda_model_set_deferred_stats(trlda_model *m, int enabled)
     int rc = check_model(m);                         // (flushes what is pending)
     if (rc)
         return rc;
-    m->deferred_stats = enabled != 0;
+    m->sw.deferred_stats = enabled != 0;
     return TRLDA_OK;
 }
 
@@ -4294,14 +4328,8 @@ int lanes_ensure(trlda_model *m)
 // about lambda -- a prefetched preamble -- is stamped with the version: a new one voids it)
 void lane_follow(const trlda_model *m, trlda_model *l)
 {
-    l->sstats_mode = m->sstats_mode; l->doc_threads = m->doc_threads; l->doc_kernel = m->doc_kernel;
-    l->small_k = m->small_k;
-    l->split_preamble = m->split_preamble; l->dense_preamble = m->dense_preamble;
-    l->pair_gathers = m->pair_gathers; l->prefetch_next = m->prefetch_next; l->split_docs = m->split_docs;
-    l->merged_launch = m->merged_launch; l->split_long_lists = m->split_long_lists;
-    l->tiled_tasks = m->tiled_tasks; l->fused_update = m->fused_update; l->carry_rowsums = m->carry_rowsums;
-    l->emit_next_preamble = m->emit_next_preamble;
-    l->deferred_stats = m->deferred_stats; l->big_emit = m->big_emit; l->keep_sstats = false;
+    l->sw = m->sw;
+    l->keep_sstats = false;
     l->rs_floor = m->rs_floor; l->lambda_positive = m->lambda_positive;
     l->lambda_exposed = m->lambda_exposed;           // (the same choice of preamble as the model's own)
     l->lambda_version = m->lambda_version;
@@ -4692,9 +4720,9 @@ int trlda_model_estep_corpus(trlda_model *m, int64_t n_docs, const int64_t *offs
         return e ? std::max(1, std::min(16, std::atoi(e))) : 8;
     }();
     constexpr int kBehind = 4;
-    const bool was_deferred = m->deferred_stats;
+    const bool was_deferred = m->sw.deferred_stats;
     const int was_lanes = m->lanes_wanted;
-    m->deferred_stats = true;
+    m->sw.deferred_stats = true;
     static const int corpus_lanes = [] {             // (A/B: TRLDA_CORPUS_LANES=1)
         const char *e = std::getenv("TRLDA_CORPUS_LANES");
         return e && e[0] == '1' ? 1 : 2;
@@ -4736,7 +4764,7 @@ int trlda_model_estep_corpus(trlda_model *m, int64_t n_docs, const int64_t *offs
     for (trlda_batch *b : batch)
         if (b)
             (void)trlda_batch_destroy(b);
-    m->deferred_stats = was_deferred;
+    m->sw.deferred_stats = was_deferred;
     m->lanes_wanted = was_lanes;
     return rc ? rc : rc_flush;
 }
@@ -4745,7 +4773,7 @@ int trlda_model_set_prefetch(trlda_model *m, int enabled)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->prefetch_next = enabled != 0;
+    m->sw.prefetch_next = enabled != 0;
     m->prefetch.valid = false;
     return TRLDA_OK;
 }
@@ -5302,7 +5330,7 @@ int online_update_fused(trlda_model *m, const trlda_batch *b, int num_documents,
             // (K > 256: there the document kernel carries the factor multiply for nothing measurable
             // -- coefficients from scalar registers, factors in LDS; at K = 129 .. 256 it cost 1.9 % of
             // the document launches, more than exp_elog_beta_kernel takes at large batches)
-            out.emit_u = !last && m->big_emit && m->carry_rowsums && K > 256;
+            out.emit_u = !last && m->sw.big_emit && m->sw.carry_rowsums && K > 256;
             if (!rc)
                 rc = estep_device(m, b, m->gamma, out, max_iter_inference, threshold, nullptr);
             if (!rc)
@@ -5956,7 +5984,7 @@ int trlda_model_set_split_lists(trlda_model *m, int enabled)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->split_long_lists = enabled != 0;
+    m->sw.split_long_lists = enabled != 0;
     return TRLDA_OK;
 }
 
@@ -6096,7 +6124,7 @@ int trlda_model_set_carry_rowsums(trlda_model *m, int carry)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->carry_rowsums = carry != 0;
+    m->sw.carry_rowsums = carry != 0;
     return TRLDA_OK;
 }
 
@@ -6104,7 +6132,7 @@ int trlda_model_set_next_preamble(trlda_model *m, int enabled)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->emit_next_preamble = enabled != 0;
+    m->sw.emit_next_preamble = enabled != 0;
     m->next_pre.valid = false;
     return TRLDA_OK;
 }
@@ -6113,7 +6141,7 @@ int trlda_model_set_fused_update(trlda_model *m, int fused)
 {
     if (!m)
         return fail(TRLDA_ERR_ARG, "model is NULL");
-    m->fused_update = fused != 0;
+    m->sw.fused_update = fused != 0;
     invalidate_rowsums(m);
     return TRLDA_OK;
 }
