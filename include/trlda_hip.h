@@ -462,6 +462,51 @@ int trlda_model_gibbs(trlda_model *model, const trlda_batch *batch, const double
 int trlda_model_gibbs_host(trlda_model *model, const trlda_batch *batch, double *theta, int use_latents,
                            double *sstats, int num_samples, int burn_in);
 
+/* ---- sampling documents: LDA::sample, src/lda.cpp:88-115, python/src/ldainterface.cpp:218-262 ----
+ * Topics beta_k ~ Dirichlet(lambda_k) are drawn once per call; per document d, its length
+ * n_d ~ Poisson(length), theta_d ~ Dirichlet(alpha) and, per token, a topic z ~ theta_d and a
+ * word w ~ beta_z.  A document is its word ids in token order (every count is 1; repeats are
+ * allowed).  Every draw is Philox4x32-10 of a 64-bit key and a counter pinned in csrc/philox.h
+ * (purposes 8 - 15), so nothing depends on the launch, the device or B: with one key, the first n
+ * documents of B > n are the n documents of B = n.  Deviations from the reference (DESIGN.md
+ * 3.11): Philox instead of rand(), Poisson by inversion (utils.cpp:269-287's product method fails
+ * from length 745 on), O(log V) word draws by binary search in a prefix table.
+ *
+ * The key for the host entries: the next two draws of the library's libc-compatible stream (first
+ * draw: the low 32 bits; 62 bits vary), the same as trlda_model_gibbs_host's.  A gamma0 drawn ahead
+ * by a model is given back to the stream first.  trlda_seed() makes a sequence of calls
+ * reproducible; successive calls differ. */
+int trlda_rng_draw_key(uint64_t *key);
+
+/* The B lengths (purpose 14, counter (d, 0, 0); u in [0, 1)) as CSR offsets: indptr_out[B+1],
+ * indptr_out[0] = 0.  n_d inverts Poisson(length) against a table built with log, exp and
+ * sequential sums only: l_0 = -length, l_k = l_{k-1} + log(length) - log(k), pmf_k = exp(l_k),
+ * CDF_k = CDF_{k-1} + pmf_k up to k_max = ceil(length + 12 sqrt(length) + 40); n_d is the first k
+ * with CDF_k > u * CDF_kmax, or, when u * CDF_kmax rounds up to CDF_kmax, the first k whose CDF
+ * equals CDF_kmax.  length = 0: every document is empty.  TRLDA_ERR_ARG: length < 0 or not finite,
+ * B < 0, or a total (indptr_out[B]) that does not fit in int32.  Host only: no device needed. */
+int trlda_sample_lengths(int B, double length, uint64_t key, int32_t *indptr_out);
+
+/* The documents on the device: indptr_dev (B+1, from trlda_sample_lengths; trusted as given) in,
+ * ids_dev (indptr[B] int32 word ids) out, theta_dev (K x B, the documents' theta) out unless NULL.
+ * Reads lambda and alpha only; flushes the deferred work and the lanes first.  The VI workspaces,
+ * trlda_model_get_sstats, the announcements and the Gibbs state keep what they held.  A topic row
+ * or theta whose weights do not sum to a finite number > 0 (an all-zero lambda row when eta = 0,
+ * say) fails the call with "Something went wrong while sampling from histogram." (utils.cpp:198).
+ * Workspaces, allocated on first use and kept until trlda_model_destroy (hipFree synchronises the
+ * device): the K x V double prefix table (K * V * 8 bytes, 400 MB at K = 500, V = 100 000;
+ * shared with the Gibbs path's table), 2 x K x ceil(V / 4096) doubles of chunk totals, and a
+ * K x B double prefix scratch sized to the largest B so far (for trlda_model_sample_host also
+ * B+1 and nnz int32 and K x B double staging).  Synchronises. */
+int trlda_model_sample(trlda_model *model, int B, const int32_t *indptr_dev, int32_t *ids_dev,
+                       double *theta_dev, uint64_t key);
+
+/* Host-pointer form of trlda_model_sample: indptr (B+1 host; checked: starts at 0, never
+ * falls) in, ids (indptr[B] host) and theta (K x B host, or NULL) out, staged through buffers the
+ * model holds.  python/src/ldainterface.cpp:218-262 -> src/lda.cpp:88-115. */
+int trlda_model_sample_host(trlda_model *model, int B, const int32_t *indptr, int32_t *ids,
+                            double *theta, uint64_t key);
+
 /* model.lambda = (1-rho) lambda' + rho (eta + scale * sstats), all device pointers.
  * src/onlinelda.cpp:99-100, :108-109; src/batchlda.cpp:60 (rho = 1, scale = 1). */
 int trlda_model_blend(trlda_model *model, const double *lambda_prime_dev,
@@ -835,8 +880,12 @@ int trlda_debug_fold16(int device, const double *in, double *out16, double *out4
 int trlda_debug_peek(trlda_model *model, int which, double *host_out, size_t count);
 /* test hook: the normalised exp E[log beta] table the model's last Gibbs call sampled from
  * (K x V; only that batch's words are filled) -- the tests' restatement of the sampler
- * (tests/gibbs_host.py) reads the same numbers the kernel did */
+ * (tests/gibbs_host.py) reads the same numbers the kernel did.  The table shares its memory with
+ * trlda_model_sample's: after a sample call this fails until the next Gibbs call. */
 int trlda_debug_gibbs_table(trlda_model *model, double *host_out);
+/* test hook: the beta prefix table the model's last trlda_model_sample call read (K x V,
+ * TOPIC-MAJOR: element (k, w) at [w + V*k]; csrc/sample_kernels.h).  Fails after a Gibbs call. */
+int trlda_debug_sample_table(trlda_model *model, double *host_out);
 /* diagnostics: the s_memrealtime stamps of the model's last merged launch, 3 x 1024 values
  * (TRLDA_MERGED_STAMPS=1; tools/merged_stamps.py) */
 int trlda_debug_merged_stamps(trlda_model *model, unsigned long long *host_out);

@@ -9,8 +9,9 @@ script written against the reference -- its README example, say -- runs unchange
     from trlda.utils import load_documents
 
 Only the accelerated path exists, together with Gibbs inference on the GPU
-(``update_variables(docs, inference_method='gibbs')``); ``sample`` and the
-``load_users`` / ``random_select`` / ``sample_dirichlet`` helpers are not part of it.
+(``update_variables(docs, inference_method='gibbs')``) and sampling
+documents from a model on the GPU (``sample``); the ``load_users`` /
+``random_select`` / ``sample_dirichlet`` helpers are not part of it.
 """
 __license__ = 'MIT License <http://www.opensource.org/licenses/mit-license.php>'
 __docformat__ = 'epytext'

@@ -108,6 +108,11 @@ _SIGNATURES = {
     "trlda_gibbs": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, f64p, f64p, f64p, C.c_int,
                               f64p, C.c_int, C.c_int, C.c_int]),
     "trlda_debug_gibbs_table": (C.c_int, [vp, f64p]),
+    "trlda_rng_draw_key": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "trlda_sample_lengths": (C.c_int, [C.c_int, C.c_double, C.c_uint64, i32p]),
+    "trlda_model_sample": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64]),
+    "trlda_model_sample_host": (C.c_int, [vp, C.c_int, i32p, i32p, vp, C.c_uint64]),
+    "trlda_debug_sample_table": (C.c_int, [vp, vp]),
     "trlda_model_blend": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_double]),
     "trlda_model_tr_init": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),
     "trlda_model_wordcounts": (C.c_int, [vp, vp, vp]),

@@ -20,7 +20,7 @@
 //           adds one to the uint32 count of (z, w)
 //   theta   Dirichlet(counts) of the final state; sstats = count / num_samples
 //
-// ---- the random stream (the contract tests/gibbs_host.py restates) ----------------------
+// ---- the random stream (the contract tests/gibbs_host.py restates; the code is philox.h's) --
 // Philox4x32-10 (Salmon et al., SC'11; Random123's constants), key = (k0, k1), the two 32-bit
 // halves of the call's 64-bit key (trlda_model_gibbs_host takes them as two draws of the
 // library's libc-compatible stream; those are 31-bit values, so there bits 31 and 63 of the key are
@@ -63,19 +63,19 @@
 // attempt n = 0, 1, ..: x = sqrt(-2 log u_open) cos(2 pi u) from purpose 3's two uniforms,
 // v = (1 + c x)^3 (rejected if 1 + c x <= 0), accepted when
 // log(u_open of purpose 4) < x^2/2 + d - d v + d log v; log G = log d + log v.  After
-// kGibbsGammaTries attempts (acceptance is above 0.95 per attempt) log d is taken.
+// kGammaTries attempts (acceptance is above 0.95 per attempt) log d is taken.
 // theta_k = exp(log G_k - max) / sum over the topics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "estep_kernels.h"
+#include "philox.h"
 
 namespace trlda {
 
 constexpr int kGibbsMaxK = 1024;      // KPL <= 16 topics per lane
 constexpr int kGibbsWaves = 4;        // documents (waves) per workgroup
-constexpr int kGibbsGammaTries = 64;
 constexpr int kGibbsInitBatch = 8;   // init: tokens of one entry that share a walk of the prefix
 
 enum : uint32_t {
@@ -102,43 +102,6 @@ struct GibbsArgs {
     int *flag;                   // set to 1 by a histogram that sums to 0 or is not finite
 };
 
-// Philox4x32-10 in place on the counter
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = (uint32_t)p1;
-        c[2] = n2;
-        c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ void gibbs_block(uint32_t (&c)[4], uint32_t index, uint32_t doc, uint32_t step,
-                                            uint32_t purpose, uint32_t k0, uint32_t k1)
-{
-    c[0] = index; c[1] = doc; c[2] = step; c[3] = purpose;
-    philox4x32_10(c, k0, k1);
-}
-
-__device__ __forceinline__ double gibbs_u(uint32_t lo, uint32_t hi)
-{
-    const uint64_t x = ((uint64_t)hi << 32) | lo;
-    return (double)(x >> 11) * 0x1.0p-53;
-}
-
-__device__ __forceinline__ double gibbs_u_open(uint32_t lo, uint32_t hi)
-{
-    const uint64_t x = ((uint64_t)hi << 32) | lo;
-    return ((double)(x >> 12) + 0.5) * 0x1.0p-52;
-}
-
 __device__ __forceinline__ double readlane_d(double v, int l)
 {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -162,39 +125,10 @@ __device__ __forceinline__ double wave_allmax(double v)
     return v;
 }
 
-// log of a Gamma(a) draw (the header's recipe); a <= 0 or not finite: -inf
+// log of a Gamma(a) draw of topic k of document `doc` (philox.h's recipe, purposes 3 / 4 / 5)
 __device__ inline double gibbs_log_gamma(double a, uint32_t k, uint32_t doc, uint32_t k0, uint32_t k1)
 {
-#pragma clang fp contract(off)
-    if (!(a > 0.0) || !(a <= 1.0e300))
-        return -INFINITY;
-    const bool boost = a < 1.0;
-    const double sh = boost ? a + 1.0 : a;
-    const double d = sh - 1.0 / 3.0;
-    const double c = 1.0 / sqrt(9.0 * d);
-    double lg = log(d);
-    for (int n = 0; n < kGibbsGammaTries; ++n) {
-        uint32_t w[4];
-        gibbs_block(w, k, doc, (uint32_t)n, kGibbsGammaNormal, k0, k1);
-        const double x = sqrt(-2.0 * log(gibbs_u_open(w[0], w[1]))) * cos(6.283185307179586 * gibbs_u(w[2], w[3]));
-        const double v1 = 1.0 + c * x;
-        if (v1 <= 0.0)
-            continue;
-        const double v = v1 * v1 * v1;
-        gibbs_block(w, k, doc, (uint32_t)n, kGibbsGammaAccept, k0, k1);
-        const double lu = log(gibbs_u_open(w[0], w[1]));
-        const double lv = log(v);
-        if (lu < 0.5 * x * x + d - d * v + d * lv) {
-            lg = log(d) + lv;
-            break;
-        }
-    }
-    if (boost) {
-        uint32_t w[4];
-        gibbs_block(w, k, doc, 0u, kGibbsGammaBoost, k0, k1);
-        lg = lg + log(gibbs_u_open(w[0], w[1])) / a;
-    }
-    return lg;
+    return philox_log_gamma(a, k, doc, kGibbsGammaNormal, kGibbsGammaAccept, kGibbsGammaBoost, k0, k1);
 }
 
 // tokens per document: the counts > 0 of its entries (lda.cpp:251-262 draws `wordcount` topics)
@@ -254,8 +188,8 @@ __global__ __launch_bounds__(kGibbsWaves * kWave) void gibbs_docs_kernel(GibbsAr
         double part = 0.0;
         for (int k = lane; k < K; k += kWave) {
             uint32_t w[4];
-            gibbs_block(w, (uint32_t)k, udoc, 0u, kGibbsInitTheta, k0, k1);
-            const double x = -log(gibbs_u_open(w[0], w[1]));
+            philox_block(w, (uint32_t)k, udoc, 0u, kGibbsInitTheta, k0, k1);
+            const double x = -log(philox_u_open(w[0], w[1]));
             th[k] = x;
             part += x;
         }
@@ -303,8 +237,8 @@ __global__ __launch_bounds__(kGibbsWaves * kWave) void gibbs_docs_kernel(GibbsAr
 #pragma unroll
                 for (int u = 0; u < kGibbsInitBatch; ++u) {
                     uint32_t w[4];
-                    gibbs_block(w, t0 + (uint32_t)(t1 + u), udoc, 0u, kGibbsInitToken, k0, k1);
-                    r[u] = __dmul_rn(gibbs_u(w[0], w[1]), tot);
+                    philox_block(w, t0 + (uint32_t)(t1 + u), udoc, 0u, kGibbsInitToken, k0, k1);
+                    r[u] = __dmul_rn(philox_u(w[0], w[1]), tot);
                     z[u] = u < n ? -1 : 0;
                     if (u < n)
                         rmax = fmax(rmax, r[u]);
@@ -397,8 +331,8 @@ __global__ __launch_bounds__(kGibbsWaves * kWave) void gibbs_docs_kernel(GibbsAr
                         }
                         const uint32_t idx = tk + lane;
                         uint32_t rw[4];
-                        gibbs_block(rw, idx, udoc, (uint32_t)s, kGibbsSweep, k0, k1);
-                        uc = gibbs_u(rw[0], rw[1]);
+                        philox_block(rw, idx, udoc, (uint32_t)s, kGibbsSweep, k0, k1);
+                        uc = philox_u(rw[0], rw[1]);
                         zc = idx < ntok ? (int)a.z[zbase + idx] : 0;
                     }
                     const int zold = __builtin_amdgcn_readlane(zc, ql);

@@ -44,6 +44,7 @@
 #include "rng_kernels.h"
 #include "dp_kernels.h"
 #include "gibbs_kernels.h"
+#include "sample_kernels.h"
 
 namespace {
 
@@ -605,7 +606,20 @@ struct trlda_model {
         // the plan (token offsets, document order) of the batch it was made for
         uint64_t plan_batch = 0;
         int64_t total_tokens = 0;
+        int table_user = 0;                     // who filled `eeb` last: 1 Gibbs, 2 sample (it shares it)
     } gibbs;
+    // sampling documents (sample_kernels.h, trlda_model_sample): the K x V prefix table lives in
+    // gibbs.eeb (per-call scratch of either path, behind a flush); the rest is its own
+    struct {
+        double *part = nullptr;                 // 2 x K x chunks: the chunks' maxima and totals
+        size_t cap_part = 0;
+        double *pre = nullptr;                  // K x B: the documents' theta prefixes
+        size_t cap_pre = 0;
+        int32_t *indptr = nullptr, *ids = nullptr;   // trlda_model_sample_host's staging
+        size_t cap_indptr = 0, cap_ids = 0;
+        double *theta = nullptr;
+        size_t cap_theta = 0;
+    } sample;
 };
 
 namespace {
@@ -3850,6 +3864,8 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->gibbs.cnt); (void)hipFree(m->gibbs.z); (void)hipFree(m->gibbs.tokens);
         (void)hipFree(m->gibbs.tok_off); (void)hipFree(m->gibbs.order); (void)hipFree(m->gibbs.flag);
         (void)hipFree(m->gibbs.theta_in); (void)hipFree(m->gibbs.theta); (void)hipFree(m->gibbs.sstats);
+        (void)hipFree(m->sample.part); (void)hipFree(m->sample.pre); (void)hipFree(m->sample.indptr);
+        (void)hipFree(m->sample.ids); (void)hipFree(m->sample.theta);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -4970,6 +4986,7 @@ int gibbs_preamble(trlda_model *m, const trlda_batch *b)
     if (!rc) rc = grow(&g.psi_sum, &g.cap_psi, 3 * (size_t)K);
     if (rc)
         return rc;
+    g.table_user = 1;
     hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K, V,
                        wpb, m->lambda, g.partial);
     HIP_TRY(hipGetLastError());
@@ -5143,9 +5160,204 @@ int trlda_debug_gibbs_table(trlda_model *m, double *host_eeb)
     int rc = check_model(m);
     if (rc)
         return rc;
-    if (!host_eeb || !m->gibbs.eeb)
-        return fail(TRLDA_ERR_ARG, "no Gibbs call has run on this model");
+    if (!host_eeb || !m->gibbs.eeb || m->gibbs.table_user != 1)
+        return fail(TRLDA_ERR_ARG, "no Gibbs call has run on this model since its last sample call");
     HIP_TRY(hipMemcpyAsync(host_eeb, m->gibbs.eeb, (size_t)m->K * m->V * sizeof(double), hipMemcpyDeviceToHost,
+                           m->stream));
+    return sync_model(m);
+}
+
+// ---- sampling documents: LDA::sample, src/lda.cpp:88-115 (sample_kernels.h) ----
+int trlda_rng_draw_key(uint64_t *key)
+{
+    if (!key)
+        return fail(TRLDA_ERR_ARG, "NULL key");
+    *key = trlda_host::rng_draw_key();
+    return TRLDA_OK;
+}
+
+// Poisson(length) by inversion against a table of the pmf built with log, exp and sequential
+// sums (include/trlda_hip.h).  The table is not kept: its values are formed twice, the same way --
+// once for the total, once in a sweep over the draws in the order of their targets.
+int trlda_sample_lengths(int B, double length, uint64_t key, int32_t *indptr_out)
+{
+    if (!(length >= 0.0) || !std::isfinite(length))
+        return fail(TRLDA_ERR_ARG, "The length should be a non-negative finite number.");
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "The number of documents should not be negative.");
+    if (!indptr_out)
+        return fail(TRLDA_ERR_ARG, "NULL indptr");
+    indptr_out[0] = 0;
+    if (B == 0)
+        return TRLDA_OK;
+    const double kmax_d = std::ceil(length + 12.0 * std::sqrt(length) + 40.0);
+    if (kmax_d > (double)INT32_MAX)
+        return fail(TRLDA_ERR_ARG, "The documents' total length does not fit in 32 bits.");
+    const int64_t kmax = (int64_t)kmax_d;
+    const double log_lambda = std::log(length);
+    // pass 1: CDF_kmax, and the first k whose CDF equals it (the CDF rises until then)
+    double l = -length, cdf = std::exp(l);
+    int64_t k_full = 0;
+    for (int64_t k = 1; k <= kmax; ++k) {
+        l = l + log_lambda - std::log((double)k);
+        const double next = cdf + std::exp(l);
+        if (next != cdf)
+            k_full = k;
+        cdf = next;
+    }
+    const double total = cdf;
+    std::vector<double> r((size_t)B);
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    for (int d = 0; d < B; ++d) {
+        uint32_t x[4];
+        trlda::philox_block(x, (uint32_t)d, 0u, 0u, trlda::kSampleLength, k0, k1);
+        r[(size_t)d] = trlda::philox_u(x[0], x[1]) * total;
+    }
+    std::vector<int32_t> order((size_t)B);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&r](int32_t a, int32_t b) { return r[(size_t)a] < r[(size_t)b]; });
+    std::vector<int64_t> n((size_t)B, k_full);      // (r rounded up to the total: the first k at it)
+    size_t i = 0;
+    l = -length;
+    cdf = std::exp(l);
+    for (int64_t k = 0; i < (size_t)B && k <= kmax; ++k) {
+        if (k > 0) {
+            l = l + log_lambda - std::log((double)k);
+            cdf = cdf + std::exp(l);
+        }
+        while (i < (size_t)B && cdf > r[(size_t)order[i]])
+            n[(size_t)order[i++]] = k;
+    }
+    int64_t sum = 0;
+    for (int d = 0; d < B; ++d) {
+        sum += n[(size_t)d];
+        if (sum > (int64_t)INT32_MAX)
+            return fail(TRLDA_ERR_ARG, "The documents' total length does not fit in 32 bits.");
+        indptr_out[d + 1] = (int32_t)sum;
+    }
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the whole call on the model's stream; waits for the device at the end (the sampling-failure flag)
+int sample_device(trlda_model *m, int B, const int32_t *indptr_dev, int32_t *ids_dev, double *theta_dev,
+                  uint64_t key)
+{
+    using namespace trlda;
+    const int K = m->K, V = m->V;
+    const size_t KV = (size_t)K * V;
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "The number of documents should not be negative.");
+    if (B > 0 && (!indptr_dev || !ids_dev))
+        return fail(TRLDA_ERR_ARG, "NULL indptr / ids");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    auto &g = m->gibbs;
+    auto &s = m->sample;
+    const int nchunk = (V + kSampleChunk - 1) / kSampleChunk;
+    int rc = grow(&g.eeb, &g.cap_eeb, KV);
+    if (!rc) rc = grow(&s.part, &s.cap_part, 2 * (size_t)K * nchunk);
+    if (!rc) rc = grow(&s.pre, &s.cap_pre, (size_t)K * std::max(B, 1));
+    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    if (rc)
+        return rc;
+    g.table_user = 2;
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    double *cmax = s.part, *ctot = s.part + (size_t)K * nchunk;
+    HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
+    const dim3 grid((unsigned)((size_t)K * nchunk));
+    hipLaunchKernelGGL(sample_topics_kernel, grid, dim3(kSampleThreads), 0, m->stream, K, V, nchunk, k0, k1,
+                       m->lambda, g.eeb, cmax);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sample_topics_scan_kernel, grid, dim3(kSampleThreads), 0, m->stream, K, V, nchunk, g.eeb,
+                       cmax, ctot);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sample_topics_offset_kernel, grid, dim3(kSampleThreads), 0, m->stream, K, V, nchunk,
+                       g.eeb, ctot, g.flag);
+    HIP_TRY(hipGetLastError());
+    if (B > 0) {
+        const int kpl = (K + kWave - 1) / kWave;
+        hipLaunchKernelGGL(sample_theta_kernel, dim3((B + kSampleWaves - 1) / kSampleWaves), dim3(kSampleThreads), 0,
+                           m->stream, K, B, kpl, k0, k1, m->alpha, s.pre, theta_dev, g.flag);
+        HIP_TRY(hipGetLastError());
+        // (the token count is indptr[B], on the device: a fixed grid strides over it)
+        hipLaunchKernelGGL(sample_tokens_kernel, dim3((unsigned)device_cus(m->device) * 16), dim3(kSampleThreads), 0,
+                           m->stream, K, V, B, k0, k1, indptr_dev, s.pre, g.eeb, ids_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_sample(trlda_model *m, int B, const int32_t *indptr_dev, int32_t *ids_dev, double *theta_dev,
+                       uint64_t key)
+{
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    return sample_device(m, B, indptr_dev, ids_dev, theta_dev, key);
+}
+
+int trlda_model_sample_host(trlda_model *m, int B, const int32_t *indptr, int32_t *ids, double *theta,
+                            uint64_t key)
+{
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "The number of documents should not be negative.");
+    if (!indptr || (B > 0 && indptr[B] > 0 && !ids))
+        return fail(TRLDA_ERR_ARG, "NULL indptr / ids");
+    if (indptr[0] != 0)
+        return fail(TRLDA_ERR_ARG, "indptr should start at 0");
+    for (int d = 0; d < B; ++d)
+        if (indptr[d + 1] < indptr[d])
+            return fail(TRLDA_ERR_ARG, "indptr should not decrease");
+    auto &s = m->sample;
+    const size_t nnz = (size_t)indptr[B];
+    const size_t tcount = (size_t)m->K * B;
+    rc = grow(&s.indptr, &s.cap_indptr, (size_t)B + 1);
+    if (!rc) rc = grow(&s.ids, &s.cap_ids, std::max<size_t>(nnz, 1));
+    if (!rc && theta) rc = grow(&s.theta, &s.cap_theta, std::max<size_t>(tcount, 1));
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(s.indptr, indptr, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    rc = sample_device(m, B, s.indptr, s.ids, theta ? s.theta : nullptr, key);
+    if (rc)
+        return rc;
+    if (nnz)
+        HIP_TRY(hipMemcpyAsync(ids, s.ids, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    if (theta && tcount)
+        HIP_TRY(hipMemcpyAsync(theta, s.theta, tcount * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    m->d2h_bytes += (int64_t)(nnz * sizeof(int32_t) + (theta ? tcount * sizeof(double) : 0));
+    return TRLDA_OK;
+}
+
+// the prefix table the last sample call read (K x V, topic-major: row k contiguous), for the tests'
+// restatement of the sampler
+int trlda_debug_sample_table(trlda_model *m, double *host_out)
+{
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!host_out || !m->gibbs.eeb || m->gibbs.table_user != 2)
+        return fail(TRLDA_ERR_ARG, "no sample call has run on this model since its last Gibbs call");
+    HIP_TRY(hipMemcpyAsync(host_out, m->gibbs.eeb, (size_t)m->K * m->V * sizeof(double), hipMemcpyDeviceToHost,
                            m->stream));
     return sync_model(m);
 }

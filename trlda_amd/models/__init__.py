@@ -9,12 +9,13 @@ goes through ``libtrlda_hip.so`` (include/trlda_hip.h) to the gfx950 kernels.  S
 like ``PyArray_FromMatrixXd`` (python/src/pyutils.cpp:15-36).
 """
 import ctypes as C
+import operator
 import os
 
 import numpy as np
 
 from .. import _ffi
-from ..documents import CSRDocuments, DeviceBatch, as_csr
+from ..documents import CSRDocuments, DeviceBatch, DocumentList, as_csr
 
 __all__ = ["Distribution", "LDA", "OnlineLDA", "BatchLDA", "CumulativeLDA"]
 
@@ -368,9 +369,38 @@ class LDA(Distribution):
         _ffi.check(_ffi.lib().trlda_model_estep_resident(self._handle, batch.handle, int(max_iter),
                                                          float(threshold)))
 
-    # -- not on the accelerated path ----------------------------------------------
-    def sample(self, num_documents, length):
-        raise NotImplementedError("sample (lda.cpp:88-115) is outside the accelerated path.")
+    # -- sampling documents (ldainterface.cpp:218-262 -> lda.cpp:88-115) ------------------------
+    def sample(self, num_documents, length, return_theta=False):
+        """Samples ``num_documents`` documents from the model: topics beta_k ~ Dirichlet(lambda_k)
+        once per call, then per document a length ~ Poisson(``length``), theta ~ Dirichlet(alpha)
+        and per token a topic ~ theta and a word ~ beta of that topic (csrc/sample_kernels.h).
+
+        Returns a list of documents, each a list of ``(word id, 1)`` tuples in token order (a
+        ``DocumentList``, which ``update_parameters`` takes as it is); with ``return_theta=True``
+        ``(documents, theta K x num_documents)``.  Deviations from the reference:
+        the random numbers are Philox4x32-10 keyed by two draws of the seeded stream, so
+        ``trlda.seed`` makes a call reproducible, and the first n documents do not depend on how
+        many more are asked for; lengths are drawn by inversion, correct for any ``length``."""
+        num_documents = operator.index(num_documents)                # the binding's "ii"
+        length = operator.index(length)
+        if num_documents < 0:
+            raise RuntimeError("The number of documents should not be negative.")
+        if length < 0:
+            raise RuntimeError("The length should not be negative.")
+        self._settle()
+        L = _ffi.lib()
+        key = C.c_uint64(0)
+        _ffi.check(L.trlda_rng_draw_key(C.byref(key)))
+        indptr = np.empty(num_documents + 1, dtype=np.int32)
+        _ffi.check(L.trlda_sample_lengths(num_documents, float(length), key.value, indptr))
+        ids = np.empty(int(indptr[-1]), dtype=np.int32)
+        theta = np.empty((self._K, num_documents), dtype=np.float64, order="F") if return_theta else None
+        _ffi.check(L.trlda_model_sample_host(self._handle, num_documents, indptr, ids,
+                                             None if theta is None else theta.ctypes.data, key.value))
+        docs = DocumentList(CSRDocuments(indptr, ids, np.ones(len(ids), dtype=np.int32)))
+        if return_theta:
+            return docs, theta
+        return docs
 
     def __str__(self):                                               # ldainterface.cpp:473-490
         self._settle()
