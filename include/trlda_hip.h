@@ -429,6 +429,18 @@ int trlda_model_lower_bound(trlda_model *model, const trlda_batch *batch, double
                             double eta, double factor, int max_iter, double threshold,
                             double *bound_out);
 
+/* Held-out predictive log-likelihood (Hoffman et al. 2013): VI on `observed` from gamma (K x B
+ * host, in: gamma0, out: gamma), then per document d the held-out words' log p(w | d) with
+ * E[theta_d] = gamma_d / sum gamma_d and E[beta_kw] = lambda_kw / sum_v lambda_kv.
+ * loglik_out[B], tokens_out[B] (host).  Synchronises.
+ * loglik_out[d] = sum over the entries (w, c) of `heldout`'s document d of c log p(w | d) (0 for a
+ * document without held-out entries; entries with c = 0 add nothing), tokens_out[d] = sum of c.
+ * The batches must hold the same number B > 0 of documents, both made for this model's V and
+ * device (else TRLDA_ERR_ARG).  csrc/heldout_kernels.h, DESIGN.md 3.12. */
+int trlda_model_predictive(trlda_model *model, const trlda_batch *observed,
+                           const trlda_batch *heldout, double *gamma, int max_iter,
+                           double threshold, double *loglik_out, double *tokens_out);
+
 /* LDA::updateVariablesGibbs (src/lda.cpp:224-293), reached from python/src/ldainterface.cpp:311-390
  * with inference_method='GIBBS': collapsed Gibbs sampling of the batch's topic assignments on the
  * device (csrc/gibbs_kernels.h), one wave64 per document, K <= 1024 (more: TRLDA_ERR_ARG).

@@ -12,6 +12,7 @@ Only the accelerated path exists, together with Gibbs infe
 (``update_variables(docs, inference_method='gibbs')``) and sampling
 documents from a model on the GPU (``sample``); the ``load_users`` /
 ``random_select`` / ``sample_dirichlet`` helpers are not part of it.
+``predictive_log_likelihood`` scores a model on held-out words on the GPU.
 """
 __license__ = 'MIT License <http://www.opensource.org/licenses/mit-license.php>'
 __docformat__ = 'epytext'

@@ -128,6 +128,7 @@ _SIGNATURES = {
                                                 vp]),
     "trlda_model_lower_bound": (C.c_int, [vp, vp, f64p, C.c_double, C.c_double, C.c_int, C.c_double,
                                 C.POINTER(C.c_double)]),
+    "trlda_model_predictive": (C.c_int, [vp, vp, vp, f64p, C.c_int, C.c_double, f64p, f64p]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),
     "trlda_model_online_update_multi": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                                   C.c_int, C.c_int, C.c_double, C.c_double,

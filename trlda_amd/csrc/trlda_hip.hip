@@ -45,6 +45,7 @@
 #include "dp_kernels.h"
 #include "gibbs_kernels.h"
 #include "sample_kernels.h"
+#include "heldout_kernels.h"
 
 namespace {
 
@@ -4905,6 +4906,73 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     pw_pb += K * std::lgamma(V * eta) - lg_lambda_sum;                     // :356
     pw_pb -= (double)K * V * std::lgamma(eta) - lg_lambda;                 // :357
     *bound_out = pw_pb + factor * pz + factor * ptheta;                    // :359
+    return TRLDA_OK;
+}
+
+// The held-out predictive log-likelihood (Hoffman et al. 2013; csrc/heldout_kernels.h): the E-step
+// of trlda_model_lower_bound on the observed parts, then one workgroup per document scores its
+// held-out part with gamma and the row sums the preamble left at psi_sum + K
+int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_batch *h, double *gamma,
+                           int max_iter, double threshold, double *loglik_out, double *tokens_out)
+{
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(o))
+        return rc_built;
+    if (int rc_built = batch_wait(h))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!o || !h || !gamma || !loglik_out || !tokens_out)
+        return fail(TRLDA_ERR_ARG, "NULL batch / gamma / loglik / tokens");
+    if (o->B != h->B)
+        return fail(TRLDA_ERR_ARG, "the observed and held-out batches hold different numbers of documents");
+    if (o->B <= 0)
+        return fail(TRLDA_ERR_ARG, "the predictive likelihood needs at least one document");
+    if (o->V != m->V || h->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (o->device != m->device || h->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    rc = ensure_update_workspace(m, o->B);
+    if (rc)
+        return rc;
+    const int K = m->K, B = o->B;
+    const size_t gbytes = (size_t)K * B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, o, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (rc)
+        return rc;
+    rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)B);
+    if (!rc)
+        rc = batch_begin(m, h);
+    if (rc)
+        return rc;
+    // (K factors in LDS: fewer bytes than the E-step's document kernel has just held for the same K)
+    const size_t lds = (size_t)K * sizeof(double);
+    if (lds > (size_t)kLdsDynBytes)
+        return fail(TRLDA_ERR_ARG, "num_topics too large for the held-out kernel's LDS layout");
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::heldout_docs_kernel<trlda::kHeldoutThreads>),
+                                 lds)))
+        return rc;
+    double *out = m->reduce_out;
+    hipLaunchKernelGGL(trlda::heldout_docs_kernel<trlda::kHeldoutThreads>, dim3(B), dim3(trlda::kHeldoutThreads),
+                       lds, m->stream, K, h->indptr, h->ids, h->cnts, m->lambda, m->psi_sum + K, m->gamma,
+                       out, out + B);
+    HIP_TRY(hipGetLastError());
+    (void)batch_end(m, o);
+    (void)batch_end(m, h);
+    std::vector<double> hbuf(2 * (size_t)B);
+    hipError_t e1 = hipMemcpyAsync(hbuf.data(), out, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    if (int rc_x = check_split_exchange(m))
+        return rc_x;
+    std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
+    std::memcpy(tokens_out, hbuf.data() + B, (size_t)B * sizeof(double));
     return TRLDA_OK;
 }
 

@@ -348,6 +348,64 @@ class LDA(Distribution):
                 batch.close()
         return bound.value
 
+    # -- held-out predictive log-likelihood (Hoffman et al. 2013; csrc/heldout_kernels.h) -----------
+    def predictive_log_likelihood(self, observed, heldout, latents=None, max_iter=100,
+                                  threshold=0.001, return_documents=False):
+        """Per-word predictive log-likelihood of held-out words: VI on ``observed`` with lambda
+        fixed (from ``latents`` as gamma0, else a random gamma drawn from the seeded stream as
+        ``update_variables`` draws it), then
+
+            score = sum_d sum_{(w, c) in heldout_d} c log p(w | d) / sum of those c,
+            p(w | d) = sum_k (gamma_dk / sum_j gamma_dj) (lambda_kw / sum_v lambda_kv),
+
+        on the GPU.  ``observed`` and ``heldout`` hold the same documents' two parts
+        (``trlda_amd.utils.split_documents``) as lists, ``DocumentList`` or ``DeviceBatch``.
+        Returns the score; with ``return_documents=True`` ``(score, loglik, tokens)``, each of the
+        last two float64 of length B (per document the sum of c log p(w | d) and of c).  lambda,
+        alpha, eta and the update counters stay as they are."""
+        obs, own_obs = self._batch(observed)
+        try:
+            held, own_held = self._batch(heldout)
+        except BaseException:
+            if own_obs:
+                obs.close()
+            raise
+        try:
+            self._settle()
+            B = len(obs)
+            if len(held) != B:
+                raise RuntimeError("Observed and held-out documents should be equal in number.")
+            if int(held.csr.cnts.sum(dtype=np.int64)) <= 0:
+                raise RuntimeError("There are no held-out tokens.")
+            L = _ffi.lib()
+            if latents is not None:
+                try:
+                    g = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if g.ndim == 1:
+                    g = g.reshape(-1, 1, order="F")
+                if g.ndim != 2 or g.shape != (self._K, B):
+                    raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+                gamma = np.asfortranarray(g)
+            else:
+                gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                L.trlda_sample_gamma_init(self._K, B, gamma)          # lda.cpp:135
+            loglik = np.empty(B, dtype=np.float64)
+            tokens = np.empty(B, dtype=np.float64)
+            _ffi.check(L.trlda_model_predictive(self._handle, obs.handle, held.handle, gamma,
+                                                int(max_iter), float(threshold), loglik, tokens))
+        finally:
+            if own_obs:
+                obs.close()
+            if own_held:
+                held.close()
+        # totals in document order, as the lower bound adds its documents' terms
+        score = float(np.cumsum(loglik)[-1] / np.cumsum(tokens)[-1])
+        if return_documents:
+            return score, loglik, tokens
+        return score
+
     # -- device reductions for the empirical-Bayes steps (csrc/eb_kernels.h) ----------------
     def _psi_gamma_diff_device(self, num_docs):
         """sum_d (psi(gamma_dk) - psi(sum_k gamma_dk)) over the gamma the last update / resident
