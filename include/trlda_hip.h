@@ -519,6 +519,41 @@ int trlda_model_sample(trlda_model *model, int B, const int32_t *indptr_dev, int
 int trlda_model_sample_host(trlda_model *model, int B, const int32_t *indptr, int32_t *ids,
                             double *theta, uint64_t key);
 
+/* ---- the utilities of trlda.utils (python/utils/__init__.py) ------------------------------- */
+
+/* TRLDA::polygamma(int, double), src/utils.cpp:107-111: psi(x) for n < 1, (-1)^(n+1) n! zeta(n+1, x)
+ * for n >= 1 (csrc/polygamma.h).  A non-positive integer x gives +inf for the zeta, so +inf for psi
+ * and odd n, -inf for even n >= 2; x = +inf gives +inf (n < 1) or a signed 0; nan gives nan; for n >= 1
+ * a non-integer x below -2^20 gives nan.  Host only: no device needed.  The same function as a device
+ * element of trlda_polygamma_device, to the last bit. */
+double trlda_polygamma(int n, double x);
+
+/* TRLDA::polygamma(int, const ArrayXXd&), src/utils.cpp:115-123: y_dev[i] = polygamma(n, x_dev[i]),
+ * i < count, device pointers on `device` (in place allowed), on the null stream; synchronises. */
+int trlda_polygamma_device(int n, int64_t count, const double *x_dev, double *y_dev, int device);
+
+/* Host-pointer form of trlda_polygamma_device, staged through a device buffer
+ * (python/src/utilsinterface.cpp, polygamma on an array). */
+int trlda_polygamma_host(int n, int64_t count, const double *x, double *y, int device);
+
+/* TRLDA::sampleDirichlet, src/utils.cpp:251-266: out_dev (m x n, F-order, a device pointer) gets n
+ * columns, each a draw from Dirichlet(alpha 1_m) (csrc/dirichlet_kernels.h): Philox under `key`,
+ * purposes 16 / 17 / 18, counter (row, column, attempt); a summation order that depends on m only.
+ * TRLDA_ERR_ARG: m or n < 0, alpha not > 0 or not finite.  m = 0 or n = 0: nothing is written.
+ * Null stream; synchronises. */
+int trlda_sample_dirichlet_device(int m, int n, double alpha, uint64_t key, double *out_dev, int device);
+
+/* Host-pointer form (python/src/utilsinterface.cpp, sample_dirichlet): the key is
+ * trlda_rng_draw_key()'s, drawn by every call that passes the argument checks (also for m = 0 or
+ * n = 0, which need no device); out (m x n, F-order) is staged through a device buffer. */
+int trlda_sample_dirichlet_host(int m, int n, double alpha, double *out, int device);
+
+/* TRLDA::randomSelect, src/utils.cpp:351-378: k of 0 .. n-1, drawn with rand() % n from the seeded
+ * stream exactly as the reference draws them (a gamma0 drawn ahead is given back first); out[0 .. k)
+ * gets them in ascending order.  TRLDA_ERR_ARG "k must be smaller than n." (k > n), then "n and k must
+ * be non-negative.".  Host only. */
+int trlda_random_select(int k, int n, int32_t *out);
+
 /* model.lambda = (1-rho) lambda' + rho (eta + scale * sstats), all device pointers.
  * src/onlinelda.cpp:99-100, :108-109; src/batchlda.cpp:60 (rho = 1, scale = 1). */
 int trlda_model_blend(trlda_model *model, const double *lambda_prime_dev,
@@ -898,6 +933,11 @@ int trlda_debug_gibbs_table(trlda_model *model, double *host_out);
 /* test hook: the beta prefix table the model's last trlda_model_sample call read (K x V,
  * TOPIC-MAJOR: element (k, w) at [w + V*k]; csrc/sample_kernels.h).  Fails after a Gibbs call. */
 int trlda_debug_sample_table(trlda_model *model, double *host_out);
+/* test hook: trlda_sample_dirichlet_device's draws under `key` stopped before the divide: w_out
+ * (m x n, host) gets W = exp(lg - column max), sums_out (n, host) the column sums S in the order
+ * csrc/dirichlet_kernels.h states (tests/dirichlet_host.py restates it from these W). m, n > 0. */
+int trlda_debug_dirichlet_sums(int m, int n, double alpha, uint64_t key, double *w_out, double *sums_out,
+                               int device);
 /* diagnostics: the s_memrealtime stamps of the model's last merged launch, 3 x 1024 values
  * (TRLDA_MERGED_STAMPS=1; tools/merged_stamps.py) */
 int trlda_debug_merged_stamps(trlda_model *model, unsigned long long *host_out);

@@ -10,9 +10,12 @@ script written against the reference -- its README example, say -- runs unchange
 
 Only the accelerated path exists, together with Gibbs inference on the GPU
 (``update_variables(docs, inference_method='gibbs')``) and sampling
-documents from a model on the GPU (``sample``); the ``load_users`` /
-``random_select`` / ``sample_dirichlet`` helpers are not part of it.
+documents from a model on the GPU (``sample``).
 ``predictive_log_likelihood`` scores a model on held-out words on the GPU.
+``trlda.utils`` has all six of the reference's names: ``polygamma`` of an array and
+``sample_dirichlet`` run on the GPU, ``random_select`` draws from the seeded stream as the
+reference does, and ``load_users`` / ``load_users_as_dict`` read rating files (DESIGN.md
+section 3.13).
 """
 __license__ = 'MIT License <http://www.opensource.org/licenses/mit-license.php>'
 __docformat__ = 'epytext'

@@ -113,6 +113,13 @@ _SIGNATURES = {
     "trlda_model_sample": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64]),
     "trlda_model_sample_host": (C.c_int, [vp, C.c_int, i32p, i32p, vp, C.c_uint64]),
     "trlda_debug_sample_table": (C.c_int, [vp, vp]),
+    "trlda_polygamma": (C.c_double, [C.c_int, C.c_double]),
+    "trlda_polygamma_device": (C.c_int, [C.c_int, C.c_int64, vp, vp, C.c_int]),
+    "trlda_polygamma_host": (C.c_int, [C.c_int, C.c_int64, vp, vp, C.c_int]),
+    "trlda_sample_dirichlet_device": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_uint64, vp, C.c_int]),
+    "trlda_sample_dirichlet_host": (C.c_int, [C.c_int, C.c_int, C.c_double, vp, C.c_int]),
+    "trlda_random_select": (C.c_int, [C.c_int, C.c_int, i32p]),
+    "trlda_debug_dirichlet_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_uint64, vp, vp, C.c_int]),
     "trlda_model_blend": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_double]),
     "trlda_model_tr_init": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),
     "trlda_model_wordcounts": (C.c_int, [vp, vp, vp]),

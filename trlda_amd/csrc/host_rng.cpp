@@ -16,6 +16,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <time.h>
 
@@ -291,6 +292,43 @@ void trlda_rng_set_state(const uint32_t *state33)
     std::memcpy(g_rng.x, state33, sizeof(g_rng.x));
     g_rng.f = (int)(state33[31] % 31u);
     g_rng.b = (int)(state33[32] % 31u);
+}
+
+// randomSelect (src/utils.cpp:351-378): the same draws of the same stream -- for k <= n / 2,
+// rand() % n until k distinct values are in (a std::set, as there); otherwise all n are in (a
+// bitmap, n < 2k + 2) and rand() % n until n - k are out.  The chosen indices, ascending, into
+// out[0 .. k).
+int trlda_random_select(int k, int n, int32_t *out)
+{
+    if (k > n)
+        return fail(TRLDA_ERR_ARG, "k must be smaller than n.");
+    if (k < 0 || n < 0)
+        return fail(TRLDA_ERR_ARG, "n and k must be non-negative.");
+    if (k > 0 && !out)
+        return fail(TRLDA_ERR_ARG, "NULL out");
+    rng_speculation_cancel();
+    if (k <= n / 2) {
+        std::set<int32_t> chosen;
+        while ((int)chosen.size() < k)
+            chosen.insert((int32_t)(g_rng.next() % (uint32_t)n));
+        std::copy(chosen.begin(), chosen.end(), out);
+        return TRLDA_OK;
+    }
+    std::vector<bool> in((size_t)n, true);
+    for (int i = 0; i < n - k; ++i) {
+        for (;;) {
+            const uint32_t v = g_rng.next() % (uint32_t)n;
+            if (in[v]) {
+                in[v] = false;
+                break;
+            }
+        }
+    }
+    int j = 0;
+    for (int v = 0; v < n; ++v)
+        if (in[(size_t)v])
+            out[j++] = v;
+    return TRLDA_OK;
 }
 
 void trlda_sample_gamma(int m, int n, int k, double *out)

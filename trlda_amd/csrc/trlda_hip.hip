@@ -46,6 +46,8 @@
 #include "gibbs_kernels.h"
 #include "sample_kernels.h"
 #include "heldout_kernels.h"
+#include "polygamma.h"
+#include "dirichlet_kernels.h"
 
 namespace {
 
@@ -7182,6 +7184,201 @@ int trlda_debug_fold16(int device, const double *in, double *out16, double *out4
     HIP_TRY(hipMemcpy(out16, o, 64 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out4, o + 64, 64 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out2, o + 128, 64 * sizeof(double), hipMemcpyDeviceToHost));
+    return TRLDA_OK;
+}
+
+// ---- the utilities: polygamma, sampleDirichlet (src/utils.cpp:107-123, :251-266) ----
+double trlda_polygamma(int n, double x)
+{
+    return trlda::pg_polygamma(n, x);
+}
+
+int trlda_polygamma_device(int n, int64_t count, const double *x_dev, double *y_dev, int device)
+{
+    if (count < 0)
+        return fail(TRLDA_ERR_ARG, "negative element count");
+    if (count > 0 && (!x_dev || !y_dev))
+        return fail(TRLDA_ERR_ARG, "NULL x / y");
+    int rc = use_device(device);
+    if (rc || count == 0)
+        return rc;
+    const int64_t blocks = std::min<int64_t>((count + trlda::kPolygammaThreads - 1) / trlda::kPolygammaThreads,
+                                             (int64_t)device_cus(device) * 64);
+    hipLaunchKernelGGL(trlda::polygamma_kernel, dim3((unsigned)blocks), dim3(trlda::kPolygammaThreads), 0, nullptr,
+                       n, count, x_dev, y_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return TRLDA_OK;
+}
+
+int trlda_polygamma_host(int n, int64_t count, const double *x, double *y, int device)
+{
+    if (count < 0)
+        return fail(TRLDA_ERR_ARG, "negative element count");
+    if (count > 0 && (!x || !y))
+        return fail(TRLDA_ERR_ARG, "NULL x / y");
+    int rc = use_device(device);
+    if (rc || count == 0)
+        return rc;
+    double *d = nullptr;
+    rc = dev_alloc(&d, 2 * (size_t)count);
+    if (rc)
+        return rc;
+    DevTemp guard;
+    guard.p = d;
+    const size_t bytes = (size_t)count * sizeof(double);
+    HIP_TRY(hipMemcpy(d, x, bytes, hipMemcpyHostToDevice));
+    rc = trlda_polygamma_device(n, count, d, d + count, device);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpy(y, d + count, bytes, hipMemcpyDeviceToHost));
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int dirichlet_check(int m, int n, double alpha)
+{
+    if (m < 0 || n < 0)
+        return fail(TRLDA_ERR_ARG, "m and n must be non-negative.");
+    if (!(alpha > 0.0) || !std::isfinite(alpha))
+        return fail(TRLDA_ERR_ARG, "alpha must be a positive finite number.");
+    return TRLDA_OK;
+}
+
+// the launch sequence of dirichlet_kernels.h on the null stream; waits for the device.  sums (a
+// test hook, device, n doubles) non-NULL: the columns are left as W, their sums S go to sums.
+int dirichlet_device(int m, int n, double alpha, uint64_t key, double *out, int device, double *sums = nullptr)
+{
+    using namespace trlda;
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    const int64_t cap = (int64_t)device_cus(device) * 64;       // workgroups of the striding reductions
+    // a launch's work-items (blocks x 256) must fit in 32 bits: at most 2^24 - 1 workgroups
+    const int64_t max_blocks = ((int64_t)1 << 24) - 1;
+    if (m <= kDirichletWaveRows) {
+        const int kpl = (m + kWave - 1) / kWave;
+        for (int64_t j0 = 0; j0 < n; j0 += max_blocks * kSampleWaves) {
+            const int64_t blocks = std::min<int64_t>(((int64_t)n - j0 + kSampleWaves - 1) / kSampleWaves, max_blocks);
+            hipLaunchKernelGGL(dirichlet_wave_kernel, dim3((unsigned)blocks), dim3(kSampleThreads), 0, nullptr, m, j0,
+                               (int64_t)n, kpl, alpha, k0, k1, out, sums);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        const int nchunk = (int)(((int64_t)m + kSampleChunk - 1) / kSampleChunk);
+        const int64_t nblocks = (int64_t)n * nchunk;
+        const int64_t cols = std::max<int64_t>(max_blocks / nchunk, 1);     // columns per launch
+        double *part = nullptr;
+        int rc = dev_alloc(&part, (size_t)nblocks + 2 * (size_t)n);
+        if (rc)
+            return rc;
+        DevTemp guard;
+        guard.p = part;
+        double *colmax = part + nblocks, *colsum = colmax + n;
+        const dim3 cgrid((unsigned)std::min<int64_t>(((int64_t)n + kSampleThreads - 1) / kSampleThreads, cap));
+        for (int64_t j0 = 0; j0 < n; j0 += cols) {
+            const dim3 grid((unsigned)(std::min<int64_t>(cols, n - j0) * nchunk));
+            hipLaunchKernelGGL(dirichlet_chunk_draw_kernel, grid, dim3(kSampleThreads), 0, nullptr, m, j0, nchunk,
+                               alpha, k0, k1, out, part);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(dirichlet_reduce_kernel<false>, cgrid, dim3(kSampleThreads), 0, nullptr, (int64_t)n,
+                           nchunk, part, colmax);
+        HIP_TRY(hipGetLastError());
+        for (int64_t j0 = 0; j0 < n; j0 += cols) {
+            const dim3 grid((unsigned)(std::min<int64_t>(cols, n - j0) * nchunk));
+            hipLaunchKernelGGL(dirichlet_chunk_exp_kernel, grid, dim3(kSampleThreads), 0, nullptr, m, j0, nchunk,
+                               colmax, out, part);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(dirichlet_reduce_kernel<true>, cgrid, dim3(kSampleThreads), 0, nullptr, (int64_t)n,
+                           nchunk, part, colsum);
+        HIP_TRY(hipGetLastError());
+        if (sums) {
+            HIP_TRY(hipMemcpyAsync(sums, colsum, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+        } else {
+            for (int64_t j0 = 0; j0 < n; j0 += cols) {
+                const dim3 grid((unsigned)(std::min<int64_t>(cols, n - j0) * nchunk));
+                hipLaunchKernelGGL(dirichlet_chunk_scale_kernel, grid, dim3(kSampleThreads), 0, nullptr, m, j0, nchunk,
+                                   colsum, out);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(nullptr));               // (before the guard frees part)
+        return TRLDA_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_sample_dirichlet_device(int m, int n, double alpha, uint64_t key, double *out_dev, int device)
+{
+    int rc = dirichlet_check(m, n, alpha);
+    if (rc)
+        return rc;
+    if ((size_t)m * (size_t)n == 0)
+        return TRLDA_OK;
+    if (!out_dev)
+        return fail(TRLDA_ERR_ARG, "NULL out");
+    rc = use_device(device);
+    if (rc)
+        return rc;
+    return dirichlet_device(m, n, alpha, key, out_dev, device);
+}
+
+int trlda_sample_dirichlet_host(int m, int n, double alpha, double *out, int device)
+{
+    int rc = dirichlet_check(m, n, alpha);
+    if (rc)
+        return rc;
+    const size_t count = (size_t)m * (size_t)n;
+    if (count > 0 && !out)
+        return fail(TRLDA_ERR_ARG, "NULL out");
+    if (count > 0 && (rc = use_device(device)))
+        return rc;
+    const uint64_t key = trlda_host::rng_draw_key();          // every valid call: two draws
+    if (count == 0)
+        return TRLDA_OK;
+    double *d = nullptr;
+    rc = dev_alloc(&d, count);
+    if (rc)
+        return rc;
+    DevTemp guard;
+    guard.p = d;
+    rc = dirichlet_device(m, n, alpha, key, d, device);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpy(out, d, count * sizeof(double), hipMemcpyDeviceToHost));
+    return TRLDA_OK;
+}
+
+int trlda_debug_dirichlet_sums(int m, int n, double alpha, uint64_t key, double *w_out, double *sums_out,
+                               int device)
+{
+    int rc = dirichlet_check(m, n, alpha);
+    if (rc)
+        return rc;
+    if (m == 0 || n == 0 || !w_out || !sums_out)
+        return fail(TRLDA_ERR_ARG, "bad Dirichlet sums arguments");
+    if ((rc = use_device(device)))
+        return rc;
+    const size_t count = (size_t)m * (size_t)n;
+    double *d = nullptr;
+    rc = dev_alloc(&d, count + (size_t)n);
+    if (rc)
+        return rc;
+    DevTemp guard;
+    guard.p = d;
+    rc = dirichlet_device(m, n, alpha, key, d, device, d + count);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpy(w_out, d, count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums_out, d + count, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return TRLDA_OK;
 }
 
