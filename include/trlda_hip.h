@@ -441,6 +441,31 @@ int trlda_model_predictive(trlda_model *model, const trlda_batch *observed,
                            const trlda_batch *heldout, double *gamma, int max_iter,
                            double threshold, double *loglik_out, double *tokens_out);
 
+/* Topic coherence (Mimno et al. 2011; Bouma 2009): the top words of each topic and the document
+ * counts of word lists, on the device (csrc/coherence_kernels.h).  The per-pair
+ * formulas are the caller's (host) arithmetic on the counts.  No reference counterpart. */
+
+/* words_out (K x top_n int32, host, topic-major: [k * top_n + r]) = the top_n word ids of each
+ * topic in decreasing order of lambda_kw, equal values by smaller id first -- the order of
+ * np.lexsort((arange(V), -lambda[k])); NaN after every number.  1 <= top_n <= min(V, 100), else
+ * TRLDA_ERR_ARG.  Pending deferred statistics and stream lanes are settled first.  Synchronises. */
+int trlda_model_top_words(trlda_model *model, int top_n, int32_t *words_out);
+
+/* A counting accumulator for T word lists of N ids each (words: T x N int32, host, row-major;
+ * 1 <= T, 2 <= N <= 100, ids in [0, V) and distinct within a row, else TRLDA_ERR_ARG), made for
+ * `model`'s V and device; it runs on the model's stream and must be destroyed before the model.
+ * Its counts stay on the device between batches. */
+typedef struct trlda_cooc trlda_cooc;
+int trlda_cooc_create(trlda_model *model, const int32_t *words, int T, int N, trlda_cooc **out);
+/* Adds a batch (made for the model's V and device, else TRLDA_ERR_ARG): document d contains word w
+ * when it has an entry (w, c) with c > 0.  Asynchronous; the batch may be destroyed at once. */
+int trlda_cooc_add(trlda_cooc *cooc, const trlda_batch *batch);
+/* The counts so far (host): doc_freq[T x N] (documents that contain word (t, i)),
+ * co_doc_freq[T x N x N] (documents that contain words (t, i) and (t, j); symmetric, doc_freq on
+ * the diagonal), *num_docs (documents added, empty ones included).  Synchronises. */
+int trlda_cooc_read(trlda_cooc *cooc, int64_t *doc_freq, int64_t *co_doc_freq, int64_t *num_docs);
+int trlda_cooc_destroy(trlda_cooc *cooc);
+
 /* LDA::updateVariablesGibbs (src/lda.cpp:224-293), reached from python/src/ldainterface.cpp:311-390
  * with inference_method='GIBBS': collapsed Gibbs sampling of the batch's topic assignments on the
  * device (csrc/gibbs_kernels.h), one wave64 per document, K <= 1024 (more: TRLDA_ERR_ARG).

@@ -20,6 +20,7 @@ SSTATS_SEGMENTED, SSTATS_ATOMIC = 0, 1
 
 i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(np.float64, flags="F_CONTIGUOUS")
+i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 vp = C.c_void_p
 
 _SIGNATURES = {
@@ -136,6 +137,11 @@ _SIGNATURES = {
     "trlda_model_lower_bound": (C.c_int, [vp, vp, f64p, C.c_double, C.c_double, C.c_int, C.c_double,
                                 C.POINTER(C.c_double)]),
     "trlda_model_predictive": (C.c_int, [vp, vp, vp, f64p, C.c_int, C.c_double, f64p, f64p]),
+    "trlda_model_top_words": (C.c_int, [vp, C.c_int, i32p]),
+    "trlda_cooc_create": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
+    "trlda_cooc_add": (C.c_int, [vp, vp]),
+    "trlda_cooc_read": (C.c_int, [vp, i64p, i64p, C.POINTER(C.c_int64)]),
+    "trlda_cooc_destroy": (C.c_int, [vp]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),
     "trlda_model_online_update_multi": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                                   C.c_int, C.c_int, C.c_double, C.c_double,

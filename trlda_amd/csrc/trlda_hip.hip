@@ -46,6 +46,7 @@
 #include "gibbs_kernels.h"
 #include "sample_kernels.h"
 #include "heldout_kernels.h"
+#include "coherence_kernels.h"
 #include "polygamma.h"
 #include "dirichlet_kernels.h"
 
@@ -4975,6 +4976,246 @@ int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_bat
         return rc_x;
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     std::memcpy(tokens_out, hbuf.data() + B, (size_t)B * sizeof(double));
+    return TRLDA_OK;
+}
+
+// ---- topic coherence: top words and document counts (csrc/coherence_kernels.h) ----
+
+// The top words: one read of lambda by tiles of word columns, then per topic a tree of merges of
+// 1024 candidates each, the last of which sorts
+int trlda_model_top_words(trlda_model *m, int top_n, int32_t *words_out)
+{
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!words_out)
+        return fail(TRLDA_ERR_ARG, "words_out is NULL");
+    if (top_n < 1 || top_n > trlda::kTopnMax || top_n > m->V)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
+    const int K = m->K, V = m->V, n = top_n;
+    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    if (K > 65535 || tiles > 65535)                      // (grid dimensions y)
+        return fail(TRLDA_ERR_ARG, "num_topics or num_words too large for the top-word kernels");
+    const size_t c1 = (size_t)tiles * n;                 // candidates per topic after the first level
+    const size_t c2 = (c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;   // after the second
+    // one allocation: the first level's candidates, the later levels' (ping-pong), the ids
+    const size_t off_b = (size_t)K * c1, cap = off_b + (size_t)K * c2;
+    DevTemp keys, ids;
+    HIP_TRY(hipMalloc(&keys.p, cap * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(&ids.p, (cap + (size_t)K * n) * sizeof(int32_t)));
+    uint64_t *kb = static_cast<uint64_t *>(keys.p);
+    int32_t *ib = static_cast<int32_t *>(ids.p);
+    int32_t *wout = ib + cap;
+    const size_t lds = (size_t)trlda::kTopnTileTopics * trlda::kTopnTileStride * sizeof(uint64_t);
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topn_tile_kernel), lds)))
+        return rc;
+    hipLaunchKernelGGL(trlda::topn_tile_kernel,
+                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, tiles),
+                       dim3(trlda::kTopnThreads), lds, m->stream, K, V, n, m->lambda, kb, ib);
+    HIP_TRY(hipGetLastError());
+    // (c2 <= c1: a level's output fits where its input was read from, in the other half)
+    uint64_t *ik = kb, *ok = kb + off_b;
+    int32_t *ii = ib, *oi = ib + off_b;
+    size_t c = c1;
+    while (c > (size_t)trlda::kTopnGroup) {
+        const size_t groups = (c + trlda::kTopnGroup - 1) / trlda::kTopnGroup;
+        hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3((unsigned)groups, K), dim3(trlda::kWave), 0,
+                           m->stream, n, (int)c, ik, ii, ok, oi, (int32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+        std::swap(ik, ok);
+        std::swap(ii, oi);
+        c = groups * n;
+    }
+    hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3(1, K), dim3(trlda::kWave), 0, m->stream, n, (int)c,
+                       ik, ii, (uint64_t *)nullptr, (int32_t *)nullptr, wout);
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(words_out, wout, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// The counting accumulator: the word lists and their slots on the device, the bit rows of one block
+// of documents at a time, and the int64 counts
+struct trlda_cooc {
+    trlda_model *model = nullptr;
+    int T = 0, N = 0, U = 0;
+    int block_docs = 64;                 // documents per block: U x block_docs / 8 bytes of bit rows
+    int32_t *slot_of_word = nullptr;     // V: the slot of a listed word, -1 for the others
+    int32_t *slot_of = nullptr;          // T x N: the slot of word (t, i)
+    unsigned long long *bits = nullptr;  // U x ceil(block_docs / 64)
+    long long *doc_freq = nullptr;       // U
+    long long *co = nullptr;             // T x N x N, i < j filled
+    std::vector<int32_t> slot_host;      // T x N
+    int64_t num_docs = 0;
+};
+
+namespace {
+
+constexpr size_t kCoocBitBytes = size_t(64) << 20;   // bit rows of a block: at most this, or 8 U bytes
+constexpr int kCoocMaxRowWords = 1024;               // (65 536 documents per block)
+
+void cooc_free(trlda_cooc *c)
+{
+    if (!c)
+        return;
+    (void)hipFree(c->slot_of_word);
+    (void)hipFree(c->slot_of);
+    (void)hipFree(c->bits);
+    (void)hipFree(c->doc_freq);
+    (void)hipFree(c->co);
+    delete c;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_cooc_create(trlda_model *m, const int32_t *words, int T, int N, trlda_cooc **out)
+{
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!words)
+        return fail(TRLDA_ERR_ARG, "words is NULL");
+    if (T < 1 || N < 2 || N > trlda::kTopnMax)
+        return fail(TRLDA_ERR_ARG, "word lists must number at least one and hold 2 to 100 ids each");
+    const int V = m->V;
+    const size_t TN = (size_t)T * N;
+    std::vector<int32_t> slot_of_word((size_t)V, -1), slot_host(TN);
+    int U = 0;
+    for (int t = 0; t < T; ++t) {
+        const int32_t *row = words + (size_t)t * N;
+        for (int i = 0; i < N; ++i) {
+            const int32_t w = row[i];
+            if (w < 0 || w >= V)
+                return fail(TRLDA_ERR_ARG, "word id out of range in the word lists");
+            for (int j = 0; j < i; ++j)
+                if (row[j] == w)
+                    return fail(TRLDA_ERR_ARG, "a word occurs twice in one word list");
+            if (slot_of_word[w] < 0)
+                slot_of_word[w] = U++;
+            slot_host[(size_t)t * N + i] = slot_of_word[w];
+        }
+    }
+    trlda_cooc *c = new trlda_cooc();
+    c->model = m;
+    c->T = T; c->N = N; c->U = U;
+    const size_t row_words = std::max<size_t>(1, std::min<size_t>(kCoocMaxRowWords, kCoocBitBytes / (8 * (size_t)U)));
+    c->block_docs = (int)(64 * row_words);
+    c->slot_host = std::move(slot_host);
+    rc = dev_alloc(&c->slot_of_word, (size_t)V);
+    if (!rc) rc = dev_alloc(&c->slot_of, TN);
+    if (!rc) rc = dev_alloc(&c->bits, (size_t)U * row_words);
+    if (!rc) rc = dev_alloc(&c->doc_freq, (size_t)U);
+    if (!rc) rc = dev_alloc(&c->co, TN * N);
+    if (!rc) {
+        hipError_t e1 = hipMemcpyAsync(c->slot_of_word, slot_of_word.data(), (size_t)V * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, m->stream);
+        hipError_t e2 = hipMemcpyAsync(c->slot_of, c->slot_host.data(), TN * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, m->stream);
+        hipError_t e3 = hipMemsetAsync(c->doc_freq, 0, (size_t)U * sizeof(long long), m->stream);
+        hipError_t e4 = hipMemsetAsync(c->co, 0, TN * N * sizeof(long long), m->stream);
+        hipError_t e5 = hipMemsetAsync(c->bits, 0, (size_t)U * row_words * sizeof(unsigned long long), m->stream);
+        hipError_t e6 = hipStreamSynchronize(m->stream);   // (the host vectors go out of scope)
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
+            e6 != hipSuccess)
+            rc = fail(TRLDA_ERR_HIP, "uploading the word lists failed");
+    }
+    if (rc) {
+        cooc_free(c);
+        return rc;
+    }
+    *out = c;
+    return TRLDA_OK;
+}
+
+int trlda_cooc_add(trlda_cooc *c, const trlda_batch *b)
+{
+    if (!c || !b)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    if (b->B > 0) {
+        if ((rc = batch_begin(m, b)))
+            return rc;
+        const size_t lds = ((size_t)c->N * trlda::kCoocChunkStride * sizeof(unsigned long long) +
+                            (size_t)c->N * c->N * sizeof(int));
+        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::cooc_pairs_kernel), lds)))
+            return rc;
+        const int per_wg = trlda::kCoocThreads / trlda::kWave;
+        for (int d0 = 0; d0 < b->B; d0 += c->block_docs) {
+            const int nb = std::min(c->block_docs, b->B - d0);
+            const int nw = (nb + 63) / 64;               // the rows' stride in this block
+            // (the rows are all zero here: zeroed at creation, cleared by the last block's cooc_df_kernel)
+            hipLaunchKernelGGL(trlda::cooc_bits_kernel, dim3((nb + per_wg - 1) / per_wg), dim3(trlda::kCoocThreads),
+                               0, m->stream, d0, nb, m->V, b->indptr, b->ids, b->cnts, c->slot_of_word, c->bits, nw);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(trlda::cooc_pairs_kernel, dim3(c->T), dim3(trlda::kCoocThreads), lds, m->stream,
+                               c->N, nw, c->slot_of, c->bits, c->co);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(trlda::cooc_df_kernel, dim3((c->U + per_wg - 1) / per_wg), dim3(trlda::kCoocThreads),
+                               0, m->stream, c->U, nw, c->bits, c->doc_freq);
+            HIP_TRY(hipGetLastError());
+        }
+        (void)batch_end(m, b);
+    }
+    c->num_docs += b->B;
+    return TRLDA_OK;
+}
+
+int trlda_cooc_read(trlda_cooc *c, int64_t *doc_freq, int64_t *co_doc_freq, int64_t *num_docs)
+{
+    if (!c || !doc_freq || !co_doc_freq || !num_docs)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int T = c->T, N = c->N;
+    const size_t TN = (size_t)T * N;
+    std::vector<long long> df((size_t)c->U);
+    hipError_t e1 = hipMemcpyAsync(df.data(), c->doc_freq, df.size() * sizeof(long long), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipMemcpyAsync(co_doc_freq, c->co, TN * N * sizeof(long long), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    for (int t = 0; t < T; ++t) {
+        int64_t *co = co_doc_freq + (size_t)t * N * N;
+        for (int i = 0; i < N; ++i) {
+            const int64_t d = df[(size_t)c->slot_host[(size_t)t * N + i]];
+            doc_freq[(size_t)t * N + i] = d;
+            co[(size_t)i * N + i] = d;
+            for (int j = 0; j < i; ++j)
+                co[(size_t)i * N + j] = co[(size_t)j * N + i];
+        }
+    }
+    *num_docs = c->num_docs;
+    return TRLDA_OK;
+}
+
+int trlda_cooc_destroy(trlda_cooc *c)
+{
+    if (!c)
+        return TRLDA_OK;
+    if (c->model && use_device(c->model->device) == TRLDA_OK && c->model->stream)
+        (void)hipStreamSynchronize(c->model->stream);    // (its kernels may still read the buffers)
+    cooc_free(c);
     return TRLDA_OK;
 }
 

@@ -64,6 +64,30 @@ def _inference_method(name):
     raise TypeError("`inference_method` should be either 'GIBBS' or 'VI'.")
 
 
+def _coherence(measure, doc_freq, co, num_docs):
+    """UMass / NPMI per word list from the device's counts (LDA.topic_coherence): K N^2-sized fp64
+    arithmetic on the host, the pairs (l, m), l < m, added in the order m ascending, then l
+    ascending."""
+    T, N = doc_freq.shape
+    m_idx, l_idx = np.array([(m, l) for m in range(1, N) for l in range(m)], dtype=np.int64).T
+    d_l = doc_freq[:, l_idx].astype(np.float64)
+    d_m = doc_freq[:, m_idx].astype(np.float64)
+    d_lm = co[:, l_idx, m_idx].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if measure == "umass":
+            keep = d_l > 0
+            term = np.where(keep, np.log((d_lm + 1.) / d_l), 0.)
+            used = keep.sum(axis=1)
+            total = np.cumsum(term, axis=1)[:, -1]
+            return np.where(used > 0, total / np.maximum(used, 1), np.nan)
+        M = float(num_docs)
+        log_m = np.log(M)
+        term = (np.log(d_lm) + log_m - np.log(d_l) - np.log(d_m)) / (log_m - np.log(d_lm))
+        term = np.where(d_lm == M, 1., term)
+        term = np.where(d_lm == 0, -1., term)
+        return np.cumsum(term, axis=1)[:, -1] / float(len(m_idx))
+
+
 class Distribution(object):
     """Abstract base (reference include/distribution.h, distributioninterface.cpp)."""
 
@@ -405,6 +429,91 @@ class LDA(Distribution):
         if return_documents:
             return score, loglik, tokens
         return score
+
+    # -- topic coherence (Mimno et al. 2011; Bouma 2009; csrc/coherence_kernels.h) -----------------
+    def top_words(self, top_n=10):
+        """The ``top_n`` word ids of each topic in decreasing order of lambda_kw (the order of
+        E[beta_kw] too), equal values by smaller word id first: row k is
+        ``np.lexsort((np.arange(V), -lambdas[k]))[:top_n]``.  Returns a K x top_n int32 array.
+        ``1 <= top_n <= min(num_words, 100)``, else RuntimeError.  The selection runs on the GPU;
+        only the ids come back."""
+        top_n = operator.index(top_n)
+        if not 1 <= top_n <= min(self._V, 100):
+            raise RuntimeError("`top_n` should lie between 1 and min(num_words, 100).")
+        self._settle()
+        words = np.empty((self._K, top_n), dtype=np.int32)
+        _ffi.check(_ffi.lib().trlda_model_top_words(self._handle, top_n, words))
+        return words
+
+    def topic_coherence(self, docs, top_n=10, measure='umass', words=None, return_counts=False):
+        """Coherence of each topic's top words on a corpus: float64, one value per word list.
+
+        ``docs`` is a batch (a list of documents, ``DocumentList``, ``CSRDocuments`` or a
+        ``DeviceBatch`` of this model) or an iterator of batches (anything with ``__next__``, e.g.
+        ``load_documents(path, 1000)``; for a list of batches pass ``iter(batches)``), whose counts
+        add up on the device.  ``words`` (T x N word ids, each row N >= 2 distinct ids in
+        [0, num_words), best first) replaces ``top_words(top_n)``; bad shapes, ids out of range
+        and repeated ids raise RuntimeError.
+
+        Document d contains word w when it has an entry (w, c) with c > 0 (repeated entries count
+        once).  M is the number of documents (empty ones included), D(w) the number containing w,
+        D(w, w') the number containing both.  For a list v_1 .. v_N:
+
+          'umass'  the mean over the pairs l < m of log((D(v_m, v_l) + 1) / D(v_l)), pairs with
+                   D(v_l) = 0 left out (NaN if none is left).  Mimno et al.'s sum is this times
+                   N (N - 1) / 2.
+          'npmi'   the mean over the pairs i < j of -1 if D_ij = 0, +1 if D_ij = M, otherwise
+                   (log D_ij + log M - log D_i - log D_j) / (log M - log D_ij).
+
+        The counting and the top-word selection run on the GPU; the per-pair formulas are fp64 on
+        the host, pairs added in the order m (j) ascending, then l (i) ascending.  ``measure`` is
+        case-insensitive; other values raise ValueError.  With ``return_counts=True`` returns
+        ``(coherence, counts)``, counts a dict of ``words`` (T x N int32), ``doc_freq`` (T x N
+        int64), ``co_doc_freq`` (T x N x N int64, symmetric, doc_freq on the diagonal) and
+        ``num_documents``.  lambda, alpha, eta, the counters and the random stream are left as
+        they are."""
+        if not isinstance(measure, str) or measure.lower() not in ("umass", "npmi"):
+            raise ValueError("`measure` should be either 'umass' or 'npmi'.")
+        measure = measure.lower()
+        self._settle()
+        if words is None:
+            top_n = operator.index(top_n)
+            if top_n < 2:
+                raise RuntimeError("Coherence needs `top_n` of at least 2.")
+            words = self.top_words(top_n)
+        else:
+            try:
+                w = np.asarray(words)
+            except (TypeError, ValueError):
+                raise RuntimeError("`words` should be a two-dimensional array of word ids.")
+            if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer):
+                raise RuntimeError("`words` should be a two-dimensional array of word ids.")
+            if ((w < 0) | (w >= self._V)).any():
+                raise RuntimeError("Word id out of range in `words`.")
+            words = np.ascontiguousarray(w, dtype=np.int32)
+        T, N = words.shape
+        L = _ffi.lib()
+        cooc = _ffi.vp()
+        _ffi.check(L.trlda_cooc_create(self._handle, words, T, N, C.byref(cooc)))
+        try:
+            for part in (docs if hasattr(docs, "__next__") else (docs,)):
+                batch, owned = self._batch(part)
+                try:
+                    _ffi.check(L.trlda_cooc_add(cooc, batch.handle))
+                finally:
+                    if owned:
+                        batch.close()
+            doc_freq = np.empty((T, N), dtype=np.int64)
+            co = np.empty((T, N, N), dtype=np.int64)
+            num_docs = C.c_int64(0)
+            _ffi.check(L.trlda_cooc_read(cooc, doc_freq, co, C.byref(num_docs)))
+        finally:
+            L.trlda_cooc_destroy(cooc)
+        coh = _coherence(measure, doc_freq, co, num_docs.value)
+        if return_counts:
+            return coh, {"words": words, "doc_freq": doc_freq, "co_doc_freq": co,
+                         "num_documents": int(num_docs.value)}
+        return coh
 
     # -- device reductions for the empirical-Bayes steps (csrc/eb_kernels.h) ----------------
     def _psi_gamma_diff_device(self, num_docs):
