@@ -320,7 +320,8 @@ int trlda_model_set_prefetch(trlda_model *model, int enabled);
 
 /* Deferred statistics for a STREAM of E-steps on an unchanged lambda (a corpus pass of
  * LDA::updateVariablesVI calls, src/lda.cpp:160-220: the statistics of one call, :207-217, feed
- * nothing of the next).  With the switch on, trlda_model_estep_io_next returns once its document
+ * nothing of the next).  With the switch on, trlda_model_estep_io_next (and through it
+ * trlda_model_estep_io_ahead and trlda_model_estep_corpus) returns once its document
  * launch is enqueued; the statistics of that call are formed by extra workgroups of the NEXT
  * trlda_model_estep_io_next call's document launch (on the CUs a 200-document batch leaves idle:
  * a step is then one launch), and are written into the `sstats_dev` THAT call was given.  They
@@ -332,7 +333,10 @@ int trlda_model_set_prefetch(trlda_model *model, int enabled);
  * always.  The sums and their order are those of the kernel of its own: bitwise the same
  * statistics.  Same range as the announcement above (small tables, K <= 128 even, batches of at
  * most 256 documents); elsewhere, and for whatever cannot ride along, the statistics are launched
- * as their own kernel.  Off by default: the Python classes never turn it on.
+ * as their own kernel.  Only those stream calls defer: every other entry point that runs an E-step
+ * (trlda_model_estep, trlda_model_estep_io, trlda_model_estep_host, trlda_model_lower_bound,
+ * trlda_model_predictive, the resident and update calls) forms its statistics within the call, with
+ * the switch on or off.  Off by default: the Python classes turn it on only inside an EStepStream.
  * trlda_model_last_deferred: bit 0 = the last E-step left its statistics pending, bit 1 = its
  * launch formed the statistics of the call before. */
 int trlda_model_set_deferred_stats(trlda_model *model, int enabled);

@@ -1105,6 +1105,11 @@ struct EstepOut {
     double inact_a = 0.0, inact_b = 0.0;
     int inact_rows = 0;
     const double *inact_part = nullptr;
+    // in: the call is an E-step of a deferred stream (trlda_model_estep_io_next / _io_ahead, and the
+    // corpus pass through them): only such a call may leave its statistics pending
+    // (trlda_model_set_deferred_stats).  Every other entry point reads or hands back the statistics
+    // itself, so they are formed within the call
+    bool stream = false;
     EstepOut() { upd = trlda::UpdateOut{}; }
     explicit EstepOut(double *sstats) : EstepOut() { upd.sstats = sstats; }
 };
@@ -1811,13 +1816,14 @@ int estep_begin(trlda_model *m, const trlda_batch *b, const EstepOut &out, int m
     // caller announced it, it fits the same path, and lambda is not about to change
     p.pre_next = next && p.fused && p.reg && !out.upd.lambda && !atomic && next->V == V &&
                  next->device == m->device && next->B > 0 && !m->lambda_exposed && m->sw.prefetch_next;
-    // Deferred statistics (trlda_model::pending).  launch_ok: this call is a plain E-step whose one
-    // document launch can take helper workgroups; defer_self: its own statistics wait for the next
+    // Deferred statistics (trlda_model::pending).  launch_ok: this call is a plain E-step of a stream
+    // (out.stream: nothing reads its statistics before the next call) whose one document launch can
+    // take helper workgroups; defer_self: its own statistics wait for the next
     // call; carry: its launch forms the statistics the call before left pending.  What cannot be
     // carried is launched as the kernel of its own before anything of this call overwrites what it
     // reads (the exp(psi(lambda)) buffer m->eeb, when this call fills it: estep_preamble)
     const double *sstats_dev = out.upd.sstats;
-    p.launch_ok = m->sw.deferred_stats && p.fused && !dp && !atomic && !out.upd.lambda && sstats_dev &&
+    p.launch_ok = m->sw.deferred_stats && out.stream && p.fused && !dp && !atomic && !out.upd.lambda && sstats_dev &&
                   B > 0 && K <= kRegMaxK && auto_docs && fused_update_available(m) && !p.comb;
     p.defer_self = p.launch_ok && stats_stage_fits(m, b);
     const bool writes_eeb = !(p.prefetched || p.handed);
@@ -4148,6 +4154,7 @@ int trlda_model_estep_io_next(trlda_model *m, const trlda_batch *b, const trlda_
         return fail(TRLDA_ERR_ARG, "NULL batch / gamma / sstats");
     }
     EstepOut out(sstats_dev);
+    out.stream = true;
     rc = estep_device(m, b, gamma_dev, out, max_iter, threshold, iters_dev, gamma0_dev, next);
     if (rc && m->pending.valid)                      // a refused call leaves nothing outstanding
         (void)flush_pending(m);
@@ -4643,6 +4650,7 @@ int trlda_model_estep_io_ahead(trlda_model *m, const trlda_batch *b, const trlda
     if (cal_first)
         HIP_TRY(hipEventRecord(cal.e[0], l->stream));
     EstepOut out(sstats_dev);
+    out.stream = true;
     call_clock.to(1);
     // (the batch this lane's NEXT launch will take: two ahead with the lanes in turn; the very next one
     // inside a one-lane stretch, whose last call hands over to the turns again)
