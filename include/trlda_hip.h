@@ -63,6 +63,16 @@ const char *trlda_last_error(void);       /* thread-local, never NULL */
 int trlda_version(void);
 int trlda_device_count(void);             /* number of HIP devices, 0 if none */
 
+/* The largest number of topics the variational path (every entry point that runs a VI E-step:
+ * the estep, stream, corpus, update, lower-bound and predictive calls, trlda_estep) takes: the
+ * general document kernel keeps 3 K + 4 doubles per workgroup in LDS (160 KiB on gfx950).  Above
+ * it those calls return TRLDA_ERR_ARG before they draw, copy or launch anything; Gibbs sampling,
+ * top words and sampling documents have bounds of their own.  trlda_vi_check_topics(K): that
+ * check on its own (TRLDA_OK, or TRLDA_ERR_ARG and the message). */
+#define TRLDA_VI_MAX_TOPICS 6814
+int trlda_vi_max_topics(void);
+int trlda_vi_check_topics(int K);
+
 /* ---- host-side RNG: bit-compatible with the reference ------------------ */
 
 /* trlda.seed(): srand(seed).  python/src/module.cpp:332-342 */
@@ -244,6 +254,8 @@ int trlda_model_set_doc_threads(trlda_model *model, int threads);
  * merged / deferred statistics, lanes) alone. */
 #define TRLDA_DOCS_SMALL 3
 #define TRLDA_DOCS_REG 4
+/* K > 512 always runs the general kernel; it takes K up to TRLDA_VI_MAX_TOPICS (its word rows
+ * stay in LDS while they fit, 36 words at K = 513, none from K = 5111; beyond, they are streamed). */
 int trlda_model_set_doc_kernel(trlda_model *model, int kind);
 /* name (as a profiler lists it, without template arguments) of the document kernel that
  * took most documents of the model's last E-step; "" before the first */

@@ -229,12 +229,13 @@ def test_batch_update_mass_balance_full_batch(hip):
 # fused device path == plain launch sequence, small tables and odd shapes
 # --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("K,V,B", [(100, 7000, 200), (7, 900, 33), (333, 13000, 40),
-                                   (129, 40000, 64), (512, 9000, 24),
+                                   (129, 40000, 64), (512, 9000, 24), (256, 3000, 48), (511, 2500, 40),
                                    (100, 1500, 3000), (200, 2000, 2500), (129, 1200, 2000)])
 def test_fused_update_equals_plain_sequence(hip, oracle, sampler, K, V, B):
     """Every update loop through both device paths: OnlineLDA with and without the trust region
     (twice, so that the second call runs on carried row sums), BatchLDA, CumulativeLDA.  K odd
-    (8-byte streaming accesses), K = 512 (four topic blocks), V not a multiple of anything; and
+    (8-byte streaming accesses), K = 512 (four topic blocks), the fused kernel's instantiations of
+    K = 256 and of odd K from 385 to 511 (K = 511), V not a multiple of anything; and
     thousands of documents over a small vocabulary: word lists of hundreds of entries walked by
     single wavefronts (the statistics kernels' per-batch threshold, kLongWord), the 512 longest by
     whole workgroups."""

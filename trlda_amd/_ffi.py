@@ -28,6 +28,8 @@ _SIGNATURES = {
     "trlda_last_error": (C.c_char_p, []),
     "trlda_version": (C.c_int, []),
     "trlda_device_count": (C.c_int, []),
+    "trlda_vi_max_topics": (C.c_int, []),
+    "trlda_vi_check_topics": (C.c_int, [C.c_int]),
     "trlda_seed": (None, [C.c_uint]),
     "trlda_rng_get_state": (None, [np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")]),
     "trlda_rng_set_state": (None, [np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")]),
@@ -270,6 +272,16 @@ class TrldaError(RuntimeError):
 def check(rc):
     if rc != OK:
         raise TrldaError(rc, lib().trlda_last_error().decode() or "trlda_hip error %d" % rc)
+
+
+def vi_max_topics():
+    """The largest number of topics the variational path takes (TRLDA_VI_MAX_TOPICS)."""
+    return lib().trlda_vi_max_topics()
+
+
+def check_vi_topics(num_topics):
+    """TrldaError(ERR_ARG) naming the bound when ``num_topics`` is above it."""
+    check(lib().trlda_vi_check_topics(int(num_topics)))
 
 
 def device_count():

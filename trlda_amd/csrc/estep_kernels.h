@@ -165,47 +165,65 @@ __global__ __launch_bounds__(T) void rowsum_combine_kernel(int K, int G,
 // sstats = 0 without reading eeb), so by default only those columns are computed: the
 // `active` list comes with the batch.  gamma and sstats are unchanged by this; eeb is not an
 // output.  trlda_model_set_dense_preamble(model, 1) fills all V columns as the reference does.
+//
+// LDS: 9 K doubles (psiSum + the 8 x K scratch), which fit gfx950's 160 KiB up to K = 2272.
+// Beyond, the launch code combines the block partials first (rowsum_combine_kernel, G = 1: the
+// same additions in the same order) and runs the Combined form, which reads the K sums and keeps
+// psiSum only (K doubles).
 // ---------------------------------------------------------------------------
 constexpr int kRowsumBlocks = 64;
 
-template <int T>
+template <int T, bool Combined = false>
 __global__ __launch_bounds__(T) void exp_elog_beta_kernel(
     int K, size_t total, int G, const double *__restrict__ lambda,
     const double *__restrict__ partial, double *__restrict__ psi_sum_out /* 2K: psi, then sums */,
     double *__restrict__ eeb, const int32_t *__restrict__ active /* word ids or nullptr */)
 {
-    extern __shared__ double psi_sum[];             // K, then 8 x K scratch
-    double *scratch = psi_sum + K;
-    // eight threads per topic, each adds G/8 block partials (all loads in flight), then
-    // one thread per topic combines the eight in order and applies psi
-    const int per = (G + 7) / 8;
-    for (int t = threadIdx.x; t < 8 * K; t += T) {
-        const int k = t % K, part = t / K;
-        const int b0 = part * per, b1 = min(G, b0 + per);
-        double acc[2] = {0.0, 0.0};
-        for (int b = b0; b < b1; b += 8) {
+    extern __shared__ double psi_sum[];             // K, then 8 x K scratch (not Combined)
+    if constexpr (Combined) {
+        // partial = the K row sums (one row)
+        for (int k = threadIdx.x; k < K; k += T) {
+            const double rs = partial[k];
+            const double ps = digamma(rs);
+            psi_sum[k] = ps;
+            if (blockIdx.x == 0) {
+                psi_sum_out[k] = ps;
+                psi_sum_out[K + k] = rs;
+            }
+        }
+    } else {
+        double *scratch = psi_sum + K;
+        // eight threads per topic, each adds G/8 block partials (all loads in flight), then
+        // one thread per topic combines the eight in order and applies psi
+        const int per = (G + 7) / 8;
+        for (int t = threadIdx.x; t < 8 * K; t += T) {
+            const int k = t % K, part = t / K;
+            const int b0 = part * per, b1 = min(G, b0 + per);
+            double acc[2] = {0.0, 0.0};
+            for (int b = b0; b < b1; b += 8) {
+                double v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    v[u] = partial[(size_t)min(b + u, G - 1) * K + k];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    acc[u & 1] += (b + u < b1) ? v[u] : 0.0;
+            }
+            scratch[part * K + k] = acc[0] + acc[1];
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < K; k += T) {
             double v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                v[u] = partial[(size_t)min(b + u, G - 1) * K + k];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                acc[u & 1] += (b + u < b1) ? v[u] : 0.0;
-        }
-        scratch[part * K + k] = acc[0] + acc[1];
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < K; k += T) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            v[u] = scratch[u * K + k];
-        const double rs = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-        const double ps = digamma(rs);
-        psi_sum[k] = ps;
-        if (blockIdx.x == 0) {
-            psi_sum_out[k] = ps;                     // kept for later kernels (elbo_kernels.h)
-            psi_sum_out[K + k] = rs;
+                v[u] = scratch[u * K + k];
+            const double rs = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+            const double ps = digamma(rs);
+            psi_sum[k] = ps;
+            if (blockIdx.x == 0) {
+                psi_sum_out[k] = ps;                     // kept for later kernels (elbo_kernels.h)
+                psi_sum_out[K + k] = rs;
+            }
         }
     }
     __syncthreads();

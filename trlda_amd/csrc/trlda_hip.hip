@@ -1069,13 +1069,33 @@ int launch_docs(trlda_model *m, const trlda::DocKernelArgs &args, int B, size_t 
     return TRLDA_OK;
 }
 
-size_t docs_lds_bytes(int K, int Kp, int n_cap, int T)
+constexpr size_t docs_lds_bytes(int K, int Kp, int n_cap, int T)
 {
     // beta[n_cap][Kp] | g[K] | e[K] | tw[n_cap] | cnt[n_cap] | part[max(T,K)] | wsum[T/64]
-    size_t doubles = (size_t)n_cap * Kp + 2 * (size_t)K + 2 * (size_t)n_cap +
-                     (size_t)std::max(T, K) + (size_t)(T / trlda::kWave);
-    return doubles * sizeof(double);
+    return ((size_t)n_cap * Kp + 2 * (size_t)K + 2 * (size_t)n_cap +
+            (size_t)std::max(T, K) + (size_t)(T / trlda::kWave)) * sizeof(double);
 }
+
+// The VI path's bound on K (include/trlda_hip.h): the general document kernel at its default 256
+// threads with no word rows in LDS -- g, e, part[K] and the wave sums, 3 K + 4 doubles -- must fit.
+// Every VI entry point checks it before it waits, draws, copies or launches anything, so a
+// rejected call leaves the model and the seeded stream as they were.
+static_assert(docs_lds_bytes(TRLDA_VI_MAX_TOPICS, TRLDA_VI_MAX_TOPICS | 1, 0, 256) <= (size_t)kLdsDynBytes &&
+                  docs_lds_bytes(TRLDA_VI_MAX_TOPICS + 1, (TRLDA_VI_MAX_TOPICS + 1) | 1, 0, 256) >
+                      (size_t)kLdsDynBytes,
+              "TRLDA_VI_MAX_TOPICS is the largest K whose document kernel fits LDS");
+
+int check_vi_topics(int K)
+{
+    if (K <= TRLDA_VI_MAX_TOPICS)
+        return TRLDA_OK;
+    return fail(TRLDA_ERR_ARG, "num_topics = " + std::to_string(K) +
+                                   " is above TRLDA_VI_MAX_TOPICS = " + std::to_string(TRLDA_VI_MAX_TOPICS) +
+                                   ": the variational E-step's document kernel keeps 3 K + 4 doubles "
+                                   "in a workgroup's 160 KiB of LDS");
+}
+
+int check_vi(const trlda_model *m) { return m ? check_vi_topics(m->K) : TRLDA_OK; }
 
 // What the statistics stage of an E-step leaves behind.
 struct EstepOut {
@@ -1954,11 +1974,33 @@ int estep_preamble(trlda_model *m, const trlda_batch *b, const EstepPlan &p, Pre
         constexpr int TE = 1024;
         const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
         const size_t lds = (size_t)K * 9 * sizeof(double);
-        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds)))
-            return rc;
-        hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, pr.G,
-                           m->lambda, pr.partial_in, m->psi_sum, m->eeb_cur, active);
-        HIP_TRY(hipGetLastError());
+        if (lds <= (size_t)kLdsDynBytes) {
+            if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds)))
+                return rc;
+            hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, pr.G,
+                               m->lambda, pr.partial_in, m->psi_sum, m->eeb_cur, active);
+            HIP_TRY(hipGetLastError());
+        } else {
+            // K > 2272: 9 K doubles do not fit.  The block partials become one row first (the
+            // last row of m->partial: the G <= 64 rows in use lie below it) -- the additions of
+            // the kernel's own prologue in the same order -- and the kernel keeps psiSum only
+            if (pr.G > 1) {
+                double *combined = m->partial + (size_t)(kMaxRowsumBlocks - 1) * K;
+                hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>,
+                                   dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
+                                   dim3(kDenseThreads), 0, m->stream, K, pr.G, pr.partial_in, combined);
+                HIP_TRY(hipGetLastError());
+                pr.partial_in = combined;
+                pr.G = 1;
+            }
+            const size_t lds1 = (size_t)K * sizeof(double);
+            auto kern = exp_elog_beta_kernel<TE, true>;
+            if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds1)))
+                return rc;
+            hipLaunchKernelGGL(kern, dim3(GE), dim3(TE), lds1, m->stream, K, total, pr.G, m->lambda,
+                               pr.partial_in, m->psi_sum, m->eeb_cur, active);
+            HIP_TRY(hipGetLastError());
+        }
     }
     return m->timing && (rc = stamp(m)) ? rc : TRLDA_OK;
 }
@@ -2438,7 +2480,8 @@ int estep_documents(trlda_model *m, const trlda_batch *b, const EstepPlan &p, co
     return m->timing && (rc = stamp(m)) ? rc : TRLDA_OK;
 }
 
-// one wavefront per word; 16 words per workgroup for small K, 8 from K = 256 on
+// one wavefront per word; 16 words per workgroup for small K, 8 from K = 256 on, fewer where the
+// long words' wpb x K partial sums would not fit LDS (4 from K = 2557, 2 from K = 5113)
 template <int TS>
 int launch_sstats_words(trlda_model *m, const trlda_batch *b, double *sstats_dev)
 {
@@ -2518,8 +2561,11 @@ int estep_statistics(trlda_model *m, const trlda_batch *b, const EstepPlan &p, c
     } else {
         if (!sstats_dev)
             return fail(TRLDA_ERR_ARG, "internal: the statistics need an sstats buffer");
-        if ((rc = p.K >= 256 ? launch_sstats_words<512>(m, b, sstats_dev)
-                             : launch_sstats_words<1024>(m, b, sstats_dev)))
+        const size_t row = (size_t)p.K * sizeof(double);
+        if ((rc = p.K < 256 ? launch_sstats_words<1024>(m, b, sstats_dev)
+                  : 8 * row <= (size_t)kLdsDynBytes ? launch_sstats_words<512>(m, b, sstats_dev)
+                  : 4 * row <= (size_t)kLdsDynBytes ? launch_sstats_words<256>(m, b, sstats_dev)
+                                                    : launch_sstats_words<128>(m, b, sstats_dev)))
             return rc;
     }
     HIP_TRY(hipGetLastError());
@@ -2797,6 +2843,10 @@ int check_model(const trlda_model *m, bool keep_pending = false, bool keep_lanes
 extern "C" {
 
 int trlda_version(void) { return 100; }
+
+int trlda_vi_max_topics(void) { return TRLDA_VI_MAX_TOPICS; }
+
+int trlda_vi_check_topics(int K) { return check_vi_topics(K); }
 
 int trlda_device_count(void)
 {
@@ -4109,6 +4159,8 @@ int trlda_model_get_sstats(trlda_model *m, double *host_sstats)
 int trlda_model_estep(trlda_model *m, const trlda_batch *b, double *gamma_dev, double *sstats_dev,
                       int max_iter, double threshold, int32_t *iters_dev)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -4124,6 +4176,8 @@ int trlda_model_estep_io(trlda_model *m, const trlda_batch *b, const double *gam
                          double *gamma_dev, double *sstats_dev, int max_iter, double threshold,
                          int32_t *iters_dev)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -4139,6 +4193,8 @@ int trlda_model_estep_io_next(trlda_model *m, const trlda_batch *b, const trlda_
                               const double *gamma0_dev, double *gamma_dev, double *sstats_dev,
                               int max_iter, double threshold, int32_t *iters_dev)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -4438,6 +4494,8 @@ int trlda_model_estep_io_ahead(trlda_model *m, const trlda_batch *b, const trlda
                                int n_upcoming, const double *gamma0_dev, double *gamma_dev,
                                double *sstats_dev, int max_iter, double threshold, int32_t *iters_dev)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     CallClock call_clock;
     if (int rc_built = batch_wait(b))
@@ -4731,6 +4789,8 @@ int trlda_model_estep_corpus(trlda_model *m, int64_t n_docs, const int64_t *offs
                              double *const *sstats_ring, int n_ring, int max_iter, double threshold,
                              int32_t *iters_dev)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     int rc = check_model(m);
     if (rc)
         return rc;
@@ -4809,6 +4869,8 @@ int trlda_model_set_prefetch(trlda_model *m, int enabled)
 int trlda_model_estep_host(trlda_model *m, const trlda_batch *b, double *gamma, double *sstats,
                            int max_iter, double threshold, int32_t *iters_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -4852,6 +4914,8 @@ int trlda_model_estep_host(trlda_model *m, const trlda_batch *b, double *gamma, 
 int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma, double eta,
                             double factor, int max_iter, double threshold, double *bound_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -4863,6 +4927,11 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     if (b->B <= 0)
         return fail(TRLDA_ERR_ARG, "the lower bound needs at least one document");
     rc = ensure_update_workspace(m, b->B);
+    if (rc)
+        return rc;
+    // elbo_docs_kernel's K + 16 doubles: more than 48 KiB from K = 6129 on
+    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::elbo_docs_kernel<kDenseThreads>),
+                            ((size_t)m->K + 4 * (kDenseThreads / trlda::kWave)) * sizeof(double));
     if (rc)
         return rc;
     const int K = m->K, V = m->V, B = b->B;
@@ -4926,6 +4995,8 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
 int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_batch *h, double *gamma,
                            int max_iter, double threshold, double *loglik_out, double *tokens_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(o))
         return rc_built;
@@ -5924,6 +5995,8 @@ int trlda_model_online_update(trlda_model *m, const trlda_batch *b, int num_docu
                               double rho, int init_gamma, int update_lambda, double threshold,
                               int *update_count, double *rho_out, double *gamma_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -5997,6 +6070,8 @@ int trlda_model_batch_update(trlda_model *m, const trlda_batch *b, double eta, i
                              int max_iter_inference, int update_lambda, double threshold,
                              double *gamma_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -6076,6 +6151,8 @@ int trlda_model_cumulative_update(trlda_model *m, const trlda_batch *b, int max_
                                   int max_iter_inference, int update_lambda, double threshold,
                                   double *gamma_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -6266,6 +6343,8 @@ int trlda_model_online_update_multi(trlda_model *m, const trlda_batch *shard, vo
                                     double rho, int init_gamma, double threshold, int *update_count,
                                     double *rho_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(shard))
         return rc_built;
@@ -6330,6 +6409,8 @@ int trlda_model_batch_update_multi(trlda_model *m, const trlda_batch *shard, voi
                                    int total_docs, int doc_lo, double eta, int max_epochs,
                                    int max_iter_inference, int update_lambda, double threshold)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(shard))
         return rc_built;
@@ -6370,6 +6451,8 @@ int trlda_model_batch_update_multi(trlda_model *m, const trlda_batch *shard, voi
 int trlda_model_estep_resident_shard(trlda_model *m, const trlda_batch *shard, int total_docs,
                                      int doc_lo, int max_iter, double threshold)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(shard))
         return rc_built;
@@ -6554,6 +6637,8 @@ int trlda_model_online_update_dp(trlda_model *m, const trlda_batch *batch, const
                                  double kappa, double tau, double rho, int init_gamma, double threshold,
                                  int *update_count, double *rho_out)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(batch))
         return rc_built;
@@ -6579,6 +6664,8 @@ int trlda_model_batch_update_dp(trlda_model *m, const trlda_batch *batch, const 
                                 double eta, int max_epochs, int max_iter_inference, int update_lambda,
                                 double threshold)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(batch))
         return rc_built;
@@ -6603,6 +6690,8 @@ int trlda_model_estep_dp(trlda_model *m, const trlda_batch *batch, const trlda_b
                          double threshold, int32_t *iters_dev, int mstep,
                          const double *lambda_prime_dev, double rho, double eta, double scale)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(batch))
         return rc_built;
@@ -6732,6 +6821,8 @@ int trlda_model_sample_gamma_cols(trlda_model *m, int rows, int cols, int col_lo
 
 int trlda_model_estep_resident(trlda_model *m, const trlda_batch *b, int max_iter, double threshold)
 {
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
         return rc_built;
@@ -7073,6 +7164,8 @@ int trlda_estep(int K, int V, int B, const int32_t *indptr, const int32_t *ids,
 {
     if (!lambda || !alpha || !sstats)
         return fail(TRLDA_ERR_ARG, "NULL lambda / alpha / sstats");
+    if (int rc_vi = check_vi_topics(K))
+        return rc_vi;
     trlda_model *m = nullptr;
     trlda_batch *b = nullptr;
     int rc = trlda_model_create(&m, device, K, V);

@@ -267,6 +267,7 @@ class LDA(Distribution):
             if return_iterations:
                 raise TypeError("`return_iterations` applies to VI only.")
             return self._update_variables_gibbs(docs, latents, num_samples, burn_in)
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
         batch, owned = self._batch(docs)
         try:
             self._settle()
@@ -351,6 +352,7 @@ class LDA(Distribution):
         if method != "VI":
             raise NotImplementedError(
                 "A lower bound from Gibbs samples (lda.cpp:224-293) is outside the accelerated path.")
+        _ffi.check_vi_topics(self._K)
         num_documents = int(num_documents)
         if num_documents < 0:
             num_documents = self._default_num_documents()            # onlinelda.cpp:184-191
@@ -387,6 +389,7 @@ class LDA(Distribution):
         Returns the score; with ``return_documents=True`` ``(score, loglik, tokens)``, each of the
         last two float64 of length B (per document the sum of c log p(w | d) and of c).  lambda,
         alpha, eta and the update counters stay as they are."""
+        _ffi.check_vi_topics(self._K)
         obs, own_obs = self._batch(observed)
         try:
             held, own_held = self._batch(heldout)
@@ -631,6 +634,7 @@ class OnlineLDA(LDA):
         sums over gamma, lambda and the statistics that the empirical-Bayes steps for alpha and
         eta and the adaptive learning rate need (onlinelda.cpp:116-175, csrc/eb_kernels.h); the
         host keeps the K- and scalar-sized Newton steps."""
+        _ffi.check_vi_topics(self._K)
         batch, owned = self._batch(docs)
         try:
             # (the previous call's empirical-Bayes step, if it is still on its way: the conversion
@@ -770,6 +774,7 @@ class BatchLDA(LDA):
         lambda = eta + sstats run on the GPU, as do the sums over gamma and lambda behind the
         alpha / eta line searches (batchlda.cpp:66-205); the searches themselves are K- and
         scalar-sized and run on the host."""
+        _ffi.check_vi_topics(self._K)
         batch, owned = self._batch(docs)
         try:
             B = len(batch)
@@ -832,6 +837,7 @@ class CumulativeLDA(LDA):
                           update_lambda=True, update_alpha=False, min_alpha=1e-6,
                           emp_bayes_threshold=1e-8, inference_threshold=0.001, verbosity=0):
         """cumulativeldainterface.cpp:115-160 -> cumulativelda.cpp:49-153."""
+        _ffi.check_vi_topics(self._K)
         batch, owned = self._batch(docs)
         try:
             B = len(batch)
