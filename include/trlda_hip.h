@@ -648,6 +648,41 @@ int trlda_model_batch_update(trlda_model *model, const trlda_batch *batch, doubl
                              double threshold, double *gamma_out);
 
 /*
+ * OnlineLDA::updateParameters with inferenceMethod = GIBBS (src/onlinelda.cpp:53-179, its
+ * E-steps through src/lda.cpp:119-157 -> 224-293; Mimno, Hoffman & Blei 2012): with
+ * max_iter_tr > 0, the initial step from the word counts (:79-86), then max_iter_tr x
+ * { Gibbs E-step; lambda = (1 - rho) lambda' + rho (eta + D / B sstats) } (:89-101); with
+ * max_iter_tr = 0, one E-step on lambda as it is and the same blend (:103-109).  rho < 0: the
+ * schedule (tau + update_count)^-kappa (:59-66).  init_theta != 0: every iteration after the first
+ * starts from the previous iteration's theta, else from Dirichlet(1) (lda.cpp:123-128).
+ * Each E-step is trlda_model_gibbs with the key of trlda_rng_draw_key, drawn in loop order after
+ * every argument check (an error draws nothing and leaves lambda alone).  The loop runs on the
+ * device without a wait (csrc/gibbs_kernels.h, gibbs_mstep_kernel): the words outside the batch
+ * are written once per call, each iteration touches the batch's active words only.  With
+ * trlda_model_set_keep_sstats on, the statistics (trlda_model_get_sstats) and the whole lambda'
+ * stay behind for trlda_model_adaptive_stats.  K <= 1024, num_samples, burn_in >= 0 (else
+ * TRLDA_ERR_ARG).  theta_out: optional host K x B, theta of the last E-step.  Inside the loop
+ * nothing waits for the device; the call waits at its end (the sampler's failure flag), and before
+ * the loop when the batch is not the one the model last made a Gibbs plan for (trlda_model_gibbs:
+ * the token counts are downloaded and the plan uploaded, two waits -- once per new batch).  A
+ * histogram that sums to 0 or is not finite fails the call with "Something went wrong while
+ * sampling from histogram." (lambda is then already written).
+ */
+int trlda_model_online_update_gibbs(trlda_model *model, const trlda_batch *batch, int num_documents,
+                                    double eta, int max_iter_tr, double kappa, double tau, double rho,
+                                    int init_theta, int update_lambda, int num_samples, int burn_in,
+                                    int *update_count, double *rho_out, double *theta_out);
+
+/*
+ * BatchLDA::updateParameters with inferenceMethod = GIBBS (src/batchlda.cpp:43-61): max_epochs x
+ * { Gibbs E-step from a fresh Dirichlet(1) theta; lambda = eta + sstats }, as
+ * trlda_model_online_update_gibbs does it (keys, checks, one wait).
+ */
+int trlda_model_batch_update_gibbs(trlda_model *model, const trlda_batch *batch, double eta,
+                                   int max_epochs, int update_lambda, int num_samples, int burn_in,
+                                   double *theta_out);
+
+/*
  * CumulativeLDA::updateParameters, lambda path: src/cumulativelda.cpp:49-72 -- lambda' =
  * lambda; lambda = sampleGamma(K, V, 100)/100 (drawn whether or not update_lambda is set,
  * like the reference); max_epochs x { E-step from a fresh random gamma; lambda = lambda' +

@@ -134,6 +134,12 @@ _SIGNATURES = {
                                             vp]),
     "trlda_model_batch_update": (C.c_int, [vp, vp, C.c_double, C.c_int, C.c_int, C.c_int,
                                            C.c_double, vp]),
+    "trlda_model_online_update_gibbs": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                  C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                  vp]),
+    "trlda_model_batch_update_gibbs": (C.c_int, [vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 vp]),
     "trlda_model_cumulative_update": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                                 vp]),
     "trlda_model_lower_bound": (C.c_int, [vp, vp, f64p, C.c_double, C.c_double, C.c_int, C.c_double,

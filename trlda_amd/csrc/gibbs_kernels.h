@@ -11,6 +11,9 @@
 //   3. gibbs_docs_kernel<KPL>  per document: init, burn_in + num_samples sweeps, theta
 //                                                                                  lda.cpp:241-290
 //   4. gibbs_finish_kernel  sstats = count * unit over K x V, the counts back to 0
+// Inside the update loops (trlda_model_online_update_gibbs / _batch_update_gibbs)
+// 3 is followed by gibbs_mstep_kernel over the batch's active words instead of 4, and the table of
+// 1 comes from the row sums the M-step left behind (exp_elog_beta_kernel's combined form).
 //
 // Semantics (the reference's, with the deviations DESIGN.md section 3.10 lists):
 //   init    each token of entry j draws z from e[:, w] * theta[:, i] (theta0 column i -- the
@@ -158,6 +161,98 @@ __global__ __launch_bounds__(T) void gibbs_finish_kernel(size_t total, double un
         if (c)
             cnt[i] = 0u;
     }
+}
+
+// ---- inside the update loops (trlda_model_online_update_gibbs / _batch_update_gibbs) ------
+// Per E-step of a trust-region iteration or epoch, over the batch's ACTIVE columns only (a word
+// outside the batch has no tokens: its lambda was given its final value once per call):
+//   s      = count * unit                               (unit = 1 / num_samples, 0 without samples)
+//   lambda = omr * lambda' + rho * (eta + scale * s)    onlinelda.cpp:99-100 (omr = 1 - rho,
+//            scale = D / B), batchlda.cpp:60 (omr = 0 without reading lambda', rho = 1, scale = 1)
+// evaluated in that order without contraction; the counts go back to 0 (they are zero between
+// calls), s is kept only where `sstats` is given, and each workgroup leaves the row sums of the
+// columns it wrote as one row of `partial` (its columns in order, then its column slots in order).
+// Workgroup g takes positions [n g / G, n (g + 1) / G) of the active list.  K <= 256 (KPT = 1):
+// K threads per column, T / K column slots; K > 256 (KPT = 4): one column at a time, topic
+// k = thread + q T.
+constexpr int kGibbsMstepThreads = 256;
+constexpr int kGibbsMstepMaxBlocks = 1024;
+
+template <int T, int KPT>
+__global__ __launch_bounds__(T) void gibbs_mstep_kernel(int K, int n_active, int cpb,
+                                                        const int32_t *__restrict__ active, double omr,
+                                                        double rho, double eta, double scale, double unit,
+                                                        const double *lambda_prime /* or nullptr */,
+                                                        uint32_t *__restrict__ cnt, double *lambda,
+                                                        double *__restrict__ sstats /* or nullptr */,
+                                                        double *__restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double scratch[T];
+    const int P = KPT == 1 ? K : T;
+    const int slot = threadIdx.x / P, kp = threadIdx.x - slot * P;
+    const int j0 = (int)((long long)n_active * blockIdx.x / gridDim.x);
+    const int j1 = (int)((long long)n_active * (blockIdx.x + 1) / gridDim.x);
+    double acc[KPT];
+#pragma unroll
+    for (int q = 0; q < KPT; ++q)
+        acc[q] = 0.0;
+    if (slot < cpb) {
+        for (int j = j0 + slot; j < j1; j += cpb) {
+            const size_t col = (size_t)active[j] * K;
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                const int k = kp + q * T;
+                if (KPT == 1 || k < K) {
+                    const size_t i = col + k;
+                    const uint32_t c = cnt[i];
+                    if (c)
+                        cnt[i] = 0u;
+                    const double s = (double)c * unit;
+                    const double hat = eta + scale * s;
+                    const double lp = lambda_prime ? omr * lambda_prime[i] : 0.0;
+                    const double y = lp + rho * hat;
+                    lambda[i] = y;
+                    if (sstats)
+                        sstats[i] = s;
+                    acc[q] += y;
+                }
+            }
+        }
+    }
+    double *row = partial + (size_t)blockIdx.x * K;
+    if constexpr (KPT == 1) {
+        if (slot < cpb)
+            scratch[slot * K + kp] = acc[0];
+        __syncthreads();
+        for (int k = threadIdx.x; k < K; k += T) {
+            double s = scratch[k];
+            for (int sl = 1; sl < cpb; ++sl)
+                s += scratch[sl * K + k];
+            row[k] = s;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < KPT; ++q) {
+            const int k = kp + q * T;
+            if (k < K)
+                row[k] = acc[q];
+        }
+    }
+}
+
+// flag = 1 when an element of lambda is not > 0 (NaN included): what trlda_model_set_lambda
+// learns from a host copy, for the lambda an update left behind
+template <int T>
+__global__ __launch_bounds__(T) void gibbs_nonpositive_kernel(size_t total, const double *__restrict__ lambda,
+                                                              int *__restrict__ flag)
+{
+    const size_t stride = (size_t)gridDim.x * T;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * T + threadIdx.x; i < total; i += stride)
+        bad |= !(lambda[i] > 0.0);
+    if (__any(bad) && (threadIdx.x & (kWave - 1)) == 0)
+        atomicOr(flag, 1);
 }
 
 // One wave per document, kGibbsWaves documents per workgroup; the waves never wait for each other.

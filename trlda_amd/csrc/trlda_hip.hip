@@ -611,6 +611,12 @@ struct trlda_model {
         uint64_t plan_batch = 0;
         int64_t total_tokens = 0;
         int table_user = 0;                     // who filled `eeb` last: 1 Gibbs, 2 sample (it shares it)
+        // the update loops (trlda_model_online_update_gibbs / _batch_update_gibbs): row sums
+        // (the words outside the batch, then those of lambda as it stands), the M-step's block
+        // rows, and the "lambda has an element <= 0" flag
+        double *rs = nullptr, *mpart = nullptr;
+        size_t cap_rs = 0, cap_mpart = 0;
+        int *nonpos = nullptr;
     } gibbs;
     // sampling documents (sample_kernels.h, trlda_model_sample): the K x V prefix table lives in
     // gibbs.eeb (per-call scratch of either path, behind a flush); the rest is its own
@@ -3924,6 +3930,7 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->gibbs.cnt); (void)hipFree(m->gibbs.z); (void)hipFree(m->gibbs.tokens);
         (void)hipFree(m->gibbs.tok_off); (void)hipFree(m->gibbs.order); (void)hipFree(m->gibbs.flag);
         (void)hipFree(m->gibbs.theta_in); (void)hipFree(m->gibbs.theta); (void)hipFree(m->gibbs.sstats);
+        (void)hipFree(m->gibbs.rs); (void)hipFree(m->gibbs.mpart); (void)hipFree(m->gibbs.nonpos);
         (void)hipFree(m->sample.part); (void)hipFree(m->sample.pre); (void)hipFree(m->sample.indptr);
         (void)hipFree(m->sample.ids); (void)hipFree(m->sample.theta);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
@@ -5555,6 +5562,288 @@ int trlda_debug_gibbs_table(trlda_model *m, double *host_eeb)
     HIP_TRY(hipMemcpyAsync(host_eeb, m->gibbs.eeb, (size_t)m->K * m->V * sizeof(double), hipMemcpyDeviceToHost,
                            m->stream));
     return sync_model(m);
+}
+
+// ---- Gibbs inside the update loops: OnlineLDA::updateParameters (src/onlinelda.cpp:53-179) and
+// BatchLDA::updateParameters (src/batchlda.cpp:43-61) with inferenceMethod = GIBBS ----
+}  // extern "C"
+
+namespace {
+
+// e = exp(psi(lambda) - psi(rs)) of the batch's active words into m->gibbs.eeb, from finished
+// row sums `rs` (K): the sweeps that follow read it
+int gibbs_table(trlda_model *m, const trlda_batch *b, const double *rs)
+{
+    using namespace trlda;
+    auto &g = m->gibbs;
+    const int K = m->K;
+    int rc = grow(&g.eeb, &g.cap_eeb, std::max<size_t>((size_t)K * m->V, 1));
+    if (!rc) rc = grow(&g.psi_sum, &g.cap_psi, 3 * (size_t)K);
+    if (rc)
+        return rc;
+    g.table_user = 1;
+    if (b->n_active <= 0)
+        return TRLDA_OK;
+    constexpr int TE = 1024;
+    const size_t total = (size_t)K * (size_t)b->n_active;
+    const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
+    const size_t lds = (size_t)K * sizeof(double);
+    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE, true>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL((exp_elog_beta_kernel<TE, true>), dim3(GE), dim3(TE), lds, m->stream, K, total, 1,
+                       m->lambda, rs, g.psi_sum, g.eeb, b->active);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// one M-step over the batch's active columns (gibbs_mstep_kernel), then rs = base + its block rows
+int gibbs_mstep(trlda_model *m, const trlda_batch *b, double omr, double rho, double eta, double scale,
+                double unit, const double *lambda_prime, double *sstats, const double *base, double *rs)
+{
+    using namespace trlda;
+    constexpr int T = kGibbsMstepThreads;
+    auto &g = m->gibbs;
+    const int K = m->K, n = std::max(b->n_active, 0);
+    const int cpb = K <= T ? T / K : 1;
+    const int G = (int)std::max<long long>(1, std::min<long long>(kGibbsMstepMaxBlocks, ((long long)n + cpb - 1) / cpb));
+    if (K <= T)
+        hipLaunchKernelGGL((gibbs_mstep_kernel<T, 1>), dim3(G), dim3(T), 0, m->stream, K, n, cpb, b->active, omr,
+                           rho, eta, scale, unit, lambda_prime, g.cnt, m->lambda, sstats, g.mpart);
+    else
+        hipLaunchKernelGGL((gibbs_mstep_kernel<T, (kGibbsMaxK + T - 1) / T>), dim3(G), dim3(T), 0, m->stream, K,
+                           n, cpb, b->active, omr, rho, eta, scale, unit, lambda_prime, g.cnt, m->lambda, sstats,
+                           g.mpart);
+    HIP_TRY(hipGetLastError());
+    return combine_rowsums(m, g.mpart, G, base, rs);
+}
+
+struct GibbsUpdate {
+    bool online;            // OnlineLDA (trust-region loop) or BatchLDA (epochs)
+    int steps;              // online: max_iter_tr; batch: max_epochs
+    double eta, rho;        // rho: online only
+    int num_documents;      // online only
+    bool init_theta;        // online: iterations after the first start from the last theta
+    int num_samples, burn_in;
+    double *theta_out;      // host K x B, or nullptr
+};
+
+// The whole call on the model's stream; one wait, at the end (the sampler's sticky failure flag,
+// the positivity flag and the row sums of the new lambda).
+int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate &u)
+{
+    using namespace trlda;
+    const int K = m->K, V = m->V, B = b->B;
+    const size_t KV = (size_t)K * V;
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
+    int rc = ensure_update_workspace(m, B);
+    if (!rc) rc = batch_begin(m, b);
+    if (!rc) rc = gibbs_plan(m, b);
+    if (rc)
+        return rc;
+    auto &g = m->gibbs;
+    if (g.total_tokens * (int64_t)std::max(u.num_samples, 1) > (int64_t)UINT32_MAX)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
+                                   "counters; split the batch");
+    const bool fresh_cnt = !g.cnt || g.cap_cnt < KV;
+    const size_t tcount = (size_t)K * std::max(B, 1);
+    rc = grow(&g.cnt, &g.cap_cnt, std::max<size_t>(KV, 1));
+    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    if (!rc && !g.nonpos) rc = dev_alloc(&g.nonpos, 1);
+    if (!rc) rc = grow(&g.rs, &g.cap_rs, 2 * (size_t)K);
+    if (!rc) rc = grow(&g.mpart, &g.cap_mpart, (size_t)kGibbsMstepMaxBlocks * K);
+    if (!rc) rc = grow(&g.theta, &g.cap_theta, tcount);
+    if (!rc) rc = grow(&g.theta_in, &g.cap_theta_in, tcount);
+    if (rc)
+        return rc;
+
+    // the E-steps' Philox keys, two draws of the libc stream each, in loop order (onlinelda.cpp:89,
+    // :103; batchlda.cpp:48) -- after every check: a call that fails up to here draws nothing
+    const int esteps = u.online ? std::max(u.steps, 1) : std::max(u.steps, 0);
+    std::vector<uint64_t> keys((size_t)esteps);
+    for (auto &k : keys)
+        k = trlda_host::rng_draw_key();
+    if (esteps == 0)
+        return batch_end(m, b);
+
+    // lambda is written from here on: nothing the VI path keeps about it stays valid
+    invalidate_rowsums(m);
+    m->next_pre.valid = false;
+    m->u_left.valid = false;
+    m->lambda_positive = false;
+    m->rs_floor = 0.0;
+
+    if (fresh_cnt)
+        HIP_TRY(hipMemsetAsync(g.cnt, 0, KV * sizeof(uint32_t), m->stream));
+    HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
+    HIP_TRY(hipMemsetAsync(g.nonpos, 0, sizeof(int), m->stream));
+    const bool keep = m->keep_sstats;      // adaptive rate: whole lambda' and the statistics stay
+    double *sstats = keep ? m->sstats : nullptr;
+    if (keep)
+        HIP_TRY(hipMemsetAsync(m->sstats, 0, KV * sizeof(double), m->stream));
+    double *rs_static = g.rs, *rs = g.rs + K;
+    const double rho = u.online ? u.rho : 1.0, omr = u.online ? 1. - u.rho : 0.0;
+    const double scale = u.online ? (double)u.num_documents / (double)B : 1.0;
+    const double unit = u.num_samples > 0 ? 1.0 / u.num_samples : 0.0;
+    const double *lambda_prime = nullptr;
+    int G = 0;
+    if (u.online && u.steps > 0) {
+        // onlinelda.cpp:68, 79-86: lambda' saved, the initial step from the word counts for the
+        // active words, the final value (1 - rho) lambda' + rho eta for all the others
+        const int32_t *wc32 = b->wc32_ok ? b->wc32 : nullptr;
+        if (!wc32) rc = wordcounts_device(m, b, m->wordcounts);
+        const double coef = (double)u.num_documents / (double)B / (double)K;   // onlinelda.cpp:86
+        if (!rc)
+            rc = keep ? launch_inactive_update<ACT_TRINIT, true>(m, omr, rho * u.eta, rho, u.eta, coef,
+                                                                  b->active_flag, m->wordcounts, m->lambda,
+                                                                  m->lambda_prime, &G, wc32)
+                      : launch_inactive_update<ACT_TRINIT, false>(m, omr, rho * u.eta, rho, u.eta, coef,
+                                                                   b->active_flag, m->wordcounts, m->lambda,
+                                                                   m->lambda_prime, &G, wc32);
+        if (!rc) rc = combine_rowsums(m, m->partial, G, nullptr, rs_static);
+        if (!rc) rc = combine_rowsums(m, m->partial + (size_t)kStreamMaxBlocks * K, G, rs_static, rs);
+        if (!rc) rc = gibbs_table(m, b, rs);
+        lambda_prime = m->lambda_prime;
+    } else {
+        // onlinelda.cpp:103-109 / batchlda.cpp:60: the first E-step sees lambda as it is (its row
+        // sums from scratch, once); the words outside the batch then get their final value
+        rc = gibbs_preamble(m, b);
+        if (!rc && u.online) {
+            lambda_prime = m->lambda;                       // in place
+            if (keep) {
+                HIP_TRY(hipMemcpyAsync(m->lambda_prime, m->lambda, KV * sizeof(double), hipMemcpyDeviceToDevice,
+                                       m->stream));
+                lambda_prime = m->lambda_prime;
+            }
+        }
+        if (!rc)
+            rc = launch_inactive_update<ACT_KEEP, false>(m, omr, rho * u.eta, rho, u.eta, 0., b->active_flag,
+                                                         nullptr, m->lambda, nullptr, &G);
+        if (!rc) rc = combine_rowsums(m, m->partial, G, nullptr, rs_static);
+    }
+    if (rc)
+        return rc;
+
+    double *th[2] = {g.theta, g.theta_in};
+    const int kpl = (K + kWave - 1) / kWave;
+    for (int i = 0; i < esteps; ++i) {
+        GibbsArgs a;
+        a.K = K; a.B = B; a.sweeps = u.num_samples + u.burn_in; a.burn_in = u.burn_in;
+        a.key0 = (uint32_t)keys[(size_t)i]; a.key1 = (uint32_t)(keys[(size_t)i] >> 32);
+        a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
+        a.order = g.order; a.tok_off = g.tok_off;
+        a.eeb = g.eeb; a.alpha = m->alpha;
+        a.theta0 = (u.online && u.init_theta && i > 0) ? th[(i - 1) & 1] : nullptr;   // lda.cpp:123-128
+        a.theta = th[i & 1];
+        a.z = g.z; a.cnt = g.cnt; a.flag = g.flag;
+        rc = kpl <= 1 ? gibbs_launch_docs<1>(m, a) : kpl <= 2 ? gibbs_launch_docs<2>(m, a)
+           : kpl <= 4 ? gibbs_launch_docs<4>(m, a) : kpl <= 8 ? gibbs_launch_docs<8>(m, a)
+           : gibbs_launch_docs<16>(m, a);
+        if (!rc)
+            rc = gibbs_mstep(m, b, omr, rho, u.eta, scale, unit, lambda_prime, sstats, rs_static, rs);
+        if (!rc && i + 1 < esteps)
+            rc = gibbs_table(m, b, rs);
+        if (rc)
+            return rc;
+    }
+    if (KV) {
+        constexpr int TP = 256;
+        const int GP = (int)std::max<size_t>(1, std::min<size_t>((KV + TP - 1) / TP, 2048));
+        hipLaunchKernelGGL(gibbs_nonpositive_kernel<TP>, dim3(GP), dim3(TP), 0, m->stream, KV, m->lambda, g.nonpos);
+        HIP_TRY(hipGetLastError());
+    }
+    (void)batch_end(m, b);
+    const size_t tbytes = (size_t)K * B * sizeof(double);
+    if (u.theta_out && tbytes) {
+        HIP_TRY(hipMemcpyAsync(u.theta_out, th[(esteps - 1) & 1], tbytes, hipMemcpyDeviceToHost, m->stream));
+        m->d2h_bytes += (int64_t)tbytes;
+    }
+    int flag = 0, nonpos = 0;
+    std::vector<double> rs_host((size_t)K);
+    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(&nonpos, g.nonpos, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(rs_host.data(), rs, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    // what trlda_model_set_lambda would learn from a host copy of this lambda (note_host_lambda)
+    m->lambda_positive = nonpos == 0;
+    if (KV < ((size_t)1 << 22) && K <= kRegMaxK) {
+        double lo = rs_host[0];
+        for (int k = 1; k < K; ++k)
+            lo = std::min(lo, rs_host[(size_t)k]);
+        m->rs_floor = lo > 0.0 ? 0.999 * lo : 0.0;
+    }
+    ++m->lambda_version;
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+    return TRLDA_OK;
+}
+
+int gibbs_update_checks(trlda_model *m, const trlda_batch *b, int num_samples, int burn_in)
+{
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b)
+        return fail(TRLDA_ERR_ARG, "NULL batch");
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
+    if (m->K > trlda::kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling supports at most 1024 topics");
+    if (num_samples < 0 || burn_in < 0 || (long long)num_samples + burn_in > INT32_MAX)
+        return fail(TRLDA_ERR_ARG, "num_samples and burn_in should not be negative");
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_online_update_gibbs(trlda_model *m, const trlda_batch *b, int num_documents, double eta,
+                                    int max_iter_tr, double kappa, double tau, double rho, int init_theta,
+                                    int update_lambda, int num_samples, int burn_in, int *update_count,
+                                    double *rho_out, double *theta_out)
+{
+    if (int rc = gibbs_update_checks(m, b, num_samples, burn_in))
+        return rc;
+    if (!update_count || !rho_out)
+        return fail(TRLDA_ERR_ARG, "NULL update_count / rho_out");
+    if (b->B == 0) {                                         // onlinelda.cpp:54-56
+        *rho_out = 1.0;
+        return TRLDA_OK;
+    }
+    if (rho < 0.)                                            // onlinelda.cpp:59-66
+        rho = std::pow(tau + (double)*update_count, -kappa);
+    *rho_out = rho;
+    if (update_lambda) {
+        GibbsUpdate u;
+        u.online = true; u.steps = std::max(max_iter_tr, 0); u.eta = eta; u.rho = rho;
+        u.num_documents = num_documents; u.init_theta = init_theta != 0;
+        u.num_samples = num_samples; u.burn_in = burn_in; u.theta_out = theta_out;
+        if (int rc = gibbs_update_device(m, b, u))
+            return rc;
+    }
+    ++*update_count;                                         // onlinelda.cpp:177
+    return TRLDA_OK;
+}
+
+int trlda_model_batch_update_gibbs(trlda_model *m, const trlda_batch *b, double eta, int max_epochs,
+                                   int update_lambda, int num_samples, int burn_in, double *theta_out)
+{
+    if (int rc = gibbs_update_checks(m, b, num_samples, burn_in))
+        return rc;
+    if (b->B == 0 || !update_lambda || max_epochs <= 0)     // batchlda.cpp:44-48
+        return TRLDA_OK;
+    GibbsUpdate u;
+    u.online = false; u.steps = max_epochs; u.eta = eta; u.rho = 1.0; u.num_documents = b->B;
+    u.init_theta = false; u.num_samples = num_samples; u.burn_in = burn_in; u.theta_out = theta_out;
+    return gibbs_update_device(m, b, u);
 }
 
 // ---- sampling documents: LDA::sample, src/lda.cpp:88-115 (sample_kernels.h) ----

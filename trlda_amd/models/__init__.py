@@ -626,15 +626,25 @@ class OnlineLDA(LDA):
     def update_parameters(self, docs, max_iter_tr=10, max_iter_inference=20, kappa=.7,
                           tau=100., rho=-1., adaptive=False, init_gamma=True,
                           update_lambda=True, update_alpha=False, update_eta=False,
-                          min_alpha=1e-6, min_eta=1e-6, verbosity=0):
+                          min_alpha=1e-6, min_eta=1e-6, verbosity=0, inference_method='VI',
+                          num_samples=1, burn_in=2):
         """One online update; returns the learning rate used
         (onlineldainterface.cpp:204-256 -> onlinelda.cpp:53-179).
 
         The lambda path (E-steps, trust-region loop, M-steps) runs on the GPU, and so do the
         sums over gamma, lambda and the statistics that the empirical-Bayes steps for alpha and
         eta and the adaptive learning rate need (onlinelda.cpp:116-175, csrc/eb_kernels.h); the
-        host keeps the K- and scalar-sized Newton steps."""
-        _ffi.check_vi_topics(self._K)
+        host keeps the K- and scalar-sized Newton steps.
+
+        ``inference_method='GIBBS'`` makes every E-step of the loop collapsed Gibbs sampling
+        (``burn_in`` sweeps, then ``num_samples`` counted ones; lda.cpp:224-293) -- the hybrid
+        stochastic inference of Mimno, Hoffman & Blei (2012), K <= 1024.  ``max_iter_inference``
+        does not apply to it; ``update_alpha`` is not supported with it (NotImplementedError)."""
+        method = _inference_method(inference_method)
+        if method == "GIBBS":
+            num_samples, burn_in = _gibbs_args(update_alpha, num_samples, burn_in)
+        else:
+            _ffi.check_vi_topics(self._K)
         batch, owned = self._batch(docs)
         try:
             # (the previous call's empirical-Bayes step, if it is still on its way: the conversion
@@ -654,11 +664,18 @@ class OnlineLDA(LDA):
                                                      int(bool(adaptive and update_lambda))))
             count = C.c_int(self._update_count)
             rho_out = C.c_double(0.)
-            _ffi.check(L.trlda_model_online_update(
-                self._handle, batch.handle, self._num_documents, self._eta, int(max_iter_tr),
-                int(max_iter_inference), float(kappa), float(tau), rho_arg,
-                int(bool(init_gamma)), int(bool(update_lambda)), 0.001,  # lda.h:56: fixed
-                C.byref(count), C.byref(rho_out), None))
+            if method == "GIBBS":
+                _ffi.check(L.trlda_model_online_update_gibbs(
+                    self._handle, batch.handle, self._num_documents, self._eta, int(max_iter_tr),
+                    float(kappa), float(tau), rho_arg, int(bool(init_gamma)),
+                    int(bool(update_lambda)), num_samples, burn_in, C.byref(count),
+                    C.byref(rho_out), None))
+            else:
+                _ffi.check(L.trlda_model_online_update(
+                    self._handle, batch.handle, self._num_documents, self._eta, int(max_iter_tr),
+                    int(max_iter_inference), float(kappa), float(tau), rho_arg,
+                    int(bool(init_gamma)), int(bool(update_lambda)), 0.001,  # lda.h:56: fixed
+                    C.byref(count), C.byref(rho_out), None))
             rho_used = rho_out.value
 
             if update_alpha or update_eta:                           # onlinelda.cpp:116-162
@@ -700,6 +717,18 @@ class OnlineLDA(LDA):
         lam, count = state
         self.lambdas = lam
         self.update_count = count
+
+
+def _gibbs_args(update_alpha, num_samples, burn_in):
+    """The checks of an update with inference_method='GIBBS' that come before anything is drawn or
+    launched: the reference would put the sampled theta where gamma belongs (onlinelda.cpp:116-141),
+    as lower_bound(..., 'gibbs') would."""
+    if update_alpha:
+        raise NotImplementedError("`update_alpha` is not supported with Gibbs sampling.")
+    num_samples, burn_in = int(num_samples), int(burn_in)
+    if num_samples < 0 or burn_in < 0:
+        raise RuntimeError("`num_samples` and `burn_in` should not be negative.")
+    return num_samples, burn_in
 
 
 def _online_alpha_step(alpha, psi_gamma_diff, num_docs, rho, min_alpha):
@@ -769,12 +798,20 @@ class BatchLDA(LDA):
     def update_parameters(self, docs, max_epochs=100, max_iter_inference=100, max_iter_alpha=10,
                           max_iter_eta=20, update_lambda=True, update_alpha=False,
                           update_eta=False, min_alpha=1e-6, min_eta=1e-6,
-                          emp_bayes_threshold=1e-8, verbosity=0):
+                          emp_bayes_threshold=1e-8, verbosity=0, inference_method='VI',
+                          num_samples=1, burn_in=2):
         """batchldainterface.cpp:126-172 -> batchlda.cpp:43-208.  The E-steps and
         lambda = eta + sstats run on the GPU, as do the sums over gamma and lambda behind the
         alpha / eta line searches (batchlda.cpp:66-205); the searches themselves are K- and
-        scalar-sized and run on the host."""
-        _ffi.check_vi_topics(self._K)
+        scalar-sized and run on the host.
+
+        ``inference_method='GIBBS'``: every epoch's E-step is collapsed Gibbs sampling from a
+        fresh theta (see OnlineLDA.update_parameters); ``update_alpha`` is not supported with it."""
+        method = _inference_method(inference_method)
+        if method == "GIBBS":
+            num_samples, burn_in = _gibbs_args(update_alpha, num_samples, burn_in)
+        else:
+            _ffi.check_vi_topics(self._K)
         batch, owned = self._batch(docs)
         try:
             B = len(batch)
@@ -782,16 +819,22 @@ class BatchLDA(LDA):
                 return 1.                                            # batchlda.cpp:44-46
             L = _ffi.lib()
             K, V = self._K, self._V
+            if method == "GIBBS":
+                def lambda_step(epochs, upd):
+                    _ffi.check(L.trlda_model_batch_update_gibbs(
+                        self._handle, batch.handle, self._eta, epochs, upd, num_samples, burn_in,
+                        None))
+            else:
+                def lambda_step(epochs, upd):
+                    _ffi.check(L.trlda_model_batch_update(
+                        self._handle, batch.handle, self._eta, epochs, int(max_iter_inference), upd,
+                        0.001, None))
             if not (update_alpha or update_eta):
-                _ffi.check(L.trlda_model_batch_update(
-                    self._handle, batch.handle, self._eta, int(max_epochs),
-                    int(max_iter_inference), int(bool(update_lambda)), 0.001, None))
+                lambda_step(int(max_epochs), int(bool(update_lambda)))
                 return 1.
             for _epoch in range(int(max_epochs)):                    # batchlda.cpp:48
                 if update_lambda:
-                    _ffi.check(L.trlda_model_batch_update(
-                        self._handle, batch.handle, self._eta, 1, int(max_iter_inference), 1,
-                        0.001, None))
+                    lambda_step(1, 1)
                 if update_alpha:                                     # batchlda.cpp:64-142
                     if not update_lambda:
                         self._resident_estep(batch, max_iter_inference)
