@@ -457,6 +457,34 @@ int trlda_model_predictive(trlda_model *model, const trlda_batch *observed,
                            const trlda_batch *heldout, double *gamma, int max_iter,
                            double threshold, double *loglik_out, double *tokens_out);
 
+/* The marginal log-likelihood of whole documents, log p(w_d | alpha, beta), by importance sampling
+ * of theta (Wallach, Murray, Salakhutdinov & Mimno 2009, section 4.1; csrc/marginal_kernels.h,
+ * DESIGN.md 3.16) with the point estimate beta_kw = lambda_kw / sum_v lambda_kv of
+ * trlda_model_predictive.  Per document d with entries (w_i, c_i) and proposal Dir(a_d):
+ *   theta^(s) ~ Dir(a_d), s < num_samples
+ *   log w_s  = sum_i c_i log(sum_k theta^(s)_k beta_{k, w_i}) + log Dir(theta^(s); alpha) - log Dir(theta^(s); a_d)
+ *   loglik_out[d] = logsumexp_s(log w_s) - log num_samples   (nats; exp of it is unbiased for p(w_d))
+ *   ess_out[d]    = (sum_s w_s)^2 / sum_s w_s^2, the effective sample size, in [1, num_samples]: far
+ *                   below num_samples the estimate rests on a few samples and is poor
+ * proposal TRLDA_PROPOSAL_VI: a_d = gamma_d of the E-step of trlda_model_estep_host on the batch
+ * (gamma: K x B host, in: gamma0, out: gamma; max_iter, threshold as there); TRLDA_PROPOSAL_PRIOR:
+ * a_d = alpha, no E-step runs, the two Dirichlet terms are dropped, gamma is not touched and may be
+ * NULL.  A document without entries gets exactly 0 (and ess = num_samples); entries with c = 0 add
+ * nothing.  loglik_out[B] host; ess_out[B] host or NULL.
+ * The draws are Philox4x32-10 (csrc/philox.h, purposes 19 - 21, counter (s K + k, d, attempt)) under
+ * one key of trlda_rng_draw_key, drawn by every call that passes the argument checks (also for an
+ * empty batch): a document's value is a function of the key, its index d in the batch, its entries
+ * and the model -- not of the batch around it.  TRLDA_ERR_ARG, before anything is drawn, copied or
+ * launched: K above TRLDA_VI_MAX_TOPICS (either proposal), an unknown proposal, num_samples < 1,
+ * num_samples * K >= 2^32, a batch of another V or device.  lambda, alpha and the counters are left
+ * alone; with TRLDA_PROPOSAL_VI trlda_model_get_sstats holds that E-step's statistics afterwards.
+ * Synchronises.  No reference counterpart. */
+#define TRLDA_PROPOSAL_VI    0
+#define TRLDA_PROPOSAL_PRIOR 1
+int trlda_model_document_loglik(trlda_model *model, const trlda_batch *batch, double *gamma,
+                                int proposal, int num_samples, int max_iter, double threshold,
+                                double *loglik_out, double *ess_out);
+
 /* Topic coherence (Mimno et al. 2011; Bouma 2009): the top words of each topic and the document
  * counts of word lists, on the device (csrc/coherence_kernels.h).  The per-pair
  * formulas are the caller's (host) arithmetic on the counts.  No reference counterpart. */

@@ -49,6 +49,7 @@
 #include "coherence_kernels.h"
 #include "polygamma.h"
 #include "dirichlet_kernels.h"
+#include "marginal_kernels.h"
 
 namespace {
 
@@ -630,6 +631,12 @@ struct trlda_model {
         double *theta = nullptr;
         size_t cap_theta = 0;
     } sample;
+    // the documents' marginal likelihood (marginal_kernels.h, trlda_model_document_loglik): row sums of
+    // lambda formed from lambda itself, and their block partials
+    struct {
+        double *partial = nullptr, *rs = nullptr;
+        size_t cap_partial = 0, cap_rs = 0;
+    } marginal;
 };
 
 namespace {
@@ -3933,6 +3940,7 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->gibbs.rs); (void)hipFree(m->gibbs.mpart); (void)hipFree(m->gibbs.nonpos);
         (void)hipFree(m->sample.part); (void)hipFree(m->sample.pre); (void)hipFree(m->sample.indptr);
         (void)hipFree(m->sample.ids); (void)hipFree(m->sample.theta);
+        (void)hipFree(m->marginal.partial); (void)hipFree(m->marginal.rs);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -5062,6 +5070,125 @@ int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_bat
         return rc_x;
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     std::memcpy(tokens_out, hbuf.data() + B, (size_t)B * sizeof(double));
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// marginal_docs_kernel<KPL> for the model's K: theta in registers up to K = 512, else in LDS
+template <int KPL>
+int launch_marginal(trlda_model *m, const trlda_batch *b, int S, uint64_t key, const double *rs,
+                    const double *gamma_dev, double *out)
+{
+    const int K = m->K, B = b->B;
+    const size_t lds = trlda::marginal_lds_doubles(K) * sizeof(double);
+    const int T = trlda::marginal_waves(K) * trlda::kWave;
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::marginal_docs_kernel<KPL>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::marginal_docs_kernel<KPL>, dim3(B), dim3(T), lds, m->stream, K, S, (uint32_t)key,
+                       (uint32_t)(key >> 32), b->indptr, b->ids, b->cnts, m->lambda, rs, m->alpha, gamma_dev, out,
+                       out + B);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// log p(w_d | alpha, beta) of whole documents by importance sampling of theta (Wallach et al. 2009,
+// section 4.1; csrc/marginal_kernels.h): for 'vi' the E-step of trlda_model_estep_host on the
+// batch, whose gamma is the proposal; then the row sums of lambda, formed from lambda itself in an
+// order that depends on K and V only (not taken from what an update or the E-step left behind, so a
+// document's value does not depend on the model's history), and one workgroup per document
+int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *gamma, int proposal,
+                                int num_samples, int max_iter, double threshold, double *loglik_out,
+                                double *ess_out)
+{
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (proposal != TRLDA_PROPOSAL_VI && proposal != TRLDA_PROPOSAL_PRIOR)
+        return fail(TRLDA_ERR_ARG, "proposal should be TRLDA_PROPOSAL_VI or TRLDA_PROPOSAL_PRIOR");
+    const bool vi = proposal == TRLDA_PROPOSAL_VI;
+    if (!b || !loglik_out || (vi && b->B > 0 && !gamma))
+        return fail(TRLDA_ERR_ARG, "NULL batch / gamma / loglik");
+    if (num_samples < 1)
+        return fail(TRLDA_ERR_ARG, "num_samples should be at least 1");
+    if ((uint64_t)num_samples * (uint64_t)m->K >= ((uint64_t)1 << 32))
+        return fail(TRLDA_ERR_ARG, "num_samples * num_topics should be below 2^32 (the draws' counter)");
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    const int K = m->K, V = m->V, B = b->B;
+    if (trlda::marginal_lds_doubles(K) > (size_t)trlda::kMarginalLdsDoubles || trlda::marginal_waves(K) < 1)
+        return fail(TRLDA_ERR_ARG, "num_topics too large for the marginal kernel's LDS layout");
+    const uint64_t key = trlda_host::rng_draw_key();   // (one per valid call, whatever B is)
+    if (B <= 0)
+        return TRLDA_OK;
+    const size_t gbytes = (size_t)K * B * sizeof(double);
+    if (vi) {
+        rc = ensure_update_workspace(m, B);
+        if (rc)
+            return rc;
+        m->gamma0_src = nullptr;                       // the caller's gamma, not one drawn ahead
+        HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+        rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    } else {
+        rc = batch_begin(m, b);
+    }
+    if (rc)
+        return rc;
+    auto &g = m->marginal;
+    int wpb = 0;
+    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks,
+                                wpb);
+    rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
+    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
+    if (!rc) rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)B);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K,
+                       V, wpb, m->lambda, g.partial);
+    HIP_TRY(hipGetLastError());
+    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
+    if (rc)
+        return rc;
+    double *out = m->reduce_out;
+    const double *gamma_dev = vi ? m->gamma : nullptr;
+    if (K > trlda::kMarginalRegMaxK)
+        rc = launch_marginal<0>(m, b, num_samples, key, g.rs, gamma_dev, out);
+    else
+        rc = ks_dispatch((K + trlda::kWave - 1) / trlda::kWave, [&](auto kpl) {
+            return launch_marginal<decltype(kpl)::value>(m, b, num_samples, key, g.rs, gamma_dev, out);
+        });
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    std::vector<double> hbuf(2 * (size_t)B);
+    hipError_t e1 = hipMemcpyAsync(hbuf.data(), out, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = vi ? hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream) : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    if (int rc_x = check_split_exchange(m))
+        return rc_x;
+    std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
+    if (ess_out)
+        std::memcpy(ess_out, hbuf.data() + B, (size_t)B * sizeof(double));
     return TRLDA_OK;
 }
 

@@ -433,6 +433,79 @@ class LDA(Distribution):
             return score, loglik, tokens
         return score
 
+    # -- marginal likelihood of whole documents (Wallach et al. 2009; csrc/marginal_kernels.h) -----
+    def document_log_likelihood(self, docs, num_samples=256, proposal='vi', latents=None,
+                                max_iter=100, threshold=0.001, return_ess=False):
+        """Estimates ``log p(w_d | alpha, beta)`` of each document of ``docs`` (a list,
+        ``DocumentList`` or ``DeviceBatch``) by importance sampling of theta on the GPU (Wallach,
+        Murray, Salakhutdinov & Mimno 2009, section 4.1).  Per document d with entries (w, c):
+
+            theta_s ~ Dir(a_d),  s = 1 .. num_samples
+            log w_s = sum_(w, c) c log(sum_k theta_sk beta_kw) + log Dir(theta_s; alpha) - log Dir(theta_s; a_d)
+            loglik_d = logsumexp_s(log w_s) - log num_samples
+
+        ``exp(loglik_d)`` is an unbiased estimate of ``p(w_d | alpha, beta)``.  Topics enter as the
+        point estimate ``beta_kw = lambda_kw / sum_v lambda_kv`` that ``predictive_log_likelihood``
+        uses, not integrated over ``Dir(lambda_k)``.  ``proposal='vi'``: ``a_d`` is the document's
+        gamma from the E-step of ``update_variables`` on lambda as it is (``latents`` as gamma0, else
+        a random gamma drawn from the seeded stream; ``max_iter``, ``threshold`` as there);
+        ``proposal='prior'``: ``a_d = alpha``, no E-step (``latents`` is then a TypeError) -- far
+        higher variance on all but the shortest documents.
+
+        Returns a float64 array of length B, nats per document (an empty document: exactly 0); with
+        ``return_ess=True`` ``(loglik, ess)``, ``ess_d = (sum_s w_s)^2 / sum_s w_s^2`` being the
+        effective sample size, between 1 and ``num_samples``: when it is a small fraction of
+        ``num_samples`` a few samples carry the estimate, which is then poor (too low, as a rule)
+        -- take more samples or the 'vi' proposal.  Per-word perplexity of the documents is
+        ``exp(-loglik.sum() / number of tokens)``.
+
+        The draws are Philox4x32-10 keyed by two draws of the seeded stream (after gamma0's), so
+        ``trlda.seed`` makes a call reproducible, and a document's value depends on its position in
+        ``docs`` but not on the other documents.  lambda, alpha, eta and the update counters stay
+        as they are."""
+        if not isinstance(proposal, str) or proposal.lower() not in ("vi", "prior"):
+            raise TypeError("`proposal` should be either 'vi' or 'prior'.")
+        vi = proposal.lower() == "vi"
+        if latents is not None and not vi:
+            raise TypeError("`latents` applies to the 'vi' proposal only.")
+        num_samples = operator.index(num_samples)
+        if num_samples < 1:
+            raise RuntimeError("`num_samples` should be positive.")
+        if num_samples * self._K >= 2 ** 32:
+            raise RuntimeError("`num_samples` times the number of topics should be below 2^32.")
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        batch, owned = self._batch(docs)
+        try:
+            self._settle()
+            B = len(batch)
+            L = _ffi.lib()
+            gamma = None
+            if latents is not None:
+                try:
+                    g = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if g.ndim == 1:
+                    g = g.reshape(-1, 1, order="F")
+                if g.ndim != 2 or g.shape != (self._K, B):
+                    raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+                gamma = np.asfortranarray(g)
+            elif vi:
+                gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                L.trlda_sample_gamma_init(self._K, B, gamma)          # lda.cpp:135
+            loglik = np.empty(B, dtype=np.float64)
+            ess = np.empty(B, dtype=np.float64)
+            _ffi.check(L.trlda_model_document_loglik(
+                self._handle, batch.handle, None if gamma is None else gamma.ctypes.data,
+                _ffi.PROPOSAL_VI if vi else _ffi.PROPOSAL_PRIOR, num_samples, int(max_iter),
+                float(threshold), loglik, ess.ctypes.data))
+        finally:
+            if owned:
+                batch.close()
+        if return_ess:
+            return loglik, ess
+        return loglik
+
     # -- topic coherence (Mimno et al. 2011; Bouma 2009; csrc/coherence_kernels.h) -----------------
     def top_words(self, top_n=10):
         """The ``top_n`` word ids of each topic in decreasing order of lambda_kw (the order of
