@@ -485,6 +485,37 @@ int trlda_model_document_loglik(trlda_model *model, const trlda_batch *batch, do
                                 int proposal, int num_samples, int max_iter, double threshold,
                                 double *loglik_out, double *ess_out);
 
+/* The marginal log-likelihood of whole documents, log p(w_d | alpha, beta), by the left-to-right
+ * sequential sampler (Wallach, Murray, Salakhutdinov & Mimno 2009, Algorithm 3; Buntine 2009;
+ * csrc/l2r_kernels.h) with the point estimate beta of trlda_model_predictive.  It
+ * samples the tokens' topics, not theta, and has no proposal.  Per document d with tokens w_0 ..
+ * w_{N-1} (the entries in order, an entry giving c > 0 consecutive tokens), particle r <
+ * num_particles and position n, with n_k the counts of the prefix's current topics:
+ *   resample != 0: for t = 0 .. n-1: take z_t out, z_t ~ beta_{k, w_t} (alpha_k + n_k), put it back
+ *   z_n ~ beta_{k, w_n} (alpha_k + n_k); p_r(n) = (sum_k beta_{k, w_n} (alpha_k + n_k)) / (sum alpha + n)
+ * resample = 0 is the O(N) sequential sampler, otherwise the work is O(N^2) per particle.
+ *   TRLDA_L2R_PARTICLE  loglik_out[d] = logsumexp_r(sum_n log p_r(n)) - log num_particles: exp of it
+ *                       is unbiased for p(w_d) for any number of particles
+ *   TRLDA_L2R_POSITION  loglik_out[d] = sum_n log(mean_r p_r(n)), Algorithm 3 as published: biased
+ *                       for num_particles > 1 (DESIGN.md 3.17 has the figures); with one particle
+ *                       the two are the same bits
+ * A document without tokens gets exactly 0.  loglik_out[B] host; tokens_out[B] host or NULL: N_d.
+ * The draws are Philox4x32-10 (csrc/philox.h, purposes 22 / 23, counter (token, position,
+ * d * num_particles + r)) under one key of trlda_rng_draw_key, drawn by every call that passes its
+ * checks (also for an empty batch): a document's value is a function of the key, its index d, its
+ * entries, num_particles and the model -- not of the batch around it nor of how the batch is cut
+ * into groups against the workspace.  TRLDA_ERR_ARG, before anything is drawn or launched:
+ * num_particles < 1, B * num_particles >= 2^32, an unknown combine, K > 1024 (the Gibbs path's
+ * limit), a batch of another V or device; and, before the key is drawn, a single document with
+ * N_d * num_particles above the workspace (2^23 token-particles; the environment's TRLDA_L2R_BUDGET
+ * replaces the figure, for tests).  TRLDA_ERR_VALUE with the Gibbs path's message when a histogram
+ * does not sum to a positive finite number.  lambda, alpha and the counters are left alone.
+ * Synchronises.  No reference counterpart. */
+#define TRLDA_L2R_PARTICLE 0
+#define TRLDA_L2R_POSITION 1
+int trlda_model_left_to_right(trlda_model *model, const trlda_batch *batch, int num_particles,
+                              int resample, int combine, double *loglik_out, double *tokens_out);
+
 /* Topic coherence (Mimno et al. 2011; Bouma 2009): the top words of each topic and the document
  * counts of word lists, on the device (csrc/coherence_kernels.h).  The per-pair
  * formulas are the caller's (host) arithmetic on the counts.  No reference counterpart. */

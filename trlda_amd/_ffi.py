@@ -18,6 +18,8 @@ OK = 0
 ERR_ARG, ERR_SHAPE, ERR_WORD_ID, ERR_NO_DEVICE, ERR_HIP, ERR_VALUE = -1, -2, -3, -4, -5, -6
 SSTATS_SEGMENTED, SSTATS_ATOMIC = 0, 1
 PROPOSAL_VI, PROPOSAL_PRIOR = 0, 1
+L2R_PARTICLE, L2R_POSITION = 0, 1
+L2R_MAX_TOPICS = 1024                        # kGibbsMaxK
 
 i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(np.float64, flags="F_CONTIGUOUS")
@@ -147,6 +149,7 @@ _SIGNATURES = {
                                 C.POINTER(C.c_double)]),
     "trlda_model_predictive": (C.c_int, [vp, vp, vp, f64p, C.c_int, C.c_double, f64p, f64p]),
     "trlda_model_document_loglik": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, f64p, vp]),
+    "trlda_model_left_to_right": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, vp]),
     "trlda_model_top_words": (C.c_int, [vp, C.c_int, i32p]),
     "trlda_cooc_create": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
     "trlda_cooc_add": (C.c_int, [vp, vp]),

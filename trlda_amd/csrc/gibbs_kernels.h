@@ -128,6 +128,55 @@ __device__ __forceinline__ double wave_allmax(double v)
     return v;
 }
 
+// One histogram draw in the order of the header ("one histogram draw"): lane l holds the weights
+// p_0 .. p_{KPL-1} of topics l*KPL .. (0 for topics >= K), u is the draw's uniform, the same in every
+// lane.  Returns the topic, the same in every lane, or -1 when the histogram's total is not > 0 or
+// not finite; `total` is x_63.  Shared with l2r_kernels.h.
+template <int KPL>
+__device__ __forceinline__ int histogram_draw(const double (&p)[KPL], double u, int lane, double &total)
+{
+    double qv[KPL];
+    int lastnz = -1;
+#pragma unroll
+    for (int q = 0; q < KPL; ++q) {
+        qv[q] = q ? __dadd_rn(qv[q - 1], p[q]) : p[q];
+        if (p[q] > 0.0)
+            lastnz = q;
+    }
+    double x = qv[KPL - 1];
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const double y = __shfl_up(x, off, kWave);
+        if (lane >= off)
+            x = __dadd_rn(x, y);
+    }
+    total = readlane_d(x, kWave - 1);
+    double excl = __shfl_up(x, 1, kWave);
+    if (lane == 0)
+        excl = 0.0;
+    const double r = __dmul_rn(u, total);
+    if (!(total > 0.0) || !(total <= 1.7976931348623157e308))
+        return -1;
+    const unsigned long long hit = __ballot(x > r);
+    int pick = -1, L = 0;
+    if (hit) {
+        L = __ffsll((long long)hit) - 1;
+#pragma unroll
+        for (int q = KPL - 1; q >= 0; --q)
+            if (__dadd_rn(excl, qv[q]) > r)
+                pick = q;
+        if (pick < 0)
+            pick = lastnz;
+        pick = __builtin_amdgcn_readlane(pick, L);
+    }
+    if (pick < 0) {
+        const unsigned long long nz = __ballot(lastnz >= 0);
+        L = 63 - __clzll((long long)nz);
+        pick = __builtin_amdgcn_readlane(lastnz, L);
+    }
+    return L * KPL + pick;
+}
+
 // log of a Gamma(a) draw of topic k of document `doc` (philox.h's recipe, purposes 3 / 4 / 5)
 __device__ inline double gibbs_log_gamma(double a, uint32_t k, uint32_t doc, uint32_t k0, uint32_t k1)
 {
@@ -435,50 +484,15 @@ __global__ __launch_bounds__(kGibbsWaves * kWave) void gibbs_docs_kernel(GibbsAr
                     for (int q = 0; q < KPL; ++q)
                         if (lane * KPL + q == zold)
                             cnt_r[q] = cnt_r[q] - 1.0;
-                    double p[KPL], qv[KPL];
-                    int lastnz = -1;
+                    double p[KPL];
 #pragma unroll
-                    for (int q = 0; q < KPL; ++q) {
+                    for (int q = 0; q < KPL; ++q)
                         p[q] = __dmul_rn(e_r[q], cnt_r[q]);
-                        qv[q] = q ? __dadd_rn(qv[q - 1], p[q]) : p[q];
-                        if (p[q] > 0.0)
-                            lastnz = q;
-                    }
-                    double x = qv[KPL - 1];
-#pragma unroll
-                    for (int off = 1; off < kWave; off <<= 1) {
-                        const double y = __shfl_up(x, off, kWave);
-                        if (lane >= off)
-                            x = __dadd_rn(x, y);
-                    }
-                    const double total = readlane_d(x, kWave - 1);
-                    double excl = __shfl_up(x, 1, kWave);
-                    if (lane == 0)
-                        excl = 0.0;
-                    const double r = __dmul_rn(readlane_d(uc, ql), total);
-                    int znew;
-                    if (!(total > 0.0) || !(total <= 1.7976931348623157e308)) {
+                    double total;
+                    int znew = histogram_draw<KPL>(p, readlane_d(uc, ql), lane, total);
+                    if (znew < 0) {
                         sweep_bad = true;
                         znew = zold;
-                    } else {
-                        const unsigned long long hit = __ballot(x > r);
-                        int pick = -1, L;
-                        if (hit) {
-                            L = __ffsll((long long)hit) - 1;
-#pragma unroll
-                            for (int q = KPL - 1; q >= 0; --q)
-                                if (__dadd_rn(excl, qv[q]) > r)
-                                    pick = q;
-                            if (pick < 0)
-                                pick = lastnz;
-                            pick = __builtin_amdgcn_readlane(pick, L);
-                        }
-                        if (pick < 0) {
-                            const unsigned long long nz = __ballot(lastnz >= 0);
-                            L = 63 - __clzll((long long)nz);
-                            pick = __builtin_amdgcn_readlane(lastnz, L);
-                        }
-                        znew = L * KPL + pick;
                     }
 #pragma unroll
                     for (int q = 0; q < KPL; ++q)

@@ -1,7 +1,8 @@
 // philox.h -- the library's counter-based random stream, shared by host code and kernels: Philox4x32-10
 // (Salmon et al., SC'11; Random123's constants), the two uniform mappings and the Marsaglia-Tsang
 // log-gamma recipe.  Every function is __host__ __device__, so the host (trlda_sample_lengths) and
-// the kernels (gibbs_kernels.h, sample_kernels.h, dirichlet_kernels.h, marginal_kernels.h) run the same code.
+// the kernels (gibbs_kernels.h, sample_kernels.h, dirichlet_kernels.h, marginal_kernels.h, l2r_kernels.h)
+// run the same code.
 //
 // A draw is one Philox block of the counter (c0, c1, c2, c3) under the call's 64-bit key (k0, k1),
 // c3 being the draw's purpose.  The purposes in use, and what the other three words hold:
@@ -19,6 +20,8 @@
 //   16 / 17 / 18 sample_dirichlet: normal / accept / boost  (row i, column j, attempt; boost 0)
 //   19 / 20 / 21 document likelihood: theta gamma:          (sample s * K + topic k, document d,
 //            normal / accept / boost                         attempt; boost 0)
+//   22       left-to-right: a prefix token's redraw         (token t of d, position n, d * R + particle r)
+//   23       left-to-right: a new token's draw              (position n, n, d * R + particle r)
 //
 // The output words (x0, x1, x2, x3) become uniforms through x = x1 * 2^32 + x0 (and x3 * 2^32 + x2):
 //     u      = (x >> 11) * 2^-53           in [0, 1)    histogram draws

@@ -50,6 +50,7 @@
 #include "polygamma.h"
 #include "dirichlet_kernels.h"
 #include "marginal_kernels.h"
+#include "l2r_kernels.h"
 
 namespace {
 
@@ -637,6 +638,19 @@ struct trlda_model {
         double *partial = nullptr, *rs = nullptr;
         size_t cap_partial = 0, cap_rs = 0;
     } marginal;
+    // the left-to-right sampler (l2r_kernels.h, trlda_model_left_to_right): row sums of lambda formed
+    // from lambda itself, sum alpha, the documents' token counts, order and offsets, and the groups'
+    // workspace (topics and the p table) under kL2rBudget
+    struct {
+        double *partial = nullptr, *rs = nullptr, *asum = nullptr, *p = nullptr, *out = nullptr;
+        size_t cap_partial = 0, cap_rs = 0, cap_p = 0, cap_out = 0;
+        int64_t *tokens = nullptr, *off = nullptr;
+        int32_t *order = nullptr;
+        size_t cap_tokens = 0, cap_off = 0, cap_order = 0;
+        uint16_t *z = nullptr;
+        size_t cap_z = 0;
+        int *flag = nullptr;
+    } l2r;
 };
 
 namespace {
@@ -3941,6 +3955,10 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->sample.part); (void)hipFree(m->sample.pre); (void)hipFree(m->sample.indptr);
         (void)hipFree(m->sample.ids); (void)hipFree(m->sample.theta);
         (void)hipFree(m->marginal.partial); (void)hipFree(m->marginal.rs);
+        (void)hipFree(m->l2r.partial); (void)hipFree(m->l2r.rs); (void)hipFree(m->l2r.asum);
+        (void)hipFree(m->l2r.p); (void)hipFree(m->l2r.out); (void)hipFree(m->l2r.tokens);
+        (void)hipFree(m->l2r.off); (void)hipFree(m->l2r.order); (void)hipFree(m->l2r.z);
+        (void)hipFree(m->l2r.flag);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -5189,6 +5207,173 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     if (ess_out)
         std::memcpy(ess_out, hbuf.data() + B, (size_t)B * sizeof(double));
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <int KPL>
+int launch_l2r(trlda_model *m, const trlda::L2rArgs &a)
+{
+    const long long blocks = (a.items + trlda::kL2rWaves - 1) / trlda::kL2rWaves;
+    hipLaunchKernelGGL(trlda::l2r_docs_kernel<KPL>, dim3((unsigned)blocks), dim3(trlda::kL2rWaves * trlda::kWave), 0,
+                       m->stream, a);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// token-particles a document group may hold: kL2rBudget, or what TRLDA_L2R_BUDGET says (read per
+// call: the tests force small groups with it)
+long long l2r_budget()
+{
+    if (const char *e = std::getenv("TRLDA_L2R_BUDGET")) {
+        const long long v = std::atoll(e);
+        if (v > 0)
+            return v;
+    }
+    return trlda::kL2rBudget;
+}
+
+}  // namespace
+
+extern "C" {
+
+// log p(w_d | alpha, beta) of whole documents by the left-to-right sequential sampler (Wallach et al.
+// 2009, Algorithm 3; csrc/l2r_kernels.h): the row sums of lambda formed from lambda itself as in
+// trlda_model_document_loglik, the documents' token counts and longest-first order as on the Gibbs
+// path, then per group of documents under the workspace budget one wave per (document, particle)
+// and one wave per document for the combination
+int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_particles, int resample,
+                              int combine, double *loglik_out, double *tokens_out)
+{
+    using namespace trlda;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b || !loglik_out)
+        return fail(TRLDA_ERR_ARG, "NULL batch / loglik");
+    if (combine != TRLDA_L2R_PARTICLE && combine != TRLDA_L2R_POSITION)
+        return fail(TRLDA_ERR_ARG, "combine should be TRLDA_L2R_PARTICLE or TRLDA_L2R_POSITION");
+    if (num_particles < 1)
+        return fail(TRLDA_ERR_ARG, "num_particles should be at least 1");
+    if ((uint64_t)std::max(b->B, 0) * (uint64_t)num_particles >= ((uint64_t)1 << 32))
+        return fail(TRLDA_ERR_ARG, "documents * num_particles should be below 2^32 (the draws' counter)");
+    if (m->K > kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "the left-to-right sampler supports at most 1024 topics (the Gibbs path's limit)");
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    const int K = m->K, V = m->V, B = b->B, R = num_particles;
+    if (B <= 0) {
+        (void)trlda_host::rng_draw_key();              // (one per valid call, whatever B is)
+        return TRLDA_OK;
+    }
+    auto &g = m->l2r;
+    rc = batch_begin(m, b);
+    if (!rc) rc = grow(&g.tokens, &g.cap_tokens, (size_t)B);
+    if (!rc) rc = grow(&g.off, &g.cap_off, (size_t)B);
+    if (!rc) rc = grow(&g.order, &g.cap_order, (size_t)B);
+    if (!rc) rc = grow(&g.out, &g.cap_out, (size_t)B);
+    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
+    if (!rc && !g.asum) rc = dev_alloc(&g.asum, 1);
+    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    if (rc)
+        return rc;
+    // the plan: tokens per document, the longest first, groups of documents under the budget
+    std::vector<int64_t> tok((size_t)B), off((size_t)B);
+    std::vector<int32_t> order((size_t)B);
+    hipLaunchKernelGGL(gibbs_tokens_kernel<256>, dim3((B + 255) / 256), dim3(256), 0, m->stream, B, b->indptr,
+                       b->cnts, g.tokens);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tok.data(), g.tokens, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(),
+                     [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
+    const long long budget = l2r_budget();
+    if (tok[(size_t)order[0]] > budget / R) {
+        (void)batch_end(m, b);
+        return fail(TRLDA_ERR_ARG, "left_to_right: a document's tokens * num_particles exceed the workspace of " +
+                                   std::to_string(budget) + " token-particles (kL2rBudget, TRLDA_L2R_BUDGET)");
+    }
+    std::vector<int> starts;                           // first slot of each group, then B
+    int64_t most = 0, fill = 0;
+    for (int s = 0; s < B; ++s) {
+        const int64_t n = tok[(size_t)order[(size_t)s]];
+        if (s == 0 || (fill + n) * R > budget) {
+            starts.push_back(s);
+            fill = 0;
+        }
+        off[(size_t)order[(size_t)s]] = fill;
+        fill += n;
+        most = std::max(most, fill);
+    }
+    starts.push_back(B);
+    const uint64_t key = trlda_host::rng_draw_key();   // (one per call that passes its checks)
+    const size_t cells = (size_t)std::max<int64_t>(most, 1) * (size_t)R;
+    rc = grow(&g.p, &g.cap_p, cells);
+    if (!rc && resample) rc = grow(&g.z, &g.cap_z, cells);
+    int wpb = 0;
+    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : kRowsumBlocks, wpb);
+    if (!rc) rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(g.off, off.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(g.order, order.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
+    hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K, V, wpb,
+                       m->lambda, g.partial);
+    HIP_TRY(hipGetLastError());
+    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(l2r_alpha_sum_kernel, dim3(1), dim3(kWave), 0, m->stream, K, m->alpha, g.asum);
+    HIP_TRY(hipGetLastError());
+    L2rArgs a;
+    a.K = K; a.R = R; a.resample = resample ? 1 : 0;
+    a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
+    a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
+    a.off = g.off; a.tokens = g.tokens;
+    a.lambda = m->lambda; a.rowsum = g.rs; a.alpha = m->alpha; a.asum = g.asum;
+    a.z = g.z; a.p = g.p; a.flag = g.flag;
+    const int kpl = (K + kWave - 1) / kWave;
+    for (size_t gi = 0; gi + 1 < starts.size(); ++gi) {
+        const int s0 = starts[gi], nd = starts[gi + 1] - s0;
+        a.docs = g.order + s0;
+        a.items = (long long)nd * R;
+        rc = kpl <= 1 ? launch_l2r<1>(m, a) : kpl <= 2 ? launch_l2r<2>(m, a) : kpl <= 4 ? launch_l2r<4>(m, a)
+           : kpl <= 8 ? launch_l2r<8>(m, a) : launch_l2r<16>(m, a);
+        if (rc)
+            return rc;
+        hipLaunchKernelGGL(l2r_finish_kernel, dim3(nd), dim3(kWave), 0, m->stream, R,
+                           combine == TRLDA_L2R_POSITION ? 1 : 0, a.docs, g.off, g.tokens, g.p, g.out);
+        HIP_TRY(hipGetLastError());
+    }
+    (void)batch_end(m, b);
+    int flag = 0;
+    std::vector<double> hbuf((size_t)B);
+    hipError_t e1 = hipMemcpyAsync(hbuf.data(), g.out, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);   // (the host vectors go out of scope)
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    if (int rc_x = check_split_exchange(m))
+        return rc_x;
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+    std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
+    if (tokens_out)
+        for (int d = 0; d < B; ++d)
+            tokens_out[d] = (double)tok[(size_t)d];
     return TRLDA_OK;
 }
 
