@@ -516,6 +516,35 @@ int trlda_model_document_loglik(trlda_model *model, const trlda_batch *batch, do
 int trlda_model_left_to_right(trlda_model *model, const trlda_batch *batch, int num_particles,
                               int resample, int combine, double *loglik_out, double *tokens_out);
 
+/* The per-word topic posteriors of the variational path: the phi that LDA::updateVariablesVI forms
+ * inside its fixed point and drops (src/lda.cpp:189-197; csrc/wordtopics_kernels.h).
+ * An E-step on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
+ * trlda_model_estep_host), then per entry p = (d, w_p, c_p) of the batch's CSR, in the batch's own
+ * entry order,
+ *   s_pk = exp(psi(gamma_dk) - psi(rs_k)) exp(psi(lambda_{k, w_p})),  rs_k = sum_v lambda_kv
+ *   phi_pk = s_pk / sum_j s_pj
+ * topics_out[p * top_n + r] (int32) and probs_out[p * top_n + r] (fp64), r < top_n: the top_n topics
+ * of row p in decreasing phi, equal values by smaller topic id first (the rule of
+ * trlda_model_top_words); host arrays of trlda_batch_nnz(batch) * top_n elements.  With top_n = K a
+ * row of probs_out is the whole posterior in ranked order.  An entry with c_p = 0 gets a row like
+ * any other (the row depends on w_p and gamma_d only); a document without entries has no rows; an
+ * empty batch writes nothing.  The order of the additions in a row's sum depends on K alone: a
+ * document's rows are bitwise the same alone and inside any batch for the same gamma column.
+ * TRLDA_ERR_ARG, before anything is waited for, copied or launched: K above TRLDA_VI_MAX_TOPICS,
+ * top_n outside [1, min(K, 32)], a batch of another V or device.  lambda, alpha and the counters are
+ * left alone; pending deferred statistics and stream lanes are settled first; afterwards
+ * trlda_model_get_sstats holds that E-step's statistics, as after trlda_model_document_loglik with
+ * TRLDA_PROPOSAL_VI.  Synchronises.  No reference counterpart. */
+int trlda_model_word_topics(trlda_model *model, const trlda_batch *batch, double *gamma, int top_n,
+                            int max_iter, double threshold, int32_t *topics_out, double *probs_out);
+
+/* The same rows from a gamma the caller keeps on the device (K x B, read only: no E-step runs, the
+ * model's statistics keep what they held), into device arrays of trlda_batch_nnz(batch) * top_n
+ * elements.  Enqueued on the model's stream; does not synchronise.  The same checks; on the same
+ * gamma bitwise the rows of trlda_model_word_topics. */
+int trlda_model_word_topics_dev(trlda_model *model, const trlda_batch *batch, const double *gamma_dev,
+                                int top_n, int32_t *topics_dev, double *probs_dev);
+
 /* Topic coherence (Mimno et al. 2011; Bouma 2009): the top words of each topic and the document
  * counts of word lists, on the device (csrc/coherence_kernels.h).  The per-pair
  * formulas are the caller's (host) arithmetic on the counts.  No reference counterpart. */

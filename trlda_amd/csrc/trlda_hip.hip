@@ -51,6 +51,7 @@
 #include "dirichlet_kernels.h"
 #include "marginal_kernels.h"
 #include "l2r_kernels.h"
+#include "wordtopics_kernels.h"
 
 namespace {
 
@@ -651,6 +652,14 @@ struct trlda_model {
         size_t cap_z = 0;
         int *flag = nullptr;
     } l2r;
+    // the per-word topic posteriors (wordtopics_kernels.h, trlda_model_word_topics): row sums of lambda
+    // formed from lambda itself and their block partials; the host form's output staging
+    struct {
+        double *partial = nullptr, *rs = nullptr, *probs = nullptr;
+        size_t cap_partial = 0, cap_rs = 0, cap_probs = 0;
+        int32_t *topics = nullptr;
+        size_t cap_topics = 0;
+    } wordtopics;
 };
 
 namespace {
@@ -3959,6 +3968,8 @@ int trlda_model_destroy(trlda_model *m)
         (void)hipFree(m->l2r.p); (void)hipFree(m->l2r.out); (void)hipFree(m->l2r.tokens);
         (void)hipFree(m->l2r.off); (void)hipFree(m->l2r.order); (void)hipFree(m->l2r.z);
         (void)hipFree(m->l2r.flag);
+        (void)hipFree(m->wordtopics.partial); (void)hipFree(m->wordtopics.rs);
+        (void)hipFree(m->wordtopics.topics); (void)hipFree(m->wordtopics.probs);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -5375,6 +5386,156 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
         for (int d = 0; d < B; ++d)
             tokens_out[d] = (double)tok[(size_t)d];
     return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- per-word topic posteriors (csrc/wordtopics_kernels.h) ----
+
+namespace {
+
+template <int KPL>
+int launch_word_topics(trlda_model *m, const trlda_batch *b, int top_n, const double *rs, const double *gamma_dev,
+                       int32_t *topics_dev, double *probs_dev)
+{
+    const size_t lds = (size_t)m->K * sizeof(double);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::word_topics_kernel<KPL>), lds);
+    if (rc)
+        return rc;
+    // (a document of more than 65 535 chunks: its workgroups take several chunks each)
+    const int chunks = std::min((b->max_n + trlda::kWordTopicsChunk - 1) / trlda::kWordTopicsChunk, 65535);
+    hipLaunchKernelGGL(trlda::word_topics_kernel<KPL>, dim3(b->B, chunks), dim3(trlda::kWordTopicsThreads), lds,
+                       m->stream, m->K, top_n, b->indptr, b->ids, m->lambda, rs, gamma_dev, topics_dev, probs_dev);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// what both forms check before anything is waited for, copied or launched
+int word_topics_checks(const trlda_model *m, const trlda_batch *b, int top_n)
+{
+    if (!b)
+        return fail(TRLDA_ERR_ARG, "NULL batch");
+    if (top_n < 1 || top_n > trlda::kWordTopicsMaxTop || top_n > m->K)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_topics, 32)]");
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    return TRLDA_OK;
+}
+
+// The scoring stage on the model's stream: the row sums of lambda formed from lambda itself as in
+// trlda_model_document_loglik (an order that depends on K and V only -- the device-pointer form has
+// no E-step whose preamble could have left them, and both forms must give the same bits), then one
+// workgroup per (document, chunk of entries).  The batch has entries and has been begun.
+int word_topics_device(trlda_model *m, const trlda_batch *b, int top_n, const double *gamma_dev,
+                       int32_t *topics_dev, double *probs_dev)
+{
+    const int K = m->K, V = m->V;
+    auto &g = m->wordtopics;
+    int wpb = 0;
+    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks,
+                                wpb);
+    int rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
+    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K,
+                       V, wpb, m->lambda, g.partial);
+    HIP_TRY(hipGetLastError());
+    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
+    if (rc)
+        return rc;
+    if (K > trlda::kWordTopicsRegMaxK)
+        return launch_word_topics<0>(m, b, top_n, g.rs, gamma_dev, topics_dev, probs_dev);
+    return ks_dispatch((K + trlda::kWave - 1) / trlda::kWave, [&](auto kpl) {
+        return launch_word_topics<decltype(kpl)::value>(m, b, top_n, g.rs, gamma_dev, topics_dev, probs_dev);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+// The per-word topic posteriors from a gamma that is already on the device (no E-step): enqueued on
+// the model's stream, not synchronised
+int trlda_model_word_topics_dev(trlda_model *m, const trlda_batch *b, const double *gamma_dev, int top_n,
+                                int32_t *topics_dev, double *probs_dev)
+{
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (m)
+        if (int rc_arg = word_topics_checks(m, b, top_n))
+            return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (b->nnz <= 0)
+        return TRLDA_OK;
+    if (!gamma_dev || !topics_dev || !probs_dev)
+        return fail(TRLDA_ERR_ARG, "NULL gamma / topics / probs");
+    rc = batch_begin(m, b);
+    if (!rc) rc = word_topics_device(m, b, top_n, gamma_dev, topics_dev, probs_dev);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    return TRLDA_OK;
+}
+
+// The E-step of trlda_model_estep_host on the batch, then the scoring stage with its gamma
+int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma, int top_n, int max_iter,
+                            double threshold, int32_t *topics_out, double *probs_out)
+{
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (m)
+        if (int rc_arg = word_topics_checks(m, b, top_n))
+            return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if ((b->B > 0 && !gamma) || (b->nnz > 0 && (!topics_out || !probs_out)))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / topics / probs");
+    const int K = m->K, B = b->B;
+    if (B <= 0)
+        return TRLDA_OK;
+    rc = ensure_update_workspace(m, B);
+    if (rc)
+        return rc;
+    auto &g = m->wordtopics;
+    const size_t cells = (size_t)b->nnz * (size_t)top_n;
+    if (cells) {
+        rc = grow(&g.topics, &g.cap_topics, cells);
+        if (!rc) rc = grow(&g.probs, &g.cap_probs, cells);
+        if (rc)
+            return rc;
+    }
+    const size_t gbytes = (size_t)K * B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc && cells)
+        rc = word_topics_device(m, b, top_n, m->gamma, g.topics, g.probs);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = cells ? hipMemcpyAsync(topics_out, g.topics, cells * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                           m->stream)
+                          : hipSuccess;
+    hipError_t e3 = cells ? hipMemcpyAsync(probs_out, g.probs, cells * sizeof(double), hipMemcpyDeviceToHost,
+                                           m->stream)
+                          : hipSuccess;
+    hipError_t e4 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
 }
 
 // ---- topic coherence: top words and document counts (csrc/coherence_kernels.h) ----

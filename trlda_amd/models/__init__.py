@@ -570,6 +570,63 @@ class LDA(Distribution):
             return loglik, tokens
         return loglik
 
+    # -- per-word topic posteriors (csrc/wordtopics_kernels.h) --------------------------------------
+    def word_topics(self, docs, top_n=1, latents=None, max_iter=100, threshold=0.001,
+                    return_gamma=False):
+        """The topics each word of each document belongs to: the variational posterior phi that
+        the E-step forms inside its fixed point.  VI on ``docs`` (a list, ``DocumentList`` or
+        ``DeviceBatch``) with lambda fixed (from ``latents`` as gamma0, else a random gamma drawn
+        from the seeded stream as ``update_variables`` draws it), then per ``(id, count)`` pair p of
+        document d, on the GPU,
+
+            s_pk = exp(psi(gamma_dk) - psi(sum_v lambda_kv)) exp(psi(lambda_{k, id_p})),
+            phi_pk = s_pk / sum_j s_pj.
+
+        Returns ``(indptr, topics, probs)``: ``indptr`` int64 of length B + 1, ``topics`` int32 and
+        ``probs`` float64 of shape (number of pairs, top_n).  Rows ``indptr[d] .. indptr[d + 1]``
+        line up with document d's pairs as given (a pair with count 0 has a row like any other); a
+        row holds the ``top_n`` topics in decreasing phi, equal values by smaller topic id first,
+        and their phi.  ``1 <= top_n <= min(num_topics, 32)``, else RuntimeError; with
+        ``top_n = num_topics`` a row of ``probs`` is the whole posterior in ranked order.  With
+        ``return_gamma=True`` gamma (K x B) is appended.  A document's rows do not depend on the
+        other documents of ``docs``.  lambda, alpha, eta and the update counters stay as they are
+        (DESIGN.md 3.18)."""
+        top_n = operator.index(top_n)
+        if not 1 <= top_n <= min(self._K, 32):
+            raise RuntimeError("`top_n` should lie between 1 and min(num_topics, 32).")
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        batch, owned = self._batch(docs)
+        try:
+            self._settle()
+            B = len(batch)
+            L = _ffi.lib()
+            if latents is not None:
+                try:
+                    g = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if g.ndim == 1:
+                    g = g.reshape(-1, 1, order="F")
+                if g.ndim != 2 or g.shape != (self._K, B):
+                    raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+                gamma = np.asfortranarray(g)
+            else:
+                gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                L.trlda_sample_gamma_init(self._K, B, gamma)          # lda.cpp:135
+            indptr = np.asarray(batch.csr.indptr, dtype=np.int64).copy()
+            nnz = int(indptr[-1])
+            topics = np.empty((nnz, top_n), dtype=np.int32)
+            probs = np.empty((nnz, top_n), dtype=np.float64)
+            _ffi.check(L.trlda_model_word_topics(self._handle, batch.handle, gamma.ctypes.data, top_n,
+                                                 int(max_iter), float(threshold), topics.ctypes.data,
+                                                 probs.ctypes.data))
+        finally:
+            if owned:
+                batch.close()
+        if return_gamma:
+            return indptr, topics, probs, gamma
+        return indptr, topics, probs
+
     # -- topic coherence (Mimno et al. 2011; Bouma 2009; csrc/coherence_kernels.h) -----------------
     def top_words(self, top_n=10):
         """The ``top_n`` word ids of each topic in decreasing order of lambda_kw (the order of
