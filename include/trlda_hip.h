@@ -570,6 +570,62 @@ int trlda_cooc_add(trlda_cooc *cooc, const trlda_batch *batch);
 int trlda_cooc_read(trlda_cooc *cooc, int64_t *doc_freq, int64_t *co_doc_freq, int64_t *num_docs);
 int trlda_cooc_destroy(trlda_cooc *cooc);
 
+/* Nearest documents in topic space (csrc/docindex_kernels.h): a table of the
+ * documents' topic proportions theta = gamma / sum(gamma) on the model's device, and the top_n
+ * nearest indexed documents of each document of a batch.  measure TRLDA_MEASURE_HELLINGER stores
+ * r_k = sqrt(theta_k), TRLDA_MEASURE_COSINE r_k = theta_k / sqrt(sum_j theta_j^2); the similarity is
+ * s(q, d) = sum_k r_qk r_dk (the Bhattacharyya coefficient / the cosine).  A row depends on its gamma
+ * column and K alone, s on the two rows and K alone; the ranking is the total order (s descending,
+ * id ascending), ids being the positions in order of addition from 0.  The index runs on the
+ * model's stream and must be destroyed before the model; it stores theta, not lambda: rows added
+ * before lambda changed are stale, which is not detected.  No reference counterpart. */
+#define TRLDA_MEASURE_HELLINGER 0
+#define TRLDA_MEASURE_COSINE    1
+typedef struct trlda_docindex trlda_docindex;
+/* An empty index for `model`'s K and device (an unknown measure: TRLDA_ERR_ARG).  No reference
+ * counterpart. */
+int trlda_docindex_create(trlda_model *model, int measure, trlda_docindex **out);
+/* Room for `rows` documents in all.  Without it the table doubles from max(1024, first batch) with a
+ * device-to-device copy on the model's stream each time.  No reference counterpart. */
+int trlda_docindex_reserve(trlda_docindex *index, int64_t rows);
+/* An E-step on the batch as trlda_model_estep_host runs it (gamma: K x B host, in: gamma0, out:
+ * gamma; afterwards trlda_model_get_sstats holds that E-step's statistics, as after
+ * trlda_model_word_topics), then the B rows are appended.  TRLDA_ERR_ARG, before anything is waited
+ * for, copied or launched: K above TRLDA_VI_MAX_TOPICS, a batch of another V or device.  lambda,
+ * alpha and the counters are left alone; pending deferred statistics and stream lanes are settled
+ * first.  Synchronises.  No reference counterpart. */
+int trlda_docindex_add(trlda_docindex *index, const trlda_batch *batch, double *gamma, int max_iter,
+                       double threshold);
+/* Appends the rows of B gamma columns (K x B host; any K >= 1; every value finite and positive,
+ * else TRLDA_ERR_VALUE and nothing is added).  No E-step, nothing drawn.  Synchronises.  No reference
+ * counterpart. */
+int trlda_docindex_add_gamma(trlda_docindex *index, const double *gamma_host, int B);
+/* The same from a gamma on the device (not validated).  Enqueued on the model's stream; does not
+ * synchronise.  On the same gamma bitwise the rows of trlda_docindex_add_gamma.  No reference
+ * counterpart. */
+int trlda_docindex_add_gamma_dev(trlda_docindex *index, const double *gamma_dev, int B);
+/* Documents indexed so far: the next id.  No reference counterpart. */
+int64_t trlda_docindex_size(const trlda_docindex *index);
+/* An E-step on the batch as in trlda_docindex_add, then per document the top_n nearest indexed
+ * documents: ids_out (int64) and sim_out (fp64, the similarity s), host, B x top_n row-major, best
+ * first.  TRLDA_ERR_ARG, before anything is waited for, copied or launched: an empty index, top_n
+ * outside [1, min(size, 100)], K above TRLDA_VI_MAX_TOPICS, a batch of another V or device.  The
+ * index is left as it was.  Synchronises.  No reference counterpart. */
+int trlda_docindex_query(trlda_docindex *index, const trlda_batch *batch, double *gamma, int max_iter,
+                         double threshold, int top_n, int64_t *ids_out, double *sim_out);
+/* The same search for B gamma columns given on the host (K x B; any K >= 1; finite and positive,
+ * else TRLDA_ERR_VALUE): no E-step, nothing drawn.  On the same gamma bitwise the results of
+ * trlda_docindex_query.  Synchronises.  No reference counterpart. */
+int trlda_docindex_query_gamma(trlda_docindex *index, const double *gamma_host, int B, int top_n,
+                               int64_t *ids_out, double *sim_out);
+/* Rows first .. first + count - 1 as stored (count x K host, row-major, without the zero pad);
+ * rows outside [0, size): TRLDA_ERR_ARG.  Synchronises.  No reference counterpart. */
+int trlda_docindex_read_rows(trlda_docindex *index, int64_t first, int64_t count, double *rows_out);
+/* A/B switch for tests and measurements: index rows per workgroup of the search (a positive multiple
+ * of 16; 0: the default, 2048).  The results do not depend on it.  No reference counterpart. */
+int trlda_docindex_set_slab_rows(trlda_docindex *index, int rows);
+int trlda_docindex_destroy(trlda_docindex *index);
+
 /* LDA::updateVariablesGibbs (src/lda.cpp:224-293), reached from python/src/ldainterface.cpp:311-390
  * with inference_method='GIBBS': collapsed Gibbs sampling of the batch's topic assignments on the
  * device (csrc/gibbs_kernels.h), one wave64 per document, K <= 1024 (more: TRLDA_ERR_ARG).

@@ -22,3 +22,4 @@ def seed(value):
 
 from . import models  # noqa: E402,F401
 from . import utils  # noqa: E402,F401
+from .index import DocumentIndex  # noqa: E402,F401

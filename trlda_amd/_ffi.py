@@ -157,6 +157,17 @@ _SIGNATURES = {
     "trlda_cooc_add": (C.c_int, [vp, vp]),
     "trlda_cooc_read": (C.c_int, [vp, i64p, i64p, C.POINTER(C.c_int64)]),
     "trlda_cooc_destroy": (C.c_int, [vp]),
+    "trlda_docindex_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "trlda_docindex_reserve": (C.c_int, [vp, C.c_int64]),
+    "trlda_docindex_add": (C.c_int, [vp, vp, vp, C.c_int, C.c_double]),
+    "trlda_docindex_add_gamma": (C.c_int, [vp, vp, C.c_int]),
+    "trlda_docindex_add_gamma_dev": (C.c_int, [vp, vp, C.c_int]),
+    "trlda_docindex_size": (C.c_int64, [vp]),
+    "trlda_docindex_query": (C.c_int, [vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]),
+    "trlda_docindex_query_gamma": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "trlda_docindex_read_rows": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
+    "trlda_docindex_set_slab_rows": (C.c_int, [vp, C.c_int]),
+    "trlda_docindex_destroy": (C.c_int, [vp]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),
     "trlda_model_online_update_multi": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                                   C.c_int, C.c_int, C.c_double, C.c_double,

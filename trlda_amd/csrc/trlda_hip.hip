@@ -52,6 +52,7 @@
 #include "marginal_kernels.h"
 #include "l2r_kernels.h"
 #include "wordtopics_kernels.h"
+#include "docindex_kernels.h"
 
 namespace {
 
@@ -5775,6 +5776,376 @@ int trlda_cooc_destroy(trlda_cooc *c)
     if (c->model && use_device(c->model->device) == TRLDA_OK && c->model->stream)
         (void)hipStreamSynchronize(c->model->stream);    // (its kernels may still read the buffers)
     cooc_free(c);
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- nearest documents in topic space (csrc/docindex_kernels.h) ----
+
+// The index: the table of rows (row-major, Kp doubles each) on the model's device, and the grow-only
+// workspaces of a query -- the queries' rows, a staged gamma, the slabs' lists, the results
+struct trlda_docindex {
+    trlda_model *model = nullptr;
+    int measure = 0;
+    int K = 0, Kp = 0;
+    double *rows = nullptr;
+    size_t cap = 0;                      // rows the table holds
+    int64_t n = 0;                       // rows in use: the next id
+    int slab_rows = 0;                   // 0: kDocIndexSlabRows
+    double *qrows = nullptr, *gstage = nullptr, *cand_s = nullptr, *out_s = nullptr;
+    long long *cand_i = nullptr, *out_i = nullptr;
+    size_t cap_qrows = 0, cap_gstage = 0, cap_cand_s = 0, cap_out_s = 0, cap_cand_i = 0, cap_out_i = 0;
+};
+
+namespace {
+
+void docindex_free(trlda_docindex *x)
+{
+    if (!x)
+        return;
+    (void)hipFree(x->rows); (void)hipFree(x->qrows); (void)hipFree(x->gstage);
+    (void)hipFree(x->cand_s); (void)hipFree(x->out_s); (void)hipFree(x->cand_i); (void)hipFree(x->out_i);
+    delete x;
+}
+
+// room for `need` rows: doubling from max(1024, first request), the rows in use copied on the
+// model's stream
+int docindex_room(trlda_docindex *x, int64_t need, int64_t first)
+{
+    if (need <= (int64_t)x->cap && x->rows)
+        return TRLDA_OK;
+    size_t cap = x->cap ? x->cap : (size_t)std::max<int64_t>(1024, first);
+    while ((int64_t)cap < need)
+        cap *= 2;
+    double *grown = nullptr;
+    int rc = dev_alloc(&grown, cap * (size_t)x->Kp);
+    if (rc)
+        return rc;
+    if (x->n > 0) {
+        hipError_t e = hipMemcpyAsync(grown, x->rows, (size_t)x->n * x->Kp * sizeof(double),
+                                      hipMemcpyDeviceToDevice, x->model->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(grown);
+            return fail(TRLDA_ERR_HIP, std::string("copying the index rows: ") + hipGetErrorString(e));
+        }
+    }
+    (void)hipFree(x->rows);              // (waits for the copy)
+    x->rows = grown;
+    x->cap = cap;
+    return TRLDA_OK;
+}
+
+int docindex_launch_rows(trlda_docindex *x, const double *gamma_dev, int B, double *rows_dev)
+{
+    constexpr int per_wg = trlda::kDocIndexThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::docindex_rows_kernel, dim3((B + per_wg - 1) / per_wg), dim3(trlda::kDocIndexThreads),
+                       0, x->model->stream, x->K, x->Kp, B, x->measure, gamma_dev, rows_dev);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// gamma on the host: finite and positive, or TRLDA_ERR_VALUE
+int docindex_check_gamma(const double *gamma, size_t count)
+{
+    for (size_t i = 0; i < count; ++i)
+        if (!(gamma[i] > 0.0) || !std::isfinite(gamma[i]))
+            return fail(TRLDA_ERR_VALUE, "gamma should be finite and positive");
+    return TRLDA_OK;
+}
+
+int docindex_slab_rows(const trlda_docindex *x)
+{
+    return x->slab_rows > 0 ? x->slab_rows : trlda::kDocIndexSlabRows;
+}
+
+// what every query checks before anything is waited for, drawn, copied or launched
+int docindex_query_checks(const trlda_docindex *x, int top_n)
+{
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (top_n < 1 || top_n > trlda::kDocIndexMaxTop || (int64_t)top_n > x->n)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(number of indexed documents, 100)]");
+    const int sr = docindex_slab_rows(x);
+    if ((x->n + sr - 1) / sr > 65535)                    // (grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
+    return TRLDA_OK;
+}
+
+int docindex_batch_checks(const trlda_model *m, const trlda_batch *b)
+{
+    if (!b)
+        return fail(TRLDA_ERR_ARG, "NULL batch");
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    return TRLDA_OK;
+}
+
+template <int SW>
+int docindex_launch_query(trlda_docindex *x, int B, int top_n, int slab_rows, int slabs)
+{
+    const size_t lds = trlda::docindex_query_lds(SW, top_n);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::docindex_query_kernel<SW>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::docindex_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
+                       dim3(trlda::kDocIndexThreads), lds, x->model->stream, x->Kp, (long long)x->n, B, top_n,
+                       slab_rows, x->rows, x->qrows, x->cand_s, x->cand_i);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The search on the model's stream for the B gamma columns at gamma_dev, the results into
+// x->out_i / x->out_s (B x top_n).  The checks have been made; B > 0.
+int docindex_query_device(trlda_docindex *x, const double *gamma_dev, int B, int top_n)
+{
+    const int sr = docindex_slab_rows(x);
+    const int slabs = (int)((x->n + sr - 1) / sr);
+    const size_t cells = (size_t)B * top_n;
+    int rc = grow(&x->qrows, &x->cap_qrows, (size_t)B * x->Kp);
+    if (!rc) rc = grow(&x->cand_s, &x->cap_cand_s, cells * slabs);
+    if (!rc) rc = grow(&x->cand_i, &x->cap_cand_i, cells * slabs);
+    if (!rc) rc = grow(&x->out_s, &x->cap_out_s, cells);
+    if (!rc) rc = grow(&x->out_i, &x->cap_out_i, cells);
+    if (!rc) rc = docindex_launch_rows(x, gamma_dev, B, x->qrows);
+    if (rc)
+        return rc;
+    // (128 query rows per workgroup while their lists fit beside the operands, 64 beyond)
+    rc = top_n <= trlda::kDocIndexWideMaxTop ? docindex_launch_query<2>(x, B, top_n, sr, slabs)
+                                             : docindex_launch_query<1>(x, B, top_n, sr, slabs);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(B), dim3(trlda::kDocIndexThreads), 0, x->model->stream,
+                       B, top_n, slabs, x->cand_s, x->cand_i, x->out_i, x->out_s);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the results to the host; waits
+int docindex_download(trlda_docindex *x, int B, int top_n, int64_t *ids_out, double *sim_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    const size_t cells = (size_t)B * top_n;
+    trlda_model *m = x->model;
+    hipError_t e1 = hipMemcpyAsync(ids_out, x->out_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(sim_out, x->out_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the E-step of trlda_model_estep_host on the batch from the caller's gamma, into m->gamma and
+// m->sstats; the batch has been waited for and the model checked
+int docindex_estep(trlda_model *m, const trlda_batch *b, const double *gamma, int max_iter, double threshold)
+{
+    int rc = ensure_update_workspace(m, b->B);
+    if (rc)
+        return rc;
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, (size_t)m->K * b->B * sizeof(double), hipMemcpyHostToDevice,
+                           m->stream));
+    return estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_create(trlda_model *m, int measure, trlda_docindex **out)
+{
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (measure < 0 || measure >= trlda::kDocIndexMeasures)
+        return fail(TRLDA_ERR_ARG, "unknown measure");
+    trlda_docindex *x = new trlda_docindex();
+    x->model = m;
+    x->measure = measure;
+    x->K = m->K;
+    x->Kp = (m->K + 3) / 4 * 4;
+    *out = x;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_reserve(trlda_docindex *x, int64_t rows)
+{
+    if (!x || rows < 0)
+        return fail(TRLDA_ERR_ARG, "NULL index / negative number of rows");
+    int rc = check_model(x->model);
+    if (rc)
+        return rc;
+    return rows > 0 ? docindex_room(x, rows, rows) : TRLDA_OK;
+}
+
+int64_t trlda_docindex_size(const trlda_docindex *x) { return x ? x->n : 0; }
+
+int trlda_docindex_set_slab_rows(trlda_docindex *x, int rows)
+{
+    if (!x || rows < 0 || rows % 16)
+        return fail(TRLDA_ERR_ARG, "slab rows: 0 (default) or a positive multiple of 16");
+    x->slab_rows = rows;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_add_gamma_dev(trlda_docindex *x, const double *gamma_dev, int B)
+{
+    if (!x || B < 0 || (B > 0 && !gamma_dev))
+        return fail(TRLDA_ERR_ARG, "NULL index / gamma, or a negative number of documents");
+    int rc = check_model(x->model);
+    if (rc || B == 0)
+        return rc;
+    rc = docindex_room(x, x->n + B, B);
+    if (!rc) rc = docindex_launch_rows(x, gamma_dev, B, x->rows + (size_t)x->n * x->Kp);
+    if (rc)
+        return rc;
+    x->n += B;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_add_gamma(trlda_docindex *x, const double *gamma, int B)
+{
+    if (!x || B < 0 || (B > 0 && !gamma))
+        return fail(TRLDA_ERR_ARG, "NULL index / gamma, or a negative number of documents");
+    const size_t count = (size_t)x->K * B;
+    if (int rc_val = docindex_check_gamma(gamma, count))
+        return rc_val;
+    int rc = check_model(x->model);
+    if (rc || B == 0)
+        return rc;
+    rc = grow(&x->gstage, &x->cap_gstage, count);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(x->gstage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
+    rc = trlda_docindex_add_gamma_dev(x, x->gstage, B);
+    // (the caller's array may go once this returns)
+    HIP_TRY(hipStreamSynchronize(x->model->stream));
+    return rc;
+}
+
+int trlda_docindex_add(trlda_docindex *x, const trlda_batch *b, double *gamma, int max_iter, double threshold)
+{
+    if (!x)
+        return fail(TRLDA_ERR_ARG, "NULL index");
+    trlda_model *m = x->model;
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (int rc_arg = docindex_batch_checks(m, b))
+        return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int B = b->B;
+    if (B <= 0)
+        return TRLDA_OK;
+    if (!gamma)
+        return fail(TRLDA_ERR_ARG, "NULL gamma");
+    rc = docindex_room(x, x->n + B, B);
+    if (!rc) rc = docindex_estep(m, b, gamma, max_iter, threshold);
+    if (!rc) rc = docindex_launch_rows(x, m->gamma, B, x->rows + (size_t)x->n * x->Kp);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, (size_t)m->K * B * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    x->n += B;
+    return check_split_exchange(m);
+}
+
+int trlda_docindex_query_gamma(trlda_docindex *x, const double *gamma, int B, int top_n, int64_t *ids_out,
+                               double *sim_out)
+{
+    if (!x || B < 0)
+        return fail(TRLDA_ERR_ARG, "NULL index, or a negative number of documents");
+    if (int rc_arg = docindex_query_checks(x, top_n))
+        return rc_arg;
+    if (B > 0 && (!gamma || !ids_out || !sim_out))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / ids / similarities");
+    const size_t count = (size_t)x->K * B;
+    if (int rc_val = docindex_check_gamma(gamma, count))
+        return rc_val;
+    int rc = check_model(x->model);
+    if (rc || B == 0)
+        return rc;
+    rc = grow(&x->gstage, &x->cap_gstage, count);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(x->gstage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
+    rc = docindex_query_device(x, x->gstage, B, top_n);
+    if (rc)
+        return rc;
+    return docindex_download(x, B, top_n, ids_out, sim_out);
+}
+
+int trlda_docindex_query(trlda_docindex *x, const trlda_batch *b, double *gamma, int max_iter, double threshold,
+                         int top_n, int64_t *ids_out, double *sim_out)
+{
+    if (!x)
+        return fail(TRLDA_ERR_ARG, "NULL index");
+    trlda_model *m = x->model;
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (int rc_arg = docindex_query_checks(x, top_n))
+        return rc_arg;
+    if (int rc_arg = docindex_batch_checks(m, b))
+        return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int B = b->B;
+    if (B <= 0)
+        return TRLDA_OK;
+    if (!gamma || !ids_out || !sim_out)
+        return fail(TRLDA_ERR_ARG, "NULL gamma / ids / similarities");
+    rc = docindex_estep(m, b, gamma, max_iter, threshold);
+    if (!rc) rc = docindex_query_device(x, m->gamma, B, top_n);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    HIP_TRY(hipMemcpyAsync(gamma, m->gamma, (size_t)m->K * B * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    rc = docindex_download(x, B, top_n, ids_out, sim_out);
+    return rc ? rc : check_split_exchange(m);
+}
+
+int trlda_docindex_read_rows(trlda_docindex *x, int64_t first, int64_t count, double *rows_out)
+{
+    if (!x || first < 0 || count < 0 || first + count > x->n)
+        return fail(TRLDA_ERR_ARG, "NULL index, or rows outside [0, size)");
+    int rc = check_model(x->model);
+    if (rc || count == 0)
+        return rc;
+    if (!rows_out)
+        return fail(TRLDA_ERR_ARG, "rows_out is NULL");
+    // (K of the Kp doubles of each row: the pad stays behind)
+    hipError_t e1 = hipMemcpy2DAsync(rows_out, (size_t)x->K * sizeof(double), x->rows + (size_t)first * x->Kp,
+                                     (size_t)x->Kp * sizeof(double), (size_t)x->K * sizeof(double), (size_t)count,
+                                     hipMemcpyDeviceToHost, x->model->stream);
+    hipError_t e2 = hipStreamSynchronize(x->model->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    return TRLDA_OK;
+}
+
+int trlda_docindex_destroy(trlda_docindex *x)
+{
+    if (!x)
+        return TRLDA_OK;
+    if (x->model && use_device(x->model->device) == TRLDA_OK && x->model->stream)
+        (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
+    docindex_free(x);
     return TRLDA_OK;
 }
 

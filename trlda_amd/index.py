@@ -1,0 +1,209 @@
+"""Nearest documents in topic space: ``DocumentIndex`` (csrc/docindex_kernels.h).
+
+A device-resident table of the documents' topic proportions theta = gamma / sum(gamma) and the
+ranked search over it.  No counterpart in the reference package.
+"""
+import ctypes as C
+import operator
+
+import numpy as np
+
+from . import _ffi
+
+MEASURES = {"hellinger": 0, "cosine": 1}
+MAX_TOP_N = 100
+
+
+def _measure(name):
+    if not isinstance(name, str):
+        raise TypeError("`measure` should be of type `str`.")
+    try:
+        return MEASURES[name.lower()]
+    except KeyError:
+        raise ValueError("Unknown measure '%s' (expected 'hellinger' or 'cosine')." % name)
+
+
+class DocumentIndex(object):
+    """The documents of a model ranked by how close their topic proportions are.
+
+    ``measure='hellinger'`` (default) stores ``sqrt(theta)`` and ranks by the Bhattacharyya
+    coefficient ``s = sum_k sqrt(theta_qk theta_dk)``; the distance is ``sqrt(max(0, 1 - s))``.
+    ``measure='cosine'`` stores ``theta / |theta|`` and ranks by the cosine ``s``; the distance is
+    ``max(0, 1 - s)``.  theta is the posterior mean ``gamma / sum(gamma)``.  Ids are the documents'
+    positions in order of addition, from 0.  Equal similarities rank by smaller id, so the result
+    does not depend on how the index was filled or how the search is cut up.
+
+    The index stores theta, not lambda: after the model's lambda changes, the rows added before
+    are stale.  This is not detected.  It lives on the model's device and is closed with it.
+    """
+
+    def __init__(self, model, measure="hellinger"):
+        self._handle = None
+        self._measure = _measure(measure)                    # (before any GPU work)
+        _ffi.require_gpu()
+        if getattr(model, "_handle", None) is None:
+            raise RuntimeError("The model has been closed.")
+        self._model = model
+        self._K = model.num_topics
+        handle = _ffi.vp()
+        _ffi.check(_ffi.lib().trlda_docindex_create(model._handle, self._measure, C.byref(handle)))
+        self._handle = handle
+        model._register_index(self)
+
+    # -- lifetime ---------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_handle", None):
+            _ffi.lib().trlda_docindex_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self._handle:
+            raise RuntimeError("The index has been closed.")
+        return self._handle
+
+    @property
+    def measure(self):
+        return "cosine" if self._measure else "hellinger"
+
+    def __len__(self):
+        return int(_ffi.lib().trlda_docindex_size(self._live()))
+
+    def reserve(self, n):
+        """Room for ``n`` documents in all, so that adding them copies nothing."""
+        _ffi.check(_ffi.lib().trlda_docindex_reserve(self._live(), operator.index(n)))
+
+    def set_slab_rows(self, rows):
+        """A/B switch: index rows per workgroup of the search (0: default).  Results do not depend on it."""
+        _ffi.check(_ffi.lib().trlda_docindex_set_slab_rows(self._live(), operator.index(rows)))
+
+    def rows(self, first=0, count=None):
+        """The stored rows ``first .. first + count - 1`` (count x K float64)."""
+        first = operator.index(first)
+        count = len(self) - first if count is None else operator.index(count)
+        out = np.empty((max(count, 0), self._K), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_read_rows(self._live(), first, count, out.ctypes.data))
+        return out
+
+    # -- arguments --------------------------------------------------------------------------------
+    def _gamma(self, gamma):
+        try:
+            g = np.array(gamma, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`gamma` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Gamma has wrong dimensionality.")
+        return np.asfortranarray(g)
+
+    def _latents(self, latents, B):
+        """gamma0 (K x B): ``latents``, else drawn from the seeded stream as ``update_variables`` draws it."""
+        if latents is not None:
+            try:
+                g = np.array(latents, dtype=np.float64, order="F", copy=True)
+            except (TypeError, ValueError):
+                raise TypeError("`latents` should be of type `ndarray`.")
+            if g.ndim == 1:
+                g = g.reshape(-1, 1, order="F")
+            if g.ndim != 2 or g.shape != (self._K, B):
+                raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+            return np.asfortranarray(g)
+        gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+        _ffi.lib().trlda_sample_gamma_init(self._K, B, gamma)                 # lda.cpp:135
+        return gamma
+
+    def _top_n(self, top_n):
+        top_n = operator.index(top_n)
+        if not 1 <= top_n <= min(len(self), MAX_TOP_N):
+            raise RuntimeError("`top_n` should lie between 1 and min(len(index), %d)." % MAX_TOP_N)
+        return top_n
+
+    def _result(self, ids, sim, return_similarity):
+        if return_similarity:
+            return ids, sim
+        rest = np.maximum(0.0, 1.0 - sim)
+        return ids, (rest if self._measure else np.sqrt(rest))
+
+    # -- adding -----------------------------------------------------------------------------------
+    def add(self, docs, latents=None, max_iter=100, threshold=0.001, return_gamma=False):
+        """VI on ``docs`` (a list, ``DocumentList`` or ``DeviceBatch``) with lambda fixed, from
+        ``latents`` as gamma0 or a gamma drawn as ``update_variables`` draws it; the documents are
+        appended.  Returns the first new id (with ``return_gamma=True`` also gamma, K x B)."""
+        handle = self._live()
+        model = self._model
+        _ffi.check_vi_topics(self._K)                                # (before the draw and the upload)
+        batch, owned = model._batch(docs)
+        try:
+            model._settle()
+            B = len(batch)
+            gamma = self._latents(latents, B)
+            first = len(self)
+            _ffi.check(_ffi.lib().trlda_docindex_add(handle, batch.handle, gamma.ctypes.data, int(max_iter),
+                                                     float(threshold)))
+        finally:
+            if owned:
+                batch.close()
+        return (first, gamma) if return_gamma else first
+
+    def add_gamma(self, gamma):
+        """Appends the documents with variational parameters ``gamma`` (K x B, finite and
+        positive); no E-step.  Returns the first new id."""
+        handle = self._live()
+        g = self._gamma(gamma)
+        first = len(self)
+        _ffi.check(_ffi.lib().trlda_docindex_add_gamma(handle, g.ctypes.data, g.shape[1]))
+        return first
+
+    def add_gamma_device(self, gamma_ptr, num_documents):
+        """The same from a device pointer to K x B float64 (not validated; enqueued on the
+        model's stream).  Returns the first new id."""
+        handle = self._live()
+        first = len(self)
+        _ffi.check(_ffi.lib().trlda_docindex_add_gamma_dev(handle, gamma_ptr, operator.index(num_documents)))
+        return first
+
+    # -- searching --------------------------------------------------------------------------------
+    def query(self, docs, top_n=10, latents=None, max_iter=100, threshold=0.001, return_gamma=False,
+              return_similarity=False):
+        """The ``top_n`` nearest indexed documents of each document of ``docs``, after VI on them
+        as in ``add``.  Returns ``(ids, dist)``, int64 and float64 of shape (B, top_n), closest
+        first; with ``return_similarity=True`` the similarity s in place of the distance; with
+        ``return_gamma=True`` gamma (K x B) is appended.  ``1 <= top_n <= min(len(index), 100)``,
+        else RuntimeError."""
+        handle = self._live()
+        model = self._model
+        top_n = self._top_n(top_n)
+        _ffi.check_vi_topics(self._K)                                # (before the draw and the upload)
+        batch, owned = model._batch(docs)
+        try:
+            model._settle()
+            B = len(batch)
+            gamma = self._latents(latents, B)
+            ids = np.empty((B, top_n), dtype=np.int64)
+            sim = np.empty((B, top_n), dtype=np.float64)
+            _ffi.check(_ffi.lib().trlda_docindex_query(handle, batch.handle, gamma.ctypes.data, int(max_iter),
+                                                       float(threshold), top_n, ids.ctypes.data,
+                                                       sim.ctypes.data))
+        finally:
+            if owned:
+                batch.close()
+        out = self._result(ids, sim, return_similarity)
+        return out + (gamma,) if return_gamma else out
+
+    def query_gamma(self, gamma, top_n=10, return_similarity=False):
+        """The same search for documents given by their ``gamma`` (K x B); no E-step."""
+        handle = self._live()
+        top_n = self._top_n(top_n)
+        g = self._gamma(gamma)
+        B = g.shape[1]
+        ids = np.empty((B, top_n), dtype=np.int64)
+        sim = np.empty((B, top_n), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_query_gamma(handle, g.ctypes.data, B, top_n, ids.ctypes.data,
+                                                         sim.ctypes.data))
+        return self._result(ids, sim, return_similarity)

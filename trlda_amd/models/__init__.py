@@ -152,6 +152,9 @@ class LDA(Distribution):
             except Exception:                        # noqa: BLE001 -- closing must not raise
                 self._eb_pending = None
         self._eb_pending = None
+        # (a document index runs on the model's stream: it goes first)
+        for index in list(getattr(self, "_indexes", None) or ()):
+            index.close()
         if getattr(self, "_handle", None):
             _ffi.lib().trlda_model_destroy(self._handle)
             self._handle = None
@@ -626,6 +629,22 @@ class LDA(Distribution):
         if return_gamma:
             return indptr, topics, probs, gamma
         return indptr, topics, probs
+
+    # -- nearest documents in topic space (csrc/docindex_kernels.h) ---------------------------------
+    def _register_index(self, index):
+        import weakref
+        if getattr(self, "_indexes", None) is None:
+            self._indexes = weakref.WeakSet()
+        self._indexes.add(index)
+
+    def document_index(self, measure='hellinger'):
+        """An empty ``trlda_amd.DocumentIndex`` for this model: documents are added to it by their
+        topic proportions theta = gamma / sum(gamma) and the ``top_n`` nearest of them are found for
+        the documents of a batch, on the GPU.  ``measure``: 'hellinger' (default) or 'cosine', case
+        does not matter; another string raises ValueError, a non-string TypeError.  The index is
+        closed with the model."""
+        from ..index import DocumentIndex
+        return DocumentIndex(self, measure)
 
     # -- topic coherence (Mimno et al. 2011; Bouma 2009; csrc/coherence_kernels.h) -----------------
     def top_words(self, top_n=10):
