@@ -1161,6 +1161,11 @@ int trlda_debug_dirichlet_sums(int m, int n, double alpha, uint64_t key, double 
 /* diagnostics: the s_memrealtime stamps of the model's last merged launch, 3 x 1024 values
  * (TRLDA_MERGED_STAMPS=1; tools/merged_stamps.py) */
 int trlda_debug_merged_stamps(trlda_model *model, unsigned long long *host_out);
+/* test hook: the device allocations the library's own buffers -- those of models, coherence
+ * accumulators, document indexes and temporaries; not batches, not trlda_dev_alloc's -- hold now
+ * (*live) and have made so far (*total) in this process.  With every handle destroyed, *live is 0
+ * (tests/test_gpu_buffers.py). */
+int trlda_debug_device_buffers(long long *live, long long *total);
 
 /* ---- measurement --------------------------------------------------------- */
 

@@ -223,6 +223,7 @@ _SIGNATURES = {
     "trlda_debug_fold16": (C.c_int, [C.c_int, vp, vp, vp, vp]),
     "trlda_debug_peek": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
     "trlda_debug_merged_stamps": (C.c_int, [vp, vp]),
+    "trlda_debug_device_buffers": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "trlda_model_set_doc_kernel": (C.c_int, [vp, C.c_int]),
     "trlda_model_last_doc_kernel": (C.c_char_p, [vp]),
     "trlda_model_set_split_preamble": (C.c_int, [vp, C.c_int]),

@@ -56,16 +56,6 @@
 
 namespace {
 
-// frees a temporary device allocation on every path out of a function
-struct DevTemp {
-    void *p = nullptr;
-    ~DevTemp()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-};
-
 using trlda_host::fail;                  // the thread-local message behind trlda_last_error()
 
 #define HIP_TRY(expr)                                                                   \
@@ -97,15 +87,65 @@ constexpr int kUpdVlRows = 4096;         // very long words whose lambdas take a
                                          // with more of them keeps them in the one-block-per-word path
 constexpr double kFusedRowsumFloor = 2e-3;   // psi(2e-3) = -500.6: exp(-psi(row sum)) stays finite
 
+// Who owns device memory: a DevBuf does -- a pointer and its capacity in elements, freed when the
+// DevBuf goes (a model's with `delete m`, a temporary's at the end of its function).  A raw T * field
+// or local borrows.  Move-only; it converts to T *, so launches, argument structs and pointer
+// arithmetic read as with a raw pointer.
+std::atomic<long long> g_devbuf_live{0}, g_devbuf_total{0};   // trlda_debug_device_buffers
+
 template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0)
-        count = 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
-    return TRLDA_OK;
-}
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        swap(o);
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+
+    void swap(DevBuf &o) noexcept
+    {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+    }
+    // (hipFree waits for the device)
+    void reset()
+    {
+        if (p_) {
+            (void)hipFree(p_);
+            --g_devbuf_live;
+        }
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // `count` elements (at least one is allocated); whatever it held is freed first
+    int alloc(size_t count)
+    {
+        reset();
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+        p_ = static_cast<T *>(p);
+        cap_ = count;
+        ++g_devbuf_live;
+        ++g_devbuf_total;
+        return TRLDA_OK;
+    }
+    // grow-only: on failure the pointer is null AND the capacity is 0, so a later, smaller request
+    // allocates again instead of launching on a null pointer
+    int grow(size_t count) { return count <= cap_ && p_ ? TRLDA_OK : alloc(count); }
+
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t cap() const { return cap_; }
+
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and size, not per launch
 int ensure_dynamic_lds(const void *func, size_t bytes)
@@ -288,8 +328,8 @@ struct trlda_model {
     // that batch while lambda has not been written (lambda_version).
     uint64_t lambda_version = 1;
     // (three of each: with deferred statistics the batch before this one still reads its buffer)
-    double *eeb_pp[3] = {nullptr, nullptr, nullptr}, *partial_pp[3] = {nullptr, nullptr, nullptr};
-    double *scale_pp[3] = {nullptr, nullptr, nullptr};   // 3 K each: the finished topic factors (PreArgs::c_out)
+    DevBuf<double> eeb_pp[3], partial_pp[3];
+    DevBuf<double> scale_pp[3];         // 3 K each: the finished topic factors (PreArgs::c_out)
     // Deferred statistics (trlda_model_set_deferred_stats; estep_merged.h): in a stream of E-steps
     // on an unchanged lambda (trlda_model_estep_io_next) the statistics of a call (lda.cpp:207-217)
     // are not launched by that call -- they ride on the NEXT call's document launch, or are
@@ -301,12 +341,11 @@ struct trlda_model {
         bool valid = false;
         const trlda_batch *batch = nullptr;
         double *sstats = nullptr;         // the caller's K x V
-        double *epg = nullptr, *tw_word = nullptr;
+        double *epg = nullptr, *tw_word = nullptr;   // (borrowed, as `eeb`: dfr_* / eeb_pp / m->eeb)
         double *eeb = nullptr;
         int eeb_buf = -1;                 // index into eeb_pp, or -1: m->eeb
     } pending;
-    double *dfr_epg_base[2] = {nullptr, nullptr}, *dfr_tw[2] = {nullptr, nullptr};
-    size_t dfr_cap_docs[2] = {0, 0}, dfr_cap_tw[2] = {0, 0};
+    DevBuf<double> dfr_epg_base[2], dfr_tw[2];
     int dfr_cur = 0;
     unsigned int defer_work_total = 0;    // what sync_counters[32] holds: the helpers' items so far
     bool last_deferred = false;           // the last E-step left its statistics pending
@@ -404,7 +443,7 @@ struct trlda_model {
         int buf = 0, G = 0;
         bool dense = false;
     } prefetch;
-    double *eeb_cur = nullptr;          // the exp E[log beta] buffer of the E-step in flight
+    double *eeb_cur = nullptr;          // the exp E[log beta] buffer of the E-step in flight (borrowed)
     // The E-step's switches (the trlda_model_set_* setters, tests and comparisons).  A stream lane
     // follows its owner's (lane_follow).
     struct Switches {
@@ -430,26 +469,28 @@ struct trlda_model {
     } sw;
     const char *last_doc_kernel = "";   // kernel that took most documents of the last E-step
     bool last_preamble_fused = false;
+    // what every launch reads: the model's own arrays, or in a stream lane its owner's (borrowed)
     double *lambda = nullptr, *alpha = nullptr;
-    double *eeb = nullptr, *psi_sum = nullptr, *partial = nullptr;
-    unsigned int *counter = nullptr;
+    DevBuf<double> lambda_own, alpha_own;   // empty in a lane
+    DevBuf<double> eeb, psi_sum, partial;
+    DevBuf<unsigned int> counter;
     // Row sums carried from the kernels that wrote lambda: rs_full[k] = sum_w lambda[k, w]
     // (lda.cpp:172) is valid while rs_valid, and the next E-step skips its row-sum pass.
     // rs_static: the part over the words outside the current update's mini-batch.
-    double *rs_full = nullptr, *rs_static = nullptr, *upd_partial = nullptr;
+    DevBuf<double> rs_full, rs_static, upd_partial;
     bool rs_valid = false;
     // ... or they are still in pieces: block partials `carry_rows` (carry_n rows of K) plus
     // `carry_base` (K, or null).  Small tables add them up inside the next preamble launch
     // (preamble_fused_kernel's combine workgroups, 8 rows into carry_out); anything else
     // resolves them with rowsum_combine_wave_kernel first.
     bool carry_pending = false;
-    const double *carry_rows = nullptr, *carry_base = nullptr;
+    const double *carry_rows = nullptr, *carry_base = nullptr;   // (borrowed)
     int carry_n = 0;
-    double *carry_out = nullptr;        // kCarryBlocks x K
+    DevBuf<double> carry_out;           // kCarryBlocks x K
     // The preamble the last M-step kernel left behind (UpdateOut::u_out / group_rows): valid for
     // lambda_version `version`, for every word (`all`) or the active words of batch `batch_id`
-    double *upd_groups = nullptr;       // kUpdGroups x K
-    unsigned int *group_counter = nullptr;
+    DevBuf<double> upd_groups;          // kUpdGroups x K
+    DevBuf<unsigned int> group_counter;
     struct {
         bool valid = false, all = false;
         uint64_t version = 0, batch_id = 0;
@@ -475,14 +516,12 @@ struct trlda_model {
     // everything else that writes lambda.  Only then may an M-step kernel also emit exp(psi(lambda))
     // with the call-free positive-argument form (psi.h, exp_digamma_positive).
     bool lambda_positive = false;
-    // per-batch workspaces, grown on demand
-    size_t cap_docs = 0, cap_tw_csr = 0, cap_tw_word = 0;
     // Data-parallel factor exchange (DpContext below): the gathered factors of all ranks, the
     // statistics kernel's row index into them, the shard cut points on the device
     DpContext *dp = nullptr;            // set for the duration of a *_dp call
-    double *dp_gather = nullptr;        // the buffer of the call in flight: one of the two below
-    double *dp_gather_own = nullptr, *dp_gather_direct = nullptr;
-    size_t cap_dp_gather = 0;
+    double *dp_gather = nullptr;        // the buffer of the call in flight: one of the two below (borrowed)
+    DevBuf<double> dp_gather_own;
+    double *dp_gather_direct = nullptr; // (borrowed: `direct.region`)
     int (*allgather_hook)(void *, const void *, void *, size_t, void *) = nullptr;
     void *allgather_ctx = nullptr;
     int (*allgatherv_hook)(void *, void *, const size_t *, int, int, void *) = nullptr;
@@ -500,44 +539,44 @@ struct trlda_model {
         std::vector<void *> opened;         // hipIpcOpenMemHandle results to close
         unsigned long long step = 0;
     } direct;
-    double *epg = nullptr, *tw_csr = nullptr, *tw_word = nullptr;
-    double *epg_base = nullptr;         // the allocation: K zeros (row -1 of epg), then epg
+    // per-batch workspaces, grown on demand
+    // (borrowed: row 0 of epg_base and tw_word_own -- or, while flush_pending launches the statistics
+    // a deferred E-step left, that call's buffers)
+    double *epg = nullptr, *tw_word = nullptr;
+    DevBuf<double> tw_csr, tw_word_own;
+    DevBuf<double> epg_base;            // the allocation: K zeros (row -1 of epg), then epg
     // very long lists (VeryLongArgs): a row of K sums per segment task, a counter per word
-    double *seg_partial = nullptr;
-    size_t cap_seg_partial = 0;
-    unsigned int *seg_counter = nullptr;
-    size_t cap_seg_counter = 0;
+    DevBuf<double> seg_partial;
+    DevBuf<unsigned int> seg_counter;
     // merged launch (estep_merged.h): the statistics as workgroups of the document launch.
     // Two counters that only grow (documents done | topic factors finished) and what they have
     // been asked to reach so far; the finished topic factors of an in-launch combine
     bool last_merged = false;
-    unsigned int *sync_counters = nullptr;
+    DevBuf<unsigned int> sync_counters;
     unsigned int docs_done_total = 0, c_ready_total = 0;
     // ... and a flag per waiter (statistics workgroups | document workgroups, 64 bytes apart) that
     // receives the number of the launch it may go on in (merged_epoch: only grows)
-    unsigned int *sync_flags = nullptr;
+    DevBuf<unsigned int> sync_flags;
     unsigned int merged_epoch = 0;
-    unsigned long long *merged_stamps = nullptr;   // diagnostics, TRLDA_MERGED_STAMPS=1
-    unsigned long long *deferred_stamps = nullptr; // ... of a deferred launch (3 x 3072)
-    double *scale_comb = nullptr;       // 3 K
+    DevBuf<unsigned long long> merged_stamps;      // diagnostics, TRLDA_MERGED_STAMPS=1
+    DevBuf<unsigned long long> deferred_stamps;    // ... of a deferred launch (3 x 3072)
+    DevBuf<double> scale_comb;          // 3 K
     // split documents: the exchange rows of a launch (NaN before it), the give-up flag
-    double *xbuf = nullptr;
-    size_t cap_xbuf = 0;
+    DevBuf<double> xbuf;
     // the give-up flag: one int in pinned, host-coherent memory that the kernels see through
     // `xerr` -- checking it after a synchronisation is a plain host read (check_split_exchange)
     int *xerr = nullptr;
     volatile int *xerr_host = nullptr;
     int last_split_wgs = 0;             // workgroups of the last document launch beyond one per document
     // update_parameters workspaces
-    double *lambda_prime = nullptr, *sstats = nullptr, *gamma = nullptr, *wordcounts = nullptr;
-    size_t cap_gamma = 0, cap_lambda_prime = 0, cap_sstats = 0, cap_wordcounts = 0;
+    DevBuf<double> lambda_prime, sstats, gamma, wordcounts;
     double *stage[2] = {nullptr, nullptr};      // pinned host buffers for gamma0 draws
     size_t cap_stage[2] = {0, 0};
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     int stage_next = 0;
     // adaptive learning rate: running average of the updates (onlinelda.cpp:170), K x V
-    double *ada_gradient = nullptr;
-    double *reduce_out = nullptr;               // small buffer for block results of reductions
+    DevBuf<double> ada_gradient;
+    DevBuf<double> reduce_out;                  // small buffer for block results of reductions
     // empirical-Bayes sums on their way to the host (trlda_model_online_eb_begin / _finish):
     // K + G + K doubles in pinned memory, complete when eb_event has passed
     struct {
@@ -547,16 +586,13 @@ struct trlda_model {
         size_t cap = 0;
         hipEvent_t event = nullptr;
     } eb;
-    size_t cap_reduce = 0;
-    int32_t *iters = nullptr;                   // per-document iteration counts (estep_host)
-    size_t cap_iters = 0;
+    DevBuf<int32_t> iters;                      // per-document iteration counts (estep_host)
     // gamma0 of the NEXT fresh E-step, drawn ahead on a stream of its own while this call's
     // kernels run (fresh_gamma_device): two buffers alternate, `spec` says what is in flight
     bool draw_ahead = false;                    // trlda_model_set_draw_ahead / TRLDA_DRAW_AHEAD=1
     hipStream_t draw_stream = nullptr;
     hipEvent_t ev_main = nullptr, ev_draw = nullptr;
-    double *gspec[2] = {nullptr, nullptr};
-    size_t cap_gspec[2] = {0, 0};
+    DevBuf<double> gspec[2];
     struct {
         bool valid = false;
         uint64_t token = 0;
@@ -564,7 +600,7 @@ struct trlda_model {
         long long total = 0, lo = 0, hi = 0;
         bool in_launch = false;                 // drawn by a document launch of the model's stream: no event
     } spec;
-    const double *gamma0_src = nullptr;         // the next E-step on m->gamma reads gamma0 here
+    const double *gamma0_src = nullptr;         // the next E-step on m->gamma reads gamma0 here (borrowed)
     // ... or INSIDE this call's document launch (round 6; estep_merged.h, AuxArgs): extra workgroups of
     // a merged launch draw it on the CUs the documents leave free.  `aux_draw_req`: the fresh draw of
     // this call asks the call's next document launch to carry the draw of the next one (same shape);
@@ -579,16 +615,12 @@ struct trlda_model {
     unsigned int aux_work_total = 0;            // what sync_counters[48] holds: the auxiliary workgroups' items so far
     int64_t inlaunch_decays = 0;                // inactive-word passes made inside a document launch (tests)
     bool aux_decay = true;                      // trlda_model_set_aux_decay / TRLDA_AUX_DECAY=0
-    uint32_t *rng_win2 = nullptr;               // scratch of the draw stream
-    size_t cap_rng_win2 = 0;
-    double *rng_vbuf2 = nullptr;
-    size_t cap_rng_vbuf2 = 0;
+    DevBuf<uint32_t> rng_win2;                  // scratch of the draw stream
+    DevBuf<double> rng_vbuf2;
     // device-side sampleGamma (rng_kernels.h): segment windows, |u| of a group of passes
     bool host_gamma_draw = false;               // true: the bit-exact host draw (glibc log)
-    uint32_t *rng_win = nullptr;
-    size_t cap_rng_win = 0;
-    double *rng_vbuf = nullptr;
-    size_t cap_rng_vbuf = 0;
+    DevBuf<uint32_t> rng_win;
+    DevBuf<double> rng_vbuf;
     // timing: five events per E-step from a pool, resolved lazily (no host sync per step)
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;   // all events ever created
@@ -599,18 +631,13 @@ struct trlda_model {
     // call leaves whatever the VI path keeps between calls -- exp(psi(lambda)) left behind, row sums,
     // prefetched preambles, deferred statistics -- as it was
     struct {
-        double *eeb = nullptr, *partial = nullptr, *psi_sum = nullptr;
-        size_t cap_eeb = 0, cap_partial = 0, cap_psi = 0;
-        uint32_t *cnt = nullptr;                // K x V, zero between calls (gibbs_finish_kernel)
-        size_t cap_cnt = 0;
-        uint16_t *z = nullptr;
-        size_t cap_z = 0;
-        int64_t *tokens = nullptr, *tok_off = nullptr;
-        int32_t *order = nullptr;
-        size_t cap_tokens = 0, cap_tok_off = 0, cap_order = 0;
-        int *flag = nullptr;
-        double *theta_in = nullptr, *theta = nullptr, *sstats = nullptr;   // trlda_model_gibbs_host's
-        size_t cap_theta_in = 0, cap_theta = 0, cap_sstats = 0;
+        DevBuf<double> eeb, partial, psi_sum;
+        DevBuf<uint32_t> cnt;                   // K x V, zero between calls (gibbs_finish_kernel)
+        DevBuf<uint16_t> z;
+        DevBuf<int64_t> tokens, tok_off;
+        DevBuf<int32_t> order;
+        DevBuf<int> flag;
+        DevBuf<double> theta_in, theta, sstats; // trlda_model_gibbs_host's
         // the plan (token offsets, document order) of the batch it was made for
         uint64_t plan_batch = 0;
         int64_t total_tokens = 0;
@@ -618,48 +645,37 @@ struct trlda_model {
         // the update loops (trlda_model_online_update_gibbs / _batch_update_gibbs): row sums
         // (the words outside the batch, then those of lambda as it stands), the M-step's block
         // rows, and the "lambda has an element <= 0" flag
-        double *rs = nullptr, *mpart = nullptr;
-        size_t cap_rs = 0, cap_mpart = 0;
-        int *nonpos = nullptr;
+        DevBuf<double> rs, mpart;
+        DevBuf<int> nonpos;
     } gibbs;
     // sampling documents (sample_kernels.h, trlda_model_sample): the K x V prefix table lives in
     // gibbs.eeb (per-call scratch of either path, behind a flush); the rest is its own
     struct {
-        double *part = nullptr;                 // 2 x K x chunks: the chunks' maxima and totals
-        size_t cap_part = 0;
-        double *pre = nullptr;                  // K x B: the documents' theta prefixes
-        size_t cap_pre = 0;
-        int32_t *indptr = nullptr, *ids = nullptr;   // trlda_model_sample_host's staging
-        size_t cap_indptr = 0, cap_ids = 0;
-        double *theta = nullptr;
-        size_t cap_theta = 0;
+        DevBuf<double> part;                    // 2 x K x chunks: the chunks' maxima and totals
+        DevBuf<double> pre;                     // K x B: the documents' theta prefixes
+        DevBuf<int32_t> indptr, ids;            // trlda_model_sample_host's staging
+        DevBuf<double> theta;
     } sample;
-    // the documents' marginal likelihood (marginal_kernels.h, trlda_model_document_loglik): row sums of
-    // lambda formed from lambda itself, and their block partials
+    // the row sums of lambda formed from lambda itself and their block partials (lambda_rowsums:
+    // trlda_model_document_loglik, trlda_model_left_to_right, trlda_model_word_topics)
     struct {
-        double *partial = nullptr, *rs = nullptr;
-        size_t cap_partial = 0, cap_rs = 0;
-    } marginal;
-    // the left-to-right sampler (l2r_kernels.h, trlda_model_left_to_right): row sums of lambda formed
-    // from lambda itself, sum alpha, the documents' token counts, order and offsets, and the groups'
-    // workspace (topics and the p table) under kL2rBudget
+        DevBuf<double> partial, rs;
+    } rowsums;
+    // the left-to-right sampler (l2r_kernels.h, trlda_model_left_to_right): sum alpha, the documents'
+    // token counts, order and offsets, and the groups' workspace (topics and the p table) under
+    // kL2rBudget
     struct {
-        double *partial = nullptr, *rs = nullptr, *asum = nullptr, *p = nullptr, *out = nullptr;
-        size_t cap_partial = 0, cap_rs = 0, cap_p = 0, cap_out = 0;
-        int64_t *tokens = nullptr, *off = nullptr;
-        int32_t *order = nullptr;
-        size_t cap_tokens = 0, cap_off = 0, cap_order = 0;
-        uint16_t *z = nullptr;
-        size_t cap_z = 0;
-        int *flag = nullptr;
+        DevBuf<double> asum, p, out;
+        DevBuf<int64_t> tokens, off;
+        DevBuf<int32_t> order;
+        DevBuf<uint16_t> z;
+        DevBuf<int> flag;
     } l2r;
-    // the per-word topic posteriors (wordtopics_kernels.h, trlda_model_word_topics): row sums of lambda
-    // formed from lambda itself and their block partials; the host form's output staging
+    // the per-word topic posteriors (wordtopics_kernels.h, trlda_model_word_topics): the host form's
+    // output staging
     struct {
-        double *partial = nullptr, *rs = nullptr, *probs = nullptr;
-        size_t cap_partial = 0, cap_rs = 0, cap_probs = 0;
-        int32_t *topics = nullptr;
-        size_t cap_topics = 0;
+        DevBuf<double> probs;
+        DevBuf<int32_t> topics;
     } wordtopics;
 };
 
@@ -869,50 +885,35 @@ int batch_end(trlda_model *m, const trlda_batch *b)
     return TRLDA_OK;
 }
 
-// grow-only device buffer: on failure the pointer is null AND the capacity is 0, so a later,
-// smaller request allocates again instead of launching on a null pointer
-template <typename T>
-int grow(T **p, size_t *cap, size_t count)
-{
-    if (count <= *cap && *p)
-        return TRLDA_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    int rc = dev_alloc(p, count);
-    if (rc)
-        return rc;
-    *cap = count;
-    return TRLDA_OK;
-}
-
 int ensure_batch_workspace(trlda_model *m, const trlda_batch *b)
 {
     // (row -1 of epg is zero: where the statistics stage of a merged launch points the entries
     // past the end of a list, estep_merged.h)
     int rc = TRLDA_OK;
     const size_t rows = (size_t)std::max(b->B, 1) + 1;
-    if (rows * (size_t)m->K > m->cap_docs || !m->epg_base) {
-        rc = grow(&m->epg_base, &m->cap_docs, rows * (size_t)m->K);
+    if (rows * (size_t)m->K > m->epg_base.cap() || !m->epg_base) {
+        rc = m->epg_base.grow(rows * (size_t)m->K);
         m->epg = nullptr;
         if (!rc) {
             HIP_TRY(hipMemsetAsync(m->epg_base, 0, (size_t)m->K * sizeof(double), m->stream));
             m->epg = m->epg_base + m->K;
         }
     }
-    if (!rc) rc = grow(&m->tw_csr, &m->cap_tw_csr, (size_t)std::max<int64_t>(b->nnz, 1));
-    if (!rc) rc = grow(&m->tw_word, &m->cap_tw_word, (size_t)std::max<int64_t>(b->nnz, 1));
+    if (!rc) rc = m->tw_csr.grow((size_t)std::max<int64_t>(b->nnz, 1));
+    if (!rc) {
+        rc = m->tw_word_own.grow((size_t)std::max<int64_t>(b->nnz, 1));
+        m->tw_word = m->tw_word_own;
+    }
     return rc;
 }
 
 int ensure_update_workspace(trlda_model *m, int B)
 {
     size_t KV = (size_t)m->K * m->V;
-    int rc = grow(&m->lambda_prime, &m->cap_lambda_prime, KV);
-    if (!rc) rc = grow(&m->sstats, &m->cap_sstats, KV);
-    if (!rc) rc = grow(&m->wordcounts, &m->cap_wordcounts, (size_t)m->V);
-    if (!rc) rc = grow(&m->gamma, &m->cap_gamma, (size_t)std::max(B, 1) * m->K);
+    int rc = m->lambda_prime.grow(KV);
+    if (!rc) rc = m->sstats.grow(KV);
+    if (!rc) rc = m->wordcounts.grow((size_t)m->V);
+    if (!rc) rc = m->gamma.grow((size_t)std::max(B, 1) * m->K);
     return rc;
 }
 
@@ -974,7 +975,7 @@ int draw_gamma_ahead(trlda_model *m, long long total, long long lo, long long hi
         HIP_TRY(hipEventCreateWithFlags(&m->ev_draw, hipEventDisableTiming));
     }
     const int which = m->gamma0_src == m->gspec[0] && m->gspec[0] ? 1 : 0;
-    int rc = grow(&m->gspec[which], &m->cap_gspec[which], (size_t)(hi - lo));
+    int rc = m->gspec[which].grow((size_t)(hi - lo));
     if (rc)
         return rc;
     HIP_TRY(hipEventRecord(m->ev_main, m->stream));
@@ -1290,10 +1291,10 @@ int launch_sstats_update(trlda_model *m, const trlda_batch *b, EstepOut &out)
         // the order that keeps concurrently running workgroups on the same documents)
         vl.task = reinterpret_cast<const int4 *>(out.sliced ? b->vl_task : b->vl_task_tiled);
         vl.word = reinterpret_cast<const int4 *>(b->vl_word);
-        int rc0 = grow(&m->seg_partial, &m->cap_seg_partial, std::max<size_t>((size_t)vl.n_tasks * K, 1));
-        if (!rc0 && (size_t)b->n_vl > m->cap_seg_counter) {
-            rc0 = grow(&m->seg_counter, &m->cap_seg_counter, (size_t)b->n_vl + 64);
-            if (!rc0 && hipMemsetAsync(m->seg_counter, 0, m->cap_seg_counter * sizeof(unsigned int), m->stream) != hipSuccess)
+        int rc0 = m->seg_partial.grow(std::max<size_t>((size_t)vl.n_tasks * K, 1));
+        if (!rc0 && (size_t)b->n_vl > m->seg_counter.cap()) {
+            rc0 = m->seg_counter.grow((size_t)b->n_vl + 64);
+            if (!rc0 && hipMemsetAsync(m->seg_counter, 0, m->seg_counter.cap() * sizeof(unsigned int), m->stream) != hipSuccess)
                 rc0 = fail(TRLDA_ERR_HIP, "hipMemsetAsync failed");
         }
         if (rc0)
@@ -1418,13 +1419,13 @@ int ensure_deferred_workspace(trlda_model *m, const trlda_batch *b, int which)
 {
     const size_t rows = (size_t)std::max(b->B, 1) + 1, K = (size_t)m->K;
     int rc = TRLDA_OK;
-    if (rows * K > m->dfr_cap_docs[which] || !m->dfr_epg_base[which]) {
-        rc = grow(&m->dfr_epg_base[which], &m->dfr_cap_docs[which], rows * K);
+    if (rows * K > m->dfr_epg_base[which].cap() || !m->dfr_epg_base[which]) {
+        rc = m->dfr_epg_base[which].grow(rows * K);
         if (!rc)                                     // row -1 is zero (estep_merged.h)
             HIP_TRY(hipMemsetAsync(m->dfr_epg_base[which], 0, K * sizeof(double), m->stream));
     }
     if (!rc)
-        rc = grow(&m->dfr_tw[which], &m->dfr_cap_tw[which], (size_t)std::max<int64_t>(b->nnz, 1));
+        rc = m->dfr_tw[which].grow((size_t)std::max<int64_t>(b->nnz, 1));
     return rc;
 }
 
@@ -1503,7 +1504,7 @@ int dp_prepare(trlda_model *m, const trlda_batch *b, DpContext *dp)
         m->dp_gather_direct = static_cast<double *>(m->direct.region);   // (the half: per E-step)
     } else {
         m->dp_gather_direct = nullptr;
-        rc = grow(&m->dp_gather_own, &m->cap_dp_gather, std::max<size_t>(dp->slot * (size_t)world, 1));
+        rc = m->dp_gather_own.grow(std::max<size_t>(dp->slot * (size_t)world, 1));
         if (rc)
             return rc;
     }
@@ -1703,6 +1704,27 @@ int rowsum_blocks(int V, int most, int &wpb)
     return (V + wpb - 1) / wpb;
 }
 
+// The K row sums of lambda formed from lambda itself on the model's stream, into the model's one
+// scratch for them (the sampling and evaluation entry points: no E-step's preamble has left any).
+// The block count and the order of summation depend on K and V only.
+int lambda_rowsums(trlda_model *m, const double **rs)
+{
+    const int K = m->K, V = m->V;
+    auto &g = m->rowsums;
+    int wpb = 0;
+    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks,
+                                wpb);
+    int rc = g.partial.grow((size_t)G * K);
+    if (!rc) rc = g.rs.grow((size_t)K);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K,
+                       V, wpb, m->lambda, g.partial);
+    HIP_TRY(hipGetLastError());
+    *rs = g.rs;
+    return combine_rowsums(m, g.partial, G, nullptr, g.rs);
+}
+
 // f(std::integral_constant<int, ks>) for the single-orientation body's ks = 1..8 (estep_wide.h;
 // beyond 8: 8)
 template <int KS = 1, class F>
@@ -1736,12 +1758,12 @@ bool stats_stage_fits(const trlda_model *m, const trlda_batch *x)
 }
 
 // diagnostics (TRLDA_MERGED_STAMPS=1): the time stamps of a merged or deferred launch, n of them
-unsigned long long *launch_stamps(unsigned long long *&buf, size_t n)
+unsigned long long *launch_stamps(DevBuf<unsigned long long> &buf, size_t n)
 {
     static const bool want_stamps = std::getenv("TRLDA_MERGED_STAMPS") != nullptr;
-    if (want_stamps && !buf && dev_alloc(&buf, n) == TRLDA_OK)
+    if (want_stamps && !buf && buf.alloc(n) == TRLDA_OK)
         (void)hipMemset(buf, 0, n * sizeof(unsigned long long));
-    return want_stamps ? buf : nullptr;
+    return want_stamps ? buf.get() : nullptr;
 }
 
 // What an E-step call launches, decided before anything is launched (estep_begin).  db: the
@@ -2140,9 +2162,9 @@ int next_preamble_args(trlda_model *m, const EstepPlan &p, int cur_buf, trlda::P
     int rc = 0;
     if (!m->eeb_pp[0]) {
         for (int i = 0; i < 3 && !rc; ++i) {
-            rc = dev_alloc(&m->eeb_pp[i], KV);
-            if (!rc) rc = dev_alloc(&m->partial_pp[i], (size_t)kRowsumBlocks * K);
-            if (!rc) rc = dev_alloc(&m->scale_pp[i], 3 * (size_t)K);
+            rc = m->eeb_pp[i].alloc(KV);
+            if (!rc) rc = m->partial_pp[i].alloc((size_t)kRowsumBlocks * K);
+            if (!rc) rc = m->scale_pp[i].alloc(3 * (size_t)K);
             if (!rc && hipMemsetAsync(m->eeb_pp[i], 0, KV * sizeof(double), m->stream) != hipSuccess)
                 rc = fail(TRLDA_ERR_HIP, "hipMemsetAsync failed");
         }
@@ -2312,7 +2334,7 @@ int aux_args(trlda_model *m, const trlda_batch *b, const EstepPlan &p, const trl
         if (cpw <= kAuxMaxChunks && n_draw < 256 &&
             !(rc = rng_aux_matrices(m->device, (long long)cpw * kAuxChunk, &mt_stride)) &&
             !(rc = rng_aux_matrices(m->device, total, &mt_total)) && mt_stride && mt_total &&
-            !(rc = grow(&m->gspec[which], &m->cap_gspec[which], (size_t)total))) {
+            !(rc = m->gspec[which].grow((size_t)total))) {
             aux.draw.n = n_draw;
             aux.draw.passes = 100; aux.draw.cpw = cpw;
             aux.draw.total = total; aux.draw.divisor = 100.;
@@ -2374,7 +2396,7 @@ int launch_reg_family(trlda_model *m, const trlda_batch *b, const EstepPlan &p, 
     a.pad_meta = db->pad_meta;
     a.pad_ids = db->pad_ids;
     if (p.split) {
-        if ((rc = grow(&m->xbuf, &m->cap_xbuf, p.xcount)))
+        if ((rc = m->xbuf.grow(p.xcount)))
             return rc;
         if ((rc = ensure_xerr(m)))
             return rc;
@@ -2923,10 +2945,8 @@ int rng_device_matrices(int device, int L, const uint32_t **out)
             for (int i = 0; i < 31; ++i)
                 for (int j = 0; j < 31; ++j)
                     h[n + mtx * 961 + (size_t)j * 31 + i] = h[mtx * 961 + (size_t)i * 31 + j];
-        uint32_t *d = nullptr;
-        int rc = dev_alloc(&d, h.size());
-        if (rc)
-            return rc;
+        uint32_t *d = nullptr;                           // (the process's: cached for its life, never freed)
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), h.size() * sizeof(uint32_t)));
         HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         it = all.emplace(key, d).first;
     }
@@ -2954,10 +2974,8 @@ int rng_aux_matrices(int device, long long L, const uint32_t **out)
             for (int i = 0; i < 31; ++i)
                 for (int j = 0; j < 31; ++j)
                     t[mtx * 961 + (size_t)j * 31 + i] = h[mtx * 961 + (size_t)i * 31 + j];
-        uint32_t *d = nullptr;
-        int rc = dev_alloc(&d, t.size());
-        if (rc)
-            return rc;
+        uint32_t *d = nullptr;                           // (the process's, as above)
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), t.size() * sizeof(uint32_t)));
         HIP_TRY(hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         it = all.emplace(key, d).first;
     }
@@ -2976,10 +2994,8 @@ int sample_gamma_on_device(trlda_model *m, long long total, int passes, double d
         trlda_host::rng_speculation_cancel();        // a draw in its turn: nothing may be ahead of it
     // a draw made ahead runs on the draw stream with scratch of its own
     const hipStream_t stream = ahead ? m->draw_stream : m->stream;
-    uint32_t *&win = ahead ? m->rng_win2 : m->rng_win;
-    size_t &cap_win = ahead ? m->cap_rng_win2 : m->cap_rng_win;
-    double *&vbuf = ahead ? m->rng_vbuf2 : m->rng_vbuf;
-    size_t &cap_vbuf = ahead ? m->cap_rng_vbuf2 : m->cap_rng_vbuf;
+    DevBuf<uint32_t> &win = ahead ? m->rng_win2 : m->rng_win;
+    DevBuf<double> &vbuf = ahead ? m->rng_vbuf2 : m->rng_vbuf;
     if (e_hi < 0)
         e_hi = total;
     constexpr int T = trlda::kRngThreads;
@@ -3007,8 +3023,8 @@ int sample_gamma_on_device(trlda_model *m, long long total, int passes, double d
     const bool fused_off = fused_env && fused_env[0] == '0';
     const bool fused = !fused_off && walk && L == trlda::kRngSegmentTiny && passes <= trlda::kRngFusedPasses &&
                        group == passes && e_hi > e_lo;
-    if (!rc) rc = grow(&win, &cap_win, (size_t)(fused ? 32 : 31) * (size_t)S + (walk ? (size_t)31 * (size_t)Sm : 0));
-    if (!rc && !fused) rc = grow(&vbuf, &cap_vbuf, (size_t)group * (size_t)total);
+    if (!rc) rc = win.grow((size_t)(fused ? 32 : 31) * (size_t)S + (walk ? (size_t)31 * (size_t)Sm : 0));
+    if (!rc && !fused) rc = vbuf.grow((size_t)group * (size_t)total);
     if (rc)
         return rc;
     uint32_t *mwin = walk ? win + (size_t)(fused ? 32 : 31) * (size_t)S : win;  // where the matrix level writes
@@ -3826,13 +3842,15 @@ int model_create(trlda_model **out, int device, int K, int V, int stream_priorit
         m->alpha = lane_of->alpha;
         m->lane_owner = lane_of;
     } else {
-        rc = dev_alloc(&m->lambda, KV);
-        if (!rc) rc = dev_alloc(&m->alpha, (size_t)K);
+        rc = m->lambda_own.alloc(KV);
+        if (!rc) rc = m->alpha_own.alloc((size_t)K);
+        m->lambda = m->lambda_own;
+        m->alpha = m->alpha_own;
     }
-    if (!rc) rc = dev_alloc(&m->eeb, KV);
-    if (!rc) rc = dev_alloc(&m->psi_sum, 3 * (size_t)K);   // psi(row sums), the row sums, exp(-psi)
-    if (!rc) rc = dev_alloc(&m->partial, (size_t)kMaxRowsumBlocks * K);
-    if (!rc) rc = dev_alloc(&m->counter, 1);
+    if (!rc) rc = m->eeb.alloc(KV);
+    if (!rc) rc = m->psi_sum.alloc(3 * (size_t)K);   // psi(row sums), the row sums, exp(-psi)
+    if (!rc) rc = m->partial.alloc((size_t)kMaxRowsumBlocks * K);
+    if (!rc) rc = m->counter.alloc(1);
     if (!rc && adopt) {
         m->own_stream = adopt;
         m->stream = adopt;
@@ -3856,26 +3874,22 @@ int model_create(trlda_model **out, int device, int K, int V, int stream_priorit
             ls.own.insert(m->own_stream);
         }
     }
-    if (!rc) rc = dev_alloc(&m->rs_full, (size_t)K);
-    if (!rc) rc = dev_alloc(&m->rs_static, (size_t)K);
-    if (!rc) rc = dev_alloc(&m->upd_partial, (size_t)(kUpdShortBlocks + kUpdLongBlocks + kUpdVlRows) * K);
-    if (!rc) rc = dev_alloc(&m->carry_out, (size_t)kCarryBlocks * K);
-    if (!rc) rc = dev_alloc(&m->upd_groups, (size_t)kUpdGroups * K);
-    if (!rc) {
-        void *p = nullptr;
-        // (+1: the row-sum workgroups' counter of a prefetched preamble)
-        if (hipMalloc(&p, (kUpdGroups + 1) * sizeof(unsigned int)) != hipSuccess ||
-            hipMemset(p, 0, (kUpdGroups + 1) * sizeof(unsigned int)) != hipSuccess)
-            rc = fail(TRLDA_ERR_HIP, "hipMalloc failed");
-        m->group_counter = static_cast<unsigned int *>(p);
-    }
-    if (!rc) rc = dev_alloc(&m->scale_comb, 3 * (size_t)K);
-    if (!rc) rc = dev_alloc(&m->sync_counters, 64);          // [0], [1]: merged launch; [32]: deferred helpers
+    if (!rc) rc = m->rs_full.alloc((size_t)K);
+    if (!rc) rc = m->rs_static.alloc((size_t)K);
+    if (!rc) rc = m->upd_partial.alloc((size_t)(kUpdShortBlocks + kUpdLongBlocks + kUpdVlRows) * K);
+    if (!rc) rc = m->carry_out.alloc((size_t)kCarryBlocks * K);
+    if (!rc) rc = m->upd_groups.alloc((size_t)kUpdGroups * K);
+    // (+1: the row-sum workgroups' counter of a prefetched preamble)
+    if (!rc) rc = m->group_counter.alloc(kUpdGroups + 1);
+    if (!rc && hipMemset(m->group_counter, 0, (kUpdGroups + 1) * sizeof(unsigned int)) != hipSuccess)
+        rc = fail(TRLDA_ERR_HIP, "hipMemset failed");
+    if (!rc) rc = m->scale_comb.alloc(3 * (size_t)K);
+    if (!rc) rc = m->sync_counters.alloc(64);          // [0], [1]: merged launch; [32]: deferred helpers
     if (!rc && hipMemset(m->sync_counters, 0, 64 * sizeof(unsigned int)) != hipSuccess)
         rc = fail(TRLDA_ERR_HIP, "hipMemset failed");
     {
         const size_t n_flags = (size_t)(trlda::kMergedMaxHelpers + trlda::kMergedMaxDocWgs) * trlda::kMergedFlagStride;
-        if (!rc) rc = dev_alloc(&m->sync_flags, n_flags);
+        if (!rc) rc = m->sync_flags.alloc(n_flags);
         if (!rc && hipMemset(m->sync_flags, 0, n_flags * sizeof(unsigned int)) != hipSuccess)
             rc = fail(TRLDA_ERR_HIP, "hipMemset failed");
     }
@@ -3935,42 +3949,15 @@ int trlda_model_destroy(trlda_model *m)
                 if (m->lane_span[p][q])
                     (void)hipEventDestroy(m->lane_span[p][q]);
         }
-        if (m->lane_owner) {                         // a lane: lambda and alpha are its owner's
-            m->lambda = nullptr;
-            m->alpha = nullptr;
-        }
         if (m->draw_stream)
             (void)hipStreamSynchronize(m->draw_stream);
-        (void)hipFree(m->lambda); (void)hipFree(m->alpha); (void)hipFree(m->eeb); (void)hipFree(m->psi_sum);
-        (void)hipFree(m->xbuf);
         if (m->xerr_host)
             (void)hipHostFree(const_cast<int *>(m->xerr_host));
         if (m->eb.host)
             (void)hipHostFree(m->eb.host);
         if (m->eb.event)
             (void)hipEventDestroy(m->eb.event);
-        (void)hipFree(m->partial); (void)hipFree(m->counter); (void)hipFree(m->epg_base); (void)hipFree(m->tw_csr);
-        (void)hipFree(m->sync_counters); (void)hipFree(m->sync_flags); (void)hipFree(m->scale_comb);
-        (void)hipFree(m->seg_partial); (void)hipFree(m->seg_counter);
-        (void)hipFree(m->tw_word); (void)hipFree(m->dp_gather_own); (void)trlda_model_dp_direct_close(m); (void)hipFree(m->lambda_prime); (void)hipFree(m->sstats); (void)hipFree(m->gamma);
-        (void)hipFree(m->wordcounts); (void)hipFree(m->rs_full); (void)hipFree(m->rs_static);
-        (void)hipFree(m->upd_partial); (void)hipFree(m->ada_gradient); (void)hipFree(m->reduce_out);
-        (void)hipFree(m->carry_out); (void)hipFree(m->upd_groups); (void)hipFree(m->group_counter);
-        (void)hipFree(m->iters); (void)hipFree(m->rng_win); (void)hipFree(m->rng_vbuf);
-        (void)hipFree(m->gibbs.eeb); (void)hipFree(m->gibbs.partial); (void)hipFree(m->gibbs.psi_sum);
-        (void)hipFree(m->gibbs.cnt); (void)hipFree(m->gibbs.z); (void)hipFree(m->gibbs.tokens);
-        (void)hipFree(m->gibbs.tok_off); (void)hipFree(m->gibbs.order); (void)hipFree(m->gibbs.flag);
-        (void)hipFree(m->gibbs.theta_in); (void)hipFree(m->gibbs.theta); (void)hipFree(m->gibbs.sstats);
-        (void)hipFree(m->gibbs.rs); (void)hipFree(m->gibbs.mpart); (void)hipFree(m->gibbs.nonpos);
-        (void)hipFree(m->sample.part); (void)hipFree(m->sample.pre); (void)hipFree(m->sample.indptr);
-        (void)hipFree(m->sample.ids); (void)hipFree(m->sample.theta);
-        (void)hipFree(m->marginal.partial); (void)hipFree(m->marginal.rs);
-        (void)hipFree(m->l2r.partial); (void)hipFree(m->l2r.rs); (void)hipFree(m->l2r.asum);
-        (void)hipFree(m->l2r.p); (void)hipFree(m->l2r.out); (void)hipFree(m->l2r.tokens);
-        (void)hipFree(m->l2r.off); (void)hipFree(m->l2r.order); (void)hipFree(m->l2r.z);
-        (void)hipFree(m->l2r.flag);
-        (void)hipFree(m->wordtopics.partial); (void)hipFree(m->wordtopics.rs);
-        (void)hipFree(m->wordtopics.topics); (void)hipFree(m->wordtopics.probs);
+        (void)trlda_model_dp_direct_close(m);
         // a gamma0 drawn ahead that nobody will use: the host stream goes back to its turn
         if (m->spec.valid)
             trlda_host::rng_speculation_cancel_if(m->spec.token);
@@ -3981,8 +3968,6 @@ int trlda_model_destroy(trlda_model *m)
             (void)hipEventDestroy(m->ev_draw);
             (void)hipStreamDestroy(m->draw_stream);
         }
-        (void)hipFree(m->gspec[0]); (void)hipFree(m->gspec[1]);
-        (void)hipFree(m->rng_win2); (void)hipFree(m->rng_vbuf2);
         for (int i = 0; i < 2; ++i) {
             if (m->stage[i])
                 (void)hipHostFree(m->stage[i]);
@@ -3991,12 +3976,6 @@ int trlda_model_destroy(trlda_model *m)
         }
         for (auto &e : m->ev_pool)
             (void)hipEventDestroy(e);
-        for (int i = 0; i < 3; ++i) {
-            (void)hipFree(m->eeb_pp[i]); (void)hipFree(m->partial_pp[i]); (void)hipFree(m->scale_pp[i]);
-        }
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(m->dfr_epg_base[i]); (void)hipFree(m->dfr_tw[i]);
-        }
         if (m->own_stream) {
             (void)hipStreamSynchronize(m->own_stream);
             // the recycled batch allocations whose last reader ran on this stream: their work is
@@ -4007,10 +3986,11 @@ int trlda_model_destroy(trlda_model *m)
             ls.own.erase(m->own_stream);
             (void)hipStreamDestroy(m->own_stream);
         }
-
     }
     if (m->pending.valid)
         const_cast<trlda_batch *>(m->pending.batch)->pending_in = nullptr;
+    // the device buffers go with the model (DevBuf).  Every stream it used has been synchronised
+    // above, so it does not matter that they are freed after the streams are destroyed
     delete m;
     return TRLDA_OK;
 }
@@ -4931,7 +4911,7 @@ int trlda_model_estep_host(trlda_model *m, const trlda_batch *b, double *gamma, 
     const size_t sbytes = (size_t)m->K * m->V * sizeof(double);
     int32_t *iters_dev = nullptr;
     if (iters_out) {
-        rc = grow(&m->iters, &m->cap_iters, (size_t)std::max(b->B, 1));
+        rc = m->iters.grow((size_t)std::max(b->B, 1));
         if (rc)
             return rc;
         iters_dev = m->iters;
@@ -4988,7 +4968,7 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     if (rc)
         return rc;
     const int G = (int)std::min<size_t>((KV + kDenseThreads - 1) / kDenseThreads, 1024);
-    rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)G + 2 * (size_t)B);
+    rc = m->reduce_out.grow(2 * (size_t)G + 2 * (size_t)B);
     if (rc)
         return rc;
     double *out = m->reduce_out;
@@ -5070,7 +5050,7 @@ int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_bat
     rc = estep_device(m, o, m->gamma, m->sstats, max_iter, threshold, nullptr);
     if (rc)
         return rc;
-    rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)B);
+    rc = m->reduce_out.grow(2 * (size_t)B);
     if (!rc)
         rc = batch_begin(m, h);
     if (rc)
@@ -5162,7 +5142,7 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
     if (m->eb.active)
         return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
                                    "yet): trlda_model_online_eb_finish first");
-    const int K = m->K, V = m->V, B = b->B;
+    const int K = m->K, B = b->B;
     if (trlda::marginal_lds_doubles(K) > (size_t)trlda::kMarginalLdsDoubles || trlda::marginal_waves(K) < 1)
         return fail(TRLDA_ERR_ARG, "num_topics too large for the marginal kernel's LDS layout");
     const uint64_t key = trlda_host::rng_draw_key();   // (one per valid call, whatever B is)
@@ -5181,28 +5161,18 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
     }
     if (rc)
         return rc;
-    auto &g = m->marginal;
-    int wpb = 0;
-    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks,
-                                wpb);
-    rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
-    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
-    if (!rc) rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)B);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K,
-                       V, wpb, m->lambda, g.partial);
-    HIP_TRY(hipGetLastError());
-    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
+    const double *rs = nullptr;
+    rc = m->reduce_out.grow(2 * (size_t)B);
+    if (!rc) rc = lambda_rowsums(m, &rs);
     if (rc)
         return rc;
     double *out = m->reduce_out;
     const double *gamma_dev = vi ? m->gamma : nullptr;
     if (K > trlda::kMarginalRegMaxK)
-        rc = launch_marginal<0>(m, b, num_samples, key, g.rs, gamma_dev, out);
+        rc = launch_marginal<0>(m, b, num_samples, key, rs, gamma_dev, out);
     else
         rc = ks_dispatch((K + trlda::kWave - 1) / trlda::kWave, [&](auto kpl) {
-            return launch_marginal<decltype(kpl)::value>(m, b, num_samples, key, g.rs, gamma_dev, out);
+            return launch_marginal<decltype(kpl)::value>(m, b, num_samples, key, rs, gamma_dev, out);
         });
     if (rc)
         return rc;
@@ -5284,20 +5254,19 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     if (m->eb.active)
         return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
                                    "yet): trlda_model_online_eb_finish first");
-    const int K = m->K, V = m->V, B = b->B, R = num_particles;
+    const int K = m->K, B = b->B, R = num_particles;
     if (B <= 0) {
         (void)trlda_host::rng_draw_key();              // (one per valid call, whatever B is)
         return TRLDA_OK;
     }
     auto &g = m->l2r;
     rc = batch_begin(m, b);
-    if (!rc) rc = grow(&g.tokens, &g.cap_tokens, (size_t)B);
-    if (!rc) rc = grow(&g.off, &g.cap_off, (size_t)B);
-    if (!rc) rc = grow(&g.order, &g.cap_order, (size_t)B);
-    if (!rc) rc = grow(&g.out, &g.cap_out, (size_t)B);
-    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
-    if (!rc && !g.asum) rc = dev_alloc(&g.asum, 1);
-    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    if (!rc) rc = g.tokens.grow((size_t)B);
+    if (!rc) rc = g.off.grow((size_t)B);
+    if (!rc) rc = g.order.grow((size_t)B);
+    if (!rc) rc = g.out.grow((size_t)B);
+    if (!rc && !g.asum) rc = g.asum.alloc(1);
+    if (!rc && !g.flag) rc = g.flag.alloc(1);
     if (rc)
         return rc;
     // the plan: tokens per document, the longest first, groups of documents under the budget
@@ -5332,21 +5301,15 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     starts.push_back(B);
     const uint64_t key = trlda_host::rng_draw_key();   // (one per call that passes its checks)
     const size_t cells = (size_t)std::max<int64_t>(most, 1) * (size_t)R;
-    rc = grow(&g.p, &g.cap_p, cells);
-    if (!rc && resample) rc = grow(&g.z, &g.cap_z, cells);
-    int wpb = 0;
-    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : kRowsumBlocks, wpb);
-    if (!rc) rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
+    rc = g.p.grow(cells);
+    if (!rc && resample) rc = g.z.grow(cells);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(g.off, off.data(), (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(g.order, order.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
-    hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K, V, wpb,
-                       m->lambda, g.partial);
-    HIP_TRY(hipGetLastError());
-    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
-    if (rc)
+    const double *rs = nullptr;
+    if ((rc = lambda_rowsums(m, &rs)))
         return rc;
     hipLaunchKernelGGL(l2r_alpha_sum_kernel, dim3(1), dim3(kWave), 0, m->stream, K, m->alpha, g.asum);
     HIP_TRY(hipGetLastError());
@@ -5355,7 +5318,7 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
     a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
     a.off = g.off; a.tokens = g.tokens;
-    a.lambda = m->lambda; a.rowsum = g.rs; a.alpha = m->alpha; a.asum = g.asum;
+    a.lambda = m->lambda; a.rowsum = rs; a.alpha = m->alpha; a.asum = g.asum;
     a.z = g.z; a.p = g.p; a.flag = g.flag;
     const int kpl = (K + kWave - 1) / kWave;
     for (size_t gi = 0; gi + 1 < starts.size(); ++gi) {
@@ -5432,25 +5395,14 @@ int word_topics_checks(const trlda_model *m, const trlda_batch *b, int top_n)
 int word_topics_device(trlda_model *m, const trlda_batch *b, int top_n, const double *gamma_dev,
                        int32_t *topics_dev, double *probs_dev)
 {
-    const int K = m->K, V = m->V;
-    auto &g = m->wordtopics;
-    int wpb = 0;
-    const int G = rowsum_blocks(V, (size_t)K * V >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks,
-                                wpb);
-    int rc = grow(&g.partial, &g.cap_partial, (size_t)G * K);
-    if (!rc) rc = grow(&g.rs, &g.cap_rs, (size_t)K);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K,
-                       V, wpb, m->lambda, g.partial);
-    HIP_TRY(hipGetLastError());
-    rc = combine_rowsums(m, g.partial, G, nullptr, g.rs);
-    if (rc)
+    const int K = m->K;
+    const double *rs = nullptr;
+    if (int rc = lambda_rowsums(m, &rs))
         return rc;
     if (K > trlda::kWordTopicsRegMaxK)
-        return launch_word_topics<0>(m, b, top_n, g.rs, gamma_dev, topics_dev, probs_dev);
+        return launch_word_topics<0>(m, b, top_n, rs, gamma_dev, topics_dev, probs_dev);
     return ks_dispatch((K + trlda::kWave - 1) / trlda::kWave, [&](auto kpl) {
-        return launch_word_topics<decltype(kpl)::value>(m, b, top_n, g.rs, gamma_dev, topics_dev, probs_dev);
+        return launch_word_topics<decltype(kpl)::value>(m, b, top_n, rs, gamma_dev, topics_dev, probs_dev);
     });
 }
 
@@ -5512,8 +5464,8 @@ int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma,
     auto &g = m->wordtopics;
     const size_t cells = (size_t)b->nnz * (size_t)top_n;
     if (cells) {
-        rc = grow(&g.topics, &g.cap_topics, cells);
-        if (!rc) rc = grow(&g.probs, &g.cap_probs, cells);
+        rc = g.topics.grow(cells);
+        if (!rc) rc = g.probs.grow(cells);
         if (rc)
             return rc;
     }
@@ -5560,11 +5512,12 @@ int trlda_model_top_words(trlda_model *m, int top_n, int32_t *words_out)
     const size_t c2 = (c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;   // after the second
     // one allocation: the first level's candidates, the later levels' (ping-pong), the ids
     const size_t off_b = (size_t)K * c1, cap = off_b + (size_t)K * c2;
-    DevTemp keys, ids;
-    HIP_TRY(hipMalloc(&keys.p, cap * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&ids.p, (cap + (size_t)K * n) * sizeof(int32_t)));
-    uint64_t *kb = static_cast<uint64_t *>(keys.p);
-    int32_t *ib = static_cast<int32_t *>(ids.p);
+    DevBuf<uint64_t> keys;
+    DevBuf<int32_t> ids;
+    if ((rc = keys.alloc(cap)) || (rc = ids.alloc(cap + (size_t)K * n)))
+        return rc;
+    uint64_t *kb = keys;
+    int32_t *ib = ids;
     int32_t *wout = ib + cap;
     const size_t lds = (size_t)trlda::kTopnTileTopics * trlda::kTopnTileStride * sizeof(uint64_t);
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topn_tile_kernel), lds)))
@@ -5604,11 +5557,11 @@ struct trlda_cooc {
     trlda_model *model = nullptr;
     int T = 0, N = 0, U = 0;
     int block_docs = 64;                 // documents per block: U x block_docs / 8 bytes of bit rows
-    int32_t *slot_of_word = nullptr;     // V: the slot of a listed word, -1 for the others
-    int32_t *slot_of = nullptr;          // T x N: the slot of word (t, i)
-    unsigned long long *bits = nullptr;  // U x ceil(block_docs / 64)
-    long long *doc_freq = nullptr;       // U
-    long long *co = nullptr;             // T x N x N, i < j filled
+    DevBuf<int32_t> slot_of_word;        // V: the slot of a listed word, -1 for the others
+    DevBuf<int32_t> slot_of;             // T x N: the slot of word (t, i)
+    DevBuf<unsigned long long> bits;     // U x ceil(block_docs / 64)
+    DevBuf<long long> doc_freq;          // U
+    DevBuf<long long> co;                // T x N x N, i < j filled
     std::vector<int32_t> slot_host;      // T x N
     int64_t num_docs = 0;
 };
@@ -5617,18 +5570,6 @@ namespace {
 
 constexpr size_t kCoocBitBytes = size_t(64) << 20;   // bit rows of a block: at most this, or 8 U bytes
 constexpr int kCoocMaxRowWords = 1024;               // (65 536 documents per block)
-
-void cooc_free(trlda_cooc *c)
-{
-    if (!c)
-        return;
-    (void)hipFree(c->slot_of_word);
-    (void)hipFree(c->slot_of);
-    (void)hipFree(c->bits);
-    (void)hipFree(c->doc_freq);
-    (void)hipFree(c->co);
-    delete c;
-}
 
 }  // namespace
 
@@ -5670,11 +5611,11 @@ int trlda_cooc_create(trlda_model *m, const int32_t *words, int T, int N, trlda_
     const size_t row_words = std::max<size_t>(1, std::min<size_t>(kCoocMaxRowWords, kCoocBitBytes / (8 * (size_t)U)));
     c->block_docs = (int)(64 * row_words);
     c->slot_host = std::move(slot_host);
-    rc = dev_alloc(&c->slot_of_word, (size_t)V);
-    if (!rc) rc = dev_alloc(&c->slot_of, TN);
-    if (!rc) rc = dev_alloc(&c->bits, (size_t)U * row_words);
-    if (!rc) rc = dev_alloc(&c->doc_freq, (size_t)U);
-    if (!rc) rc = dev_alloc(&c->co, TN * N);
+    rc = c->slot_of_word.alloc((size_t)V);
+    if (!rc) rc = c->slot_of.alloc(TN);
+    if (!rc) rc = c->bits.alloc((size_t)U * row_words);
+    if (!rc) rc = c->doc_freq.alloc((size_t)U);
+    if (!rc) rc = c->co.alloc(TN * N);
     if (!rc) {
         hipError_t e1 = hipMemcpyAsync(c->slot_of_word, slot_of_word.data(), (size_t)V * sizeof(int32_t),
                                        hipMemcpyHostToDevice, m->stream);
@@ -5689,7 +5630,7 @@ int trlda_cooc_create(trlda_model *m, const int32_t *words, int T, int N, trlda_
             rc = fail(TRLDA_ERR_HIP, "uploading the word lists failed");
     }
     if (rc) {
-        cooc_free(c);
+        delete c;
         return rc;
     }
     *out = c;
@@ -5775,7 +5716,7 @@ int trlda_cooc_destroy(trlda_cooc *c)
         return TRLDA_OK;
     if (c->model && use_device(c->model->device) == TRLDA_OK && c->model->stream)
         (void)hipStreamSynchronize(c->model->stream);    // (its kernels may still read the buffers)
-    cooc_free(c);
+    delete c;
     return TRLDA_OK;
 }
 
@@ -5789,50 +5730,36 @@ struct trlda_docindex {
     trlda_model *model = nullptr;
     int measure = 0;
     int K = 0, Kp = 0;
-    double *rows = nullptr;
-    size_t cap = 0;                      // rows the table holds
+    DevBuf<double> rows;                 // (its capacity: Kp doubles per row the table holds)
     int64_t n = 0;                       // rows in use: the next id
     int slab_rows = 0;                   // 0: kDocIndexSlabRows
-    double *qrows = nullptr, *gstage = nullptr, *cand_s = nullptr, *out_s = nullptr;
-    long long *cand_i = nullptr, *out_i = nullptr;
-    size_t cap_qrows = 0, cap_gstage = 0, cap_cand_s = 0, cap_out_s = 0, cap_cand_i = 0, cap_out_i = 0;
+    DevBuf<double> qrows, gstage, cand_s, out_s;
+    DevBuf<long long> cand_i, out_i;
 };
 
 namespace {
-
-void docindex_free(trlda_docindex *x)
-{
-    if (!x)
-        return;
-    (void)hipFree(x->rows); (void)hipFree(x->qrows); (void)hipFree(x->gstage);
-    (void)hipFree(x->cand_s); (void)hipFree(x->out_s); (void)hipFree(x->cand_i); (void)hipFree(x->out_i);
-    delete x;
-}
 
 // room for `need` rows: doubling from max(1024, first request), the rows in use copied on the
 // model's stream
 int docindex_room(trlda_docindex *x, int64_t need, int64_t first)
 {
-    if (need <= (int64_t)x->cap && x->rows)
+    const size_t held = x->rows.cap() / (size_t)x->Kp;
+    if (need <= (int64_t)held && x->rows)
         return TRLDA_OK;
-    size_t cap = x->cap ? x->cap : (size_t)std::max<int64_t>(1024, first);
+    size_t cap = held ? held : (size_t)std::max<int64_t>(1024, first);
     while ((int64_t)cap < need)
         cap *= 2;
-    double *grown = nullptr;
-    int rc = dev_alloc(&grown, cap * (size_t)x->Kp);
+    DevBuf<double> grown;
+    int rc = grown.alloc(cap * (size_t)x->Kp);
     if (rc)
         return rc;
     if (x->n > 0) {
         hipError_t e = hipMemcpyAsync(grown, x->rows, (size_t)x->n * x->Kp * sizeof(double),
                                       hipMemcpyDeviceToDevice, x->model->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(grown);
+        if (e != hipSuccess)
             return fail(TRLDA_ERR_HIP, std::string("copying the index rows: ") + hipGetErrorString(e));
-        }
     }
-    (void)hipFree(x->rows);              // (waits for the copy)
-    x->rows = grown;
-    x->cap = cap;
+    x->rows.swap(grown);                 // (the old table is freed on return, which waits for the copy)
     return TRLDA_OK;
 }
 
@@ -5904,11 +5831,11 @@ int docindex_query_device(trlda_docindex *x, const double *gamma_dev, int B, int
     const int sr = docindex_slab_rows(x);
     const int slabs = (int)((x->n + sr - 1) / sr);
     const size_t cells = (size_t)B * top_n;
-    int rc = grow(&x->qrows, &x->cap_qrows, (size_t)B * x->Kp);
-    if (!rc) rc = grow(&x->cand_s, &x->cap_cand_s, cells * slabs);
-    if (!rc) rc = grow(&x->cand_i, &x->cap_cand_i, cells * slabs);
-    if (!rc) rc = grow(&x->out_s, &x->cap_out_s, cells);
-    if (!rc) rc = grow(&x->out_i, &x->cap_out_i, cells);
+    int rc = x->qrows.grow((size_t)B * x->Kp);
+    if (!rc) rc = x->cand_s.grow(cells * slabs);
+    if (!rc) rc = x->cand_i.grow(cells * slabs);
+    if (!rc) rc = x->out_s.grow(cells);
+    if (!rc) rc = x->out_i.grow(cells);
     if (!rc) rc = docindex_launch_rows(x, gamma_dev, B, x->qrows);
     if (rc)
         return rc;
@@ -6018,7 +5945,7 @@ int trlda_docindex_add_gamma(trlda_docindex *x, const double *gamma, int B)
     int rc = check_model(x->model);
     if (rc || B == 0)
         return rc;
-    rc = grow(&x->gstage, &x->cap_gstage, count);
+    rc = x->gstage.grow(count);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(x->gstage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
@@ -6078,7 +6005,7 @@ int trlda_docindex_query_gamma(trlda_docindex *x, const double *gamma, int B, in
     int rc = check_model(x->model);
     if (rc || B == 0)
         return rc;
-    rc = grow(&x->gstage, &x->cap_gstage, count);
+    rc = x->gstage.grow(count);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(x->gstage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
@@ -6145,7 +6072,7 @@ int trlda_docindex_destroy(trlda_docindex *x)
         return TRLDA_OK;
     if (x->model && use_device(x->model->device) == TRLDA_OK && x->model->stream)
         (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
-    docindex_free(x);
+    delete x;
     return TRLDA_OK;
 }
 
@@ -6165,9 +6092,9 @@ int gibbs_plan(trlda_model *m, const trlda_batch *b)
     g.plan_batch = 0;
     const int B = b->B;
     const size_t nb = (size_t)std::max(B, 1);
-    int rc = grow(&g.tokens, &g.cap_tokens, nb);
-    if (!rc) rc = grow(&g.tok_off, &g.cap_tok_off, nb);
-    if (!rc) rc = grow(&g.order, &g.cap_order, nb);
+    int rc = g.tokens.grow(nb);
+    if (!rc) rc = g.tok_off.grow(nb);
+    if (!rc) rc = g.order.grow(nb);
     if (rc)
         return rc;
     std::vector<int64_t> tok((size_t)B), off((size_t)B);
@@ -6192,7 +6119,7 @@ int gibbs_plan(trlda_model *m, const trlda_batch *b)
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(),
                      [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
-    rc = grow(&g.z, &g.cap_z, (size_t)std::max<int64_t>(total, 1));
+    rc = g.z.grow((size_t)std::max<int64_t>(total, 1));
     if (rc)
         return rc;
     if (B > 0) {
@@ -6222,9 +6149,9 @@ int gibbs_preamble(trlda_model *m, const trlda_batch *b)
     int G = std::min(big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, std::max(1, V / 32));
     const int wpb = (V + G - 1) / G;
     G = (V + wpb - 1) / wpb;
-    int rc = grow(&g.eeb, &g.cap_eeb, KV);
-    if (!rc) rc = grow(&g.partial, &g.cap_partial, ((size_t)G + 1) * K);
-    if (!rc) rc = grow(&g.psi_sum, &g.cap_psi, 3 * (size_t)K);
+    int rc = g.eeb.grow(KV);
+    if (!rc) rc = g.partial.grow(((size_t)G + 1) * K);
+    if (!rc) rc = g.psi_sum.grow(3 * (size_t)K);
     if (rc)
         return rc;
     g.table_user = 1;
@@ -6297,9 +6224,9 @@ int gibbs_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev,
     if (g.total_tokens * (int64_t)std::max(num_samples, 1) > (int64_t)UINT32_MAX)
         return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
                                    "counters; split the batch");
-    const bool fresh_cnt = !g.cnt || g.cap_cnt < KV;
-    rc = grow(&g.cnt, &g.cap_cnt, std::max<size_t>(KV, 1));
-    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    const bool fresh_cnt = !g.cnt || g.cnt.cap() < KV;
+    rc = g.cnt.grow(std::max<size_t>(KV, 1));
+    if (!rc && !g.flag) rc = g.flag.alloc(1);
     if (rc)
         return rc;
     if (fresh_cnt)
@@ -6373,9 +6300,9 @@ int trlda_model_gibbs_host(trlda_model *m, const trlda_batch *b, double *theta, 
     auto &g = m->gibbs;
     const size_t tcount = (size_t)m->K * std::max(b->B, 1);
     const size_t KV = (size_t)m->K * m->V;
-    rc = grow(&g.theta, &g.cap_theta, tcount);
-    if (!rc && use_latents) rc = grow(&g.theta_in, &g.cap_theta_in, tcount);
-    if (!rc) rc = grow(&g.sstats, &g.cap_sstats, std::max<size_t>(KV, 1));
+    rc = g.theta.grow(tcount);
+    if (!rc && use_latents) rc = g.theta_in.grow(tcount);
+    if (!rc) rc = g.sstats.grow(std::max<size_t>(KV, 1));
     if (rc)
         return rc;
     const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
@@ -6421,8 +6348,8 @@ int gibbs_table(trlda_model *m, const trlda_batch *b, const double *rs)
     using namespace trlda;
     auto &g = m->gibbs;
     const int K = m->K;
-    int rc = grow(&g.eeb, &g.cap_eeb, std::max<size_t>((size_t)K * m->V, 1));
-    if (!rc) rc = grow(&g.psi_sum, &g.cap_psi, 3 * (size_t)K);
+    int rc = g.eeb.grow(std::max<size_t>((size_t)K * m->V, 1));
+    if (!rc) rc = g.psi_sum.grow(3 * (size_t)K);
     if (rc)
         return rc;
     g.table_user = 1;
@@ -6493,15 +6420,15 @@ int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate 
     if (g.total_tokens * (int64_t)std::max(u.num_samples, 1) > (int64_t)UINT32_MAX)
         return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
                                    "counters; split the batch");
-    const bool fresh_cnt = !g.cnt || g.cap_cnt < KV;
+    const bool fresh_cnt = !g.cnt || g.cnt.cap() < KV;
     const size_t tcount = (size_t)K * std::max(B, 1);
-    rc = grow(&g.cnt, &g.cap_cnt, std::max<size_t>(KV, 1));
-    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
-    if (!rc && !g.nonpos) rc = dev_alloc(&g.nonpos, 1);
-    if (!rc) rc = grow(&g.rs, &g.cap_rs, 2 * (size_t)K);
-    if (!rc) rc = grow(&g.mpart, &g.cap_mpart, (size_t)kGibbsMstepMaxBlocks * K);
-    if (!rc) rc = grow(&g.theta, &g.cap_theta, tcount);
-    if (!rc) rc = grow(&g.theta_in, &g.cap_theta_in, tcount);
+    rc = g.cnt.grow(std::max<size_t>(KV, 1));
+    if (!rc && !g.flag) rc = g.flag.alloc(1);
+    if (!rc && !g.nonpos) rc = g.nonpos.alloc(1);
+    if (!rc) rc = g.rs.grow(2 * (size_t)K);
+    if (!rc) rc = g.mpart.grow((size_t)kGibbsMstepMaxBlocks * K);
+    if (!rc) rc = g.theta.grow(tcount);
+    if (!rc) rc = g.theta_in.grow(tcount);
     if (rc)
         return rc;
 
@@ -6782,10 +6709,10 @@ int sample_device(trlda_model *m, int B, const int32_t *indptr_dev, int32_t *ids
     auto &g = m->gibbs;
     auto &s = m->sample;
     const int nchunk = (V + kSampleChunk - 1) / kSampleChunk;
-    int rc = grow(&g.eeb, &g.cap_eeb, KV);
-    if (!rc) rc = grow(&s.part, &s.cap_part, 2 * (size_t)K * nchunk);
-    if (!rc) rc = grow(&s.pre, &s.cap_pre, (size_t)K * std::max(B, 1));
-    if (!rc && !g.flag) rc = dev_alloc(&g.flag, 1);
+    int rc = g.eeb.grow(KV);
+    if (!rc) rc = s.part.grow(2 * (size_t)K * nchunk);
+    if (!rc) rc = s.pre.grow((size_t)K * std::max(B, 1));
+    if (!rc && !g.flag) rc = g.flag.alloc(1);
     if (rc)
         return rc;
     g.table_user = 2;
@@ -6852,9 +6779,9 @@ int trlda_model_sample_host(trlda_model *m, int B, const int32_t *indptr, int32_
     auto &s = m->sample;
     const size_t nnz = (size_t)indptr[B];
     const size_t tcount = (size_t)m->K * B;
-    rc = grow(&s.indptr, &s.cap_indptr, (size_t)B + 1);
-    if (!rc) rc = grow(&s.ids, &s.cap_ids, std::max<size_t>(nnz, 1));
-    if (!rc && theta) rc = grow(&s.theta, &s.cap_theta, std::max<size_t>(tcount, 1));
+    rc = s.indptr.grow((size_t)B + 1);
+    if (!rc) rc = s.ids.grow(std::max<size_t>(nnz, 1));
+    if (!rc && theta) rc = s.theta.grow(std::max<size_t>(tcount, 1));
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(s.indptr, indptr, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
@@ -7990,7 +7917,7 @@ int trlda_model_eb_gamma_stats_multi(trlda_model *m, void *rccl_comm, int B, con
     if (B < 0 || !out_host)
         return fail(TRLDA_ERR_ARG, "bad eb_gamma_stats arguments");
     if (B == 0) {
-        rc = grow(&m->reduce_out, &m->cap_reduce, (size_t)m->K);
+        rc = m->reduce_out.grow((size_t)m->K);
         if (rc)
             return rc;
         HIP_TRY(hipMemsetAsync(m->reduce_out, 0, (size_t)m->K * sizeof(double), m->stream));
@@ -8004,11 +7931,11 @@ int trlda_model_eb_gamma_stats_multi(trlda_model *m, void *rccl_comm, int B, con
         return TRLDA_OK;
     }
     const double *gamma = gamma_dev ? gamma_dev : m->gamma;
-    if (!gamma || (!gamma_dev && (size_t)B * m->K > m->cap_gamma))
+    if (!gamma || (!gamma_dev && (size_t)B * m->K > m->gamma.cap()))
         return fail(TRLDA_ERR_ARG, "no gamma of that size is resident in the model");
     const int K = m->K;
     const int chunks = (B + trlda::kEbDocsPerBlock - 1) / trlda::kEbDocsPerBlock;
-    rc = grow(&m->reduce_out, &m->cap_reduce, (size_t)(chunks + 1) * K);
+    rc = m->reduce_out.grow((size_t)(chunks + 1) * K);
     if (rc)
         return rc;
     constexpr int T = 256;
@@ -8042,7 +7969,7 @@ int trlda_model_eb_lambda_stats(trlda_model *m, double *sum_psi_lambda, double *
     const size_t KV = (size_t)K * m->V;
     constexpr int T = 256;
     const int G = (int)std::max<size_t>(1, std::min<size_t>((KV + 4 * T - 1) / (4 * T), 2048));
-    rc = grow(&m->reduce_out, &m->cap_reduce, (size_t)G + (size_t)K);
+    rc = m->reduce_out.grow((size_t)G + (size_t)K);
     if (rc)
         return rc;
     hipLaunchKernelGGL(trlda::eb_lambda_kernel<T>, dim3(G), dim3(T), 0, m->stream, KV, m->lambda,
@@ -8111,7 +8038,7 @@ int trlda_model_online_eb_begin(trlda_model *m, void *rccl_comm, int B_local, in
     const int G = (int)std::max<size_t>(1, std::min<size_t>((KV + 4 * T - 1) / (4 * T), 2048));
     // reduce_out: [gamma chunks | gamma sum (K)] [lambda blocks (G)]
     const size_t off_sum = (size_t)chunks * K, off_lam = off_sum + (size_t)K;
-    rc = grow(&m->reduce_out, &m->cap_reduce, off_lam + (size_t)G);
+    rc = m->reduce_out.grow(off_lam + (size_t)G);
     if (rc)
         return rc;
     const size_t hn = (size_t)K + (size_t)G + (size_t)K;
@@ -8129,7 +8056,7 @@ int trlda_model_online_eb_begin(trlda_model *m, void *rccl_comm, int B_local, in
     if (update_alpha) {
         double *sum = m->reduce_out + off_sum;
         if (B_local > 0) {
-            if ((size_t)B_local * K > m->cap_gamma || !m->gamma)
+            if ((size_t)B_local * K > m->gamma.cap() || !m->gamma)
                 return fail(TRLDA_ERR_ARG, "no gamma of that size is resident in the model");
             const size_t lds = ((size_t)K + T / trlda::kWave + 1) * sizeof(double);
             auto kern = trlda::eb_gamma_kernel<T>;
@@ -8260,14 +8187,14 @@ int trlda_model_adaptive_stats_dev(trlda_model *m, const double *sstats_dev,
         return fail(TRLDA_ERR_ARG, "bad adaptive_stats arguments");
     const size_t KV = (size_t)m->K * m->V;
     if (!m->ada_gradient) {
-        rc = dev_alloc(&m->ada_gradient, KV);                // mAdaGradient starts at zero
+        rc = m->ada_gradient.alloc(KV);                // mAdaGradient starts at zero
         if (rc)
             return rc;
         HIP_TRY(hipMemsetAsync(m->ada_gradient, 0, KV * sizeof(double), m->stream));
     }
     constexpr int T = 256;
     const int G = (int)std::max<size_t>(1, std::min<size_t>((KV + 4 * T - 1) / (4 * T), 2048));
-    rc = grow(&m->reduce_out, &m->cap_reduce, 2 * (size_t)G);
+    rc = m->reduce_out.grow(2 * (size_t)G);
     if (rc)
         return rc;
     hipLaunchKernelGGL(trlda::adaptive_kernel<T>, dim3(G), dim3(T), 0, m->stream, KV, eta, scale, tau,
@@ -8545,6 +8472,16 @@ extern "C" int trlda_debug_merged_stamps(trlda_model *m, unsigned long long *hos
     return TRLDA_OK;
 }
 
+// test hook: the device allocations DevBufs hold now, and all they have ever made, in this process
+extern "C" int trlda_debug_device_buffers(long long *live, long long *total)
+{
+    if (!live || !total)
+        return fail(TRLDA_ERR_ARG, "live / total is NULL");
+    *live = g_devbuf_live.load();
+    *total = g_devbuf_total.load();
+    return TRLDA_OK;
+}
+
 // diagnostics: copy out one of the model's intermediate buffers of the last E-step
 //   0  exp(psi(lambda)) / exp E[log beta] as the last call's kernels read it (K x V)
 //   1  the documents' exp E[log theta] rows (count values)
@@ -8555,7 +8492,7 @@ extern "C" int trlda_debug_peek(trlda_model *m, int which, double *host, size_t 
     if (!m || !host)
         return TRLDA_ERR_ARG;
     const double *src = which == 0 ? m->eeb_cur : which == 1 ? m->epg : which == 2 ? m->tw_word
-                        : which == 3 ? m->sstats : nullptr;
+                        : which == 3 ? m->sstats.get() : nullptr;
     if (!src)
         return TRLDA_ERR_ARG;
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -8620,12 +8557,10 @@ int trlda_debug_digamma(int device, int n, double c, const double *x, double *ps
         return rc;
     if (n <= 0 || !x || !psi || !epsi || !epsi_lean || !eminus)
         return fail(TRLDA_ERR_ARG, "bad digamma table arguments");
-    double *d = nullptr;
-    rc = dev_alloc(&d, (size_t)n * 5);
-    if (rc)
+    DevBuf<double> buf;
+    if ((rc = buf.alloc((size_t)n * 5)))
         return rc;
-    DevTemp guard;
-    guard.p = d;
+    double *d = buf;
     const size_t bytes = (size_t)n * sizeof(double);
     HIP_TRY(hipMemcpy(d, x, bytes, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(trlda::digamma_table_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, n,
@@ -8645,12 +8580,10 @@ int trlda_debug_fold16(int device, const double *in, double *out16, double *out4
         return rc;
     if (!in || !out16 || !out4 || !out2)
         return fail(TRLDA_ERR_ARG, "bad fold table arguments");
-    double *d = nullptr;
-    rc = dev_alloc(&d, 64 * 16 + 3 * 64);
-    if (rc)
+    DevBuf<double> buf;
+    if ((rc = buf.alloc(64 * 16 + 3 * 64)))
         return rc;
-    DevTemp guard;
-    guard.p = d;
+    double *d = buf;
     HIP_TRY(hipMemcpy(d, in, 64 * 16 * sizeof(double), hipMemcpyHostToDevice));
     double *o = d + 64 * 16;
     hipLaunchKernelGGL(trlda::debug_fold16_kernel, dim3(1), dim3(64), 0, nullptr, d, o, o + 64,
@@ -8695,12 +8628,10 @@ int trlda_polygamma_host(int n, int64_t count, const double *x, double *y, int d
     int rc = use_device(device);
     if (rc || count == 0)
         return rc;
-    double *d = nullptr;
-    rc = dev_alloc(&d, 2 * (size_t)count);
-    if (rc)
+    DevBuf<double> buf;
+    if ((rc = buf.alloc(2 * (size_t)count)))
         return rc;
-    DevTemp guard;
-    guard.p = d;
+    double *d = buf;
     const size_t bytes = (size_t)count * sizeof(double);
     HIP_TRY(hipMemcpy(d, x, bytes, hipMemcpyHostToDevice));
     rc = trlda_polygamma_device(n, count, d, d + count, device);
@@ -8744,12 +8675,10 @@ int dirichlet_device(int m, int n, double alpha, uint64_t key, double *out, int 
         const int nchunk = (int)(((int64_t)m + kSampleChunk - 1) / kSampleChunk);
         const int64_t nblocks = (int64_t)n * nchunk;
         const int64_t cols = std::max<int64_t>(max_blocks / nchunk, 1);     // columns per launch
-        double *part = nullptr;
-        int rc = dev_alloc(&part, (size_t)nblocks + 2 * (size_t)n);
-        if (rc)
+        DevBuf<double> buf;
+        if (int rc = buf.alloc((size_t)nblocks + 2 * (size_t)n))
             return rc;
-        DevTemp guard;
-        guard.p = part;
+        double *part = buf;
         double *colmax = part + nblocks, *colsum = colmax + n;
         const dim3 cgrid((unsigned)std::min<int64_t>(((int64_t)n + kSampleThreads - 1) / kSampleThreads, cap));
         for (int64_t j0 = 0; j0 < n; j0 += cols) {
@@ -8780,7 +8709,7 @@ int dirichlet_device(int m, int n, double alpha, uint64_t key, double *out, int 
                 HIP_TRY(hipGetLastError());
             }
         }
-        HIP_TRY(hipStreamSynchronize(nullptr));               // (before the guard frees part)
+        HIP_TRY(hipStreamSynchronize(nullptr));               // (before buf frees part)
         return TRLDA_OK;
     }
     HIP_TRY(hipStreamSynchronize(nullptr));
@@ -8819,12 +8748,10 @@ int trlda_sample_dirichlet_host(int m, int n, double alpha, double *out, int dev
     const uint64_t key = trlda_host::rng_draw_key();          // every valid call: two draws
     if (count == 0)
         return TRLDA_OK;
-    double *d = nullptr;
-    rc = dev_alloc(&d, count);
-    if (rc)
+    DevBuf<double> buf;
+    if ((rc = buf.alloc(count)))
         return rc;
-    DevTemp guard;
-    guard.p = d;
+    double *d = buf;
     rc = dirichlet_device(m, n, alpha, key, d, device);
     if (rc)
         return rc;
@@ -8843,12 +8770,10 @@ int trlda_debug_dirichlet_sums(int m, int n, double alpha, uint64_t key, double 
     if ((rc = use_device(device)))
         return rc;
     const size_t count = (size_t)m * (size_t)n;
-    double *d = nullptr;
-    rc = dev_alloc(&d, count + (size_t)n);
-    if (rc)
+    DevBuf<double> buf;
+    if ((rc = buf.alloc(count + (size_t)n)))
         return rc;
-    DevTemp guard;
-    guard.p = d;
+    double *d = buf;
     rc = dirichlet_device(m, n, alpha, key, d, device, d + count);
     if (rc)
         return rc;
