@@ -626,6 +626,36 @@ int trlda_docindex_read_rows(trlda_docindex *index, int64_t first, int64_t count
 int trlda_docindex_set_slab_rows(trlda_docindex *index, int rows);
 int trlda_docindex_destroy(trlda_docindex *index);
 
+/* Distances between topics (csrc/topicdist_kernels.h).  A topic is p_i = lambda_i /
+ * S_i, S_i = sum_v lambda_iv; the second lambda, mu (K2 x V), gives q_j = mu_j / T_j.  dist_out (K x K2
+ * column-major, host: [i + K * j]) =
+ *   TRLDA_TOPICDIST_HELLINGER  sqrt(max(0, 1 - sum_v sqrt(p_iv q_jv)))
+ *   TRLDA_TOPICDIST_COSINE     max(0, 1 - sum_v p_iv q_jv / (|p_i| |q_j|))
+ *   TRLDA_TOPICDIST_KL         sum_v p_iv log(p_iv / q_jv), nats, the row topic first
+ *   TRLDA_TOPICDIST_JS         H(m) - H(p_i) / 2 - H(q_j) / 2, m = (p_i + q_j) / 2, nats (not its root)
+ * The second lambda is `other`'s (a model of the same V on the same device), or lambda_host (K2 x V
+ * column-major, uploaded to a temporary and not kept; not validated), or with both NULL -- or
+ * other == model -- the model's own: then the diagonal is exactly 0 and the three symmetric measures
+ * are bitwise symmetric.  K2 is the second lambda's number of topics in every case.  No floating-point
+ * atomics: how V is cut into chunks and the matrix into tiles depends on (K, K2, V, measure) alone and
+ * the chunks' sums are added in ascending order, so equal inputs give equal bits.  A lambda with zeros
+ * gives what IEEE arithmetic gives.
+ * TRLDA_ERR_ARG, before anything is waited for, copied or launched: a NULL model or dist_out, both
+ * `other` and lambda_host, another V or device, a K2 that is not the second lambda's, an unknown
+ * measure, more tiles or chunks than a grid takes.  Runs on the model's stream; pending deferred
+ * statistics and stream lanes of both models are settled first and `other`'s stream is waited for.
+ * lambda, alpha and the generator are left alone.  Synchronises.  No reference counterpart. */
+#define TRLDA_TOPICDIST_HELLINGER 0
+#define TRLDA_TOPICDIST_COSINE    1
+#define TRLDA_TOPICDIST_KL        2
+#define TRLDA_TOPICDIST_JS        3
+int trlda_model_topic_distances(trlda_model *model, trlda_model *other, const double *lambda_host, int K2,
+                                int measure, double *dist_out);
+/* A/B switch for tests and measurements: words per chunk of V in trlda_model_topic_distances (any
+ * positive number; 0: automatic).  The results agree within rounding, not bitwise.  No reference
+ * counterpart. */
+int trlda_model_set_topicdist_chunk(trlda_model *model, int words);
+
 /* LDA::updateVariablesGibbs (src/lda.cpp:224-293), reached from python/src/ldainterface.cpp:311-390
  * with inference_method='GIBBS': collapsed Gibbs sampling of the batch's topic assignments on the
  * device (csrc/gibbs_kernels.h), one wave64 per document, K <= 1024 (more: TRLDA_ERR_ARG).

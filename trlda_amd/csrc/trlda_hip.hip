@@ -53,6 +53,7 @@
 #include "l2r_kernels.h"
 #include "wordtopics_kernels.h"
 #include "docindex_kernels.h"
+#include "topicdist_kernels.h"
 
 namespace {
 
@@ -510,6 +511,7 @@ struct trlda_model {
     // exp(-psi(row sum)), which overflows below 1.4e-3 (estep_kernels.h, 2b)
     double rs_floor = 0.0;
     int64_t d2h_bytes = 0;              // bytes copied to the host through this model (tests)
+    int topicdist_chunk = 0;            // words per chunk of trlda_model_topic_distances (0: automatic)
     bool lambda_exposed = false;        // trlda_model_lambda_dev was handed out: never trust rs_*
     // Every element of lambda is known to be > 0 (or NaN): set from the host copy when lambda is
     // uploaded, kept by the M-steps that provably keep it (mstep_keeps_positive), dropped by
@@ -6073,6 +6075,117 @@ int trlda_docindex_destroy(trlda_docindex *x)
     if (x->model && use_device(x->model->device) == TRLDA_OK && x->model->stream)
         (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
     delete x;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- distances between topics (csrc/topicdist_kernels.h) ----
+
+namespace {
+
+// The row statistics of a K x V lambda on `stream`: 3 x K into `stats`, through `part`
+int topicdist_stats(hipStream_t stream, int K, int V, const double *lam, double *part, double *stats)
+{
+    const int blocks = (V + trlda::kTopicDistStatWords - 1) / trlda::kTopicDistStatWords;
+    hipLaunchKernelGGL(trlda::topicdist_stats_kernel, dim3(blocks), dim3(trlda::kTopicDistThreads), 0, stream,
+                       K, V, lam, part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdist_stats_sum_kernel,
+                       dim3((3 * K + trlda::kTopicDistThreads - 1) / trlda::kTopicDistThreads),
+                       dim3(trlda::kTopicDistThreads), 0, stream, K, blocks, part, stats);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_set_topicdist_chunk(trlda_model *m, int words)
+{
+    if (!m || words < 0)
+        return fail(TRLDA_ERR_ARG, "NULL model, or words per chunk below 0 (0: automatic)");
+    m->topicdist_chunk = words;
+    return TRLDA_OK;
+}
+
+int trlda_model_topic_distances(trlda_model *m, trlda_model *other, const double *lambda_host, int K2,
+                                int measure, double *dist_out)
+{
+    if (!m || !dist_out)
+        return fail(TRLDA_ERR_ARG, "model / dist_out is NULL");
+    if (other && lambda_host)
+        return fail(TRLDA_ERR_ARG, "give another model or a host lambda, not both");
+    if (measure < 0 || measure >= trlda::kTopicDistMeasures)
+        return fail(TRLDA_ERR_ARG, "unknown measure");
+    if (other && (other->V != m->V || other->device != m->device))
+        return fail(TRLDA_ERR_ARG, "the other model has another number of words or lives on another device");
+    const bool self = other == m || (!other && !lambda_host);
+    if (K2 < 1 || (other && K2 != other->K) || (self && K2 != m->K))
+        return fail(TRLDA_ERR_ARG, "K2 is not the second lambda's number of topics");
+    const int K = m->K, V = m->V, T = trlda::kTopicDistTile;
+    const int cw = m->topicdist_chunk > 0 ? m->topicdist_chunk : trlda::topicdist_chunk_words(K, K2, V);
+    const long long chunks = ((long long)V + cw - 1) / cw;
+    const size_t n = (size_t)K * K2;
+    if ((K + T - 1) / T > 65535 || (K2 + T - 1) / T > 65535 || chunks > 65535 || (long long)V + cw > INT_MAX ||
+        (n + trlda::kTopicDistThreads - 1) / trlda::kTopicDistThreads > (size_t)INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many topics or chunks of words for the topic-distance kernels");
+
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (other && other != m) {
+        if ((rc = check_model(other)))
+            return rc;
+        HIP_TRY(hipStreamSynchronize(other->stream));
+    }
+    hipStream_t stream = m->stream;
+    DevBuf<double> mu_own, spart, stats, part, out;
+    const double *mu = self ? m->lambda : other ? other->lambda : nullptr;
+    if (!mu) {
+        if ((rc = mu_own.alloc((size_t)K2 * V)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(mu_own, lambda_host, (size_t)K2 * V * sizeof(double), hipMemcpyHostToDevice,
+                               stream));
+        mu = mu_own;
+    }
+    const size_t sblocks = (size_t)(V + trlda::kTopicDistStatWords - 1) / trlda::kTopicDistStatWords;
+    if ((rc = spart.alloc(sblocks * 3 * std::max(K, K2))) || (rc = stats.alloc(3 * ((size_t)K + K2))) ||
+        (rc = part.alloc((size_t)chunks * n)) || (rc = out.alloc(n)))
+        return rc;
+    double *sa = stats, *sb = self ? sa : sa + 3 * (size_t)K;
+    if ((rc = topicdist_stats(stream, K, V, m->lambda, spart, sa)))
+        return rc;
+    if (!self && (rc = topicdist_stats(stream, K2, V, mu, spart, sb)))
+        return rc;
+    const dim3 grid((K + T - 1) / T, (K2 + T - 1) / T, (unsigned)chunks), block(trlda::kTopicDistThreads);
+    switch (measure) {
+    case 0:
+        hipLaunchKernelGGL(trlda::topicdist_product_kernel<0>, grid, block, 0, stream, K, K2, V, cw, m->lambda, mu,
+                           part.get());
+        break;
+    case 1:
+        hipLaunchKernelGGL(trlda::topicdist_product_kernel<1>, grid, block, 0, stream, K, K2, V, cw, m->lambda, mu,
+                           part.get());
+        break;
+    case 2:
+        hipLaunchKernelGGL(trlda::topicdist_product_kernel<2>, grid, block, 0, stream, K, K2, V, cw, m->lambda, mu,
+                           part.get());
+        break;
+    default:
+        hipLaunchKernelGGL(trlda::topicdist_js_kernel, grid, block, 0, stream, K, K2, V, cw, m->lambda, mu, sa, sb,
+                           part.get());
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdist_finish_kernel,
+                       dim3((unsigned)((n + trlda::kTopicDistThreads - 1) / trlda::kTopicDistThreads)), block, 0,
+                       stream, K, K2, (int)chunks, measure, self ? 1 : 0, part.get(), sa, sb, out.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(dist_out, out, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    m->d2h_bytes += (int64_t)(n * sizeof(double));
     return TRLDA_OK;
 }
 

@@ -88,6 +88,39 @@ def _coherence(measure, doc_freq, co, num_docs):
         return np.cumsum(term, axis=1)[:, -1] / float(len(m_idx))
 
 
+TOPIC_MEASURES = {"hellinger": 0, "cosine": 1, "kl": 2, "jensen_shannon": 3, "js": 3}
+
+
+def _topic_measure(name):
+    if not isinstance(name, str):
+        raise TypeError("`measure` should be of type `str`.")
+    try:
+        return TOPIC_MEASURES[name.lower()]
+    except KeyError:
+        raise ValueError("Unknown measure '%s' (expected 'hellinger', 'cosine', 'kl' or "
+                         "'jensen_shannon')." % name)
+
+
+def _greedy_match(dist):
+    """Greedy one-to-one matching on a K x K' distance matrix (LDA.match_topics): K K'-sized host
+    arithmetic.  The pairs in the total order (distance, i, j) -- a stable sort of the row-major
+    matrix -- each kept when both its topics are free."""
+    K, K2 = dist.shape
+    match = np.full(K, -1, dtype=np.int64)
+    best = np.full(K, np.inf, dtype=np.float64)
+    col_free = np.ones(K2, dtype=bool)
+    left = min(K, K2)
+    flat = np.ascontiguousarray(dist).ravel()
+    for e in np.argsort(flat, kind="stable"):
+        i, j = divmod(int(e), K2)
+        if match[i] < 0 and col_free[j]:
+            match[i], best[i], col_free[j] = j, flat[e], False
+            left -= 1
+            if left == 0:
+                break
+    return match, best
+
+
 class Distribution(object):
     """Abstract base (reference include/distribution.h, distributioninterface.cpp)."""
 
@@ -645,6 +678,82 @@ class LDA(Distribution):
         closed with the model."""
         from ..index import DocumentIndex
         return DocumentIndex(self, measure)
+
+    # -- distances between topics (csrc/topicdist_kernels.h) ---------------------------------------
+    def _second_lambda(self, other):
+        """(the other model or None, a K2 x V Fortran-ordered lambda or None, K2) for ``other`` of
+        ``topic_distances``, checked without any GPU work."""
+        if other is None or other is self:
+            return None, None, self._K
+        if isinstance(other, LDA):
+            if other.num_words != self._V:
+                raise ValueError("The other model has another number of words.")
+            if other.device != self._device:
+                raise ValueError("The other model lives on another device.")
+            return other, None, other.num_topics
+        try:                                             # (a string, a dict: no array; a number: no dimensions)
+            arr = np.asarray(other, dtype=np.float64)
+        except (TypeError, ValueError):
+            arr = None
+        if arr is None or arr.ndim == 0:
+            raise TypeError("`other` should be None, an LDA model or a K' x V array of lambdas.")
+        if arr.ndim != 2 or arr.shape[0] < 1 or arr.shape[1] != self._V:
+            raise ValueError("An array `other` should be K' x %d (topics x words)." % self._V)
+        if not (np.all(np.isfinite(arr)) and np.all(arr > 0)):
+            raise ValueError("Every lambda of `other` should be finite and positive.")
+        return None, np.asfortranarray(arr), int(arr.shape[0])
+
+    def topic_distances(self, other=None, measure='hellinger'):
+        """Distances between this model's topics and the topics of ``other``: a K x K' float64 array.
+
+        A topic is the distribution ``p_i = lambdas[i] / lambdas[i].sum()`` (E[beta_i], what
+        ``top_words`` ranks by); ``q_j`` is the same of the second lambda.  Entry (i, j):
+
+        - ``'hellinger'`` (default): ``sqrt(max(0, 1 - sum_v sqrt(p_iv q_jv)))``, in [0, 1];
+        - ``'cosine'``: ``max(0, 1 - sum_v p_iv q_jv / (|p_i| |q_j|))``, in [0, 1];
+        - ``'kl'``: ``sum_v p_iv log(p_iv / q_jv)`` in nats, this model's topic first (asymmetric);
+        - ``'jensen_shannon'`` (or ``'js'``): ``H(m) - H(p_i) / 2 - H(q_j) / 2`` with
+          ``m = (p_i + q_j) / 2``, in nats, at most ln 2 -- the divergence, not its square root.
+
+        Case does not matter; another string raises ValueError, a non-string TypeError.
+
+        ``other`` is None (the model against itself: the diagonal is exactly 0 and the three symmetric
+        measures give a bitwise symmetric matrix), another model of any subclass with the same
+        ``num_words`` on the same device, or a K' x V array-like of lambdas (finite and positive, e.g.
+        the topics a synthetic corpus was drawn from; it is uploaded for the call and not kept).
+        Anything else raises TypeError; another number of words or device, or an array of the wrong
+        shape or with a non-finite or non-positive entry, ValueError -- all before any GPU work.  A
+        *copy* of the model is another model: its diagonal is near 0, not exactly 0.  The models'
+        own lambdas are not checked; one set by hand with zeros gives what IEEE arithmetic gives.
+
+        The matrix is formed on the GPU without atomics, in an order that depends on (K, K', V,
+        measure) alone: two calls on the same lambdas agree bitwise.  Only the K x K' result is
+        copied to the host."""
+        code = _topic_measure(measure)                               # (before the model is looked at)
+        model, lam, K2 = self._second_lambda(other)
+        if getattr(self, "_handle", None) is None or (model is not None and model._handle is None):
+            raise RuntimeError("The model has been closed.")
+        self._settle()
+        if model is not None:
+            model._settle()
+        out = np.empty((self._K, K2), dtype=np.float64, order="F")
+        _ffi.check(_ffi.lib().trlda_model_topic_distances(
+            self._handle, None if model is None else model._handle,
+            None if lam is None else lam.ctypes.data, K2, code, out.ctypes.data))
+        return out
+
+    def match_topics(self, other, measure='hellinger'):
+        """``(match, dist)``: for each topic i of this model the topic ``match[i]`` of ``other`` it is
+        paired with (int64) and their distance ``dist[i]`` (float64), by greedy one-to-one matching on
+        ``topic_distances(other, measure)``: the pairs are taken in the order (distance ascending, i
+        ascending, j ascending) and a pair is kept when both its topics are still free.  With more
+        topics here than in ``other`` the rows left over get ``match = -1`` and ``dist = inf``.  Not
+        the optimal assignment.  ``other=None`` raises ValueError (a model matched with itself is the
+        identity); ``other`` and ``measure`` are otherwise those of ``topic_distances``."""
+        _topic_measure(measure)
+        if other is None:
+            raise ValueError("`other` is None: a model matched with itself is the identity.")
+        return _greedy_match(self.topic_distances(other, measure))
 
     # -- topic coherence (Mimno et al. 2011; Bouma 2009; csrc/coherence_kernels.h) -----------------
     def top_words(self, top_n=10):
