@@ -689,6 +689,48 @@ int trlda_model_gibbs(trlda_model *model, const trlda_batch *batch, const double
 int trlda_model_gibbs_host(trlda_model *model, const trlda_batch *batch, double *theta, int use_latents,
                            double *sstats, int num_samples, int burn_in);
 
+/* Collapsed variational Bayes, zero order (CVB0) of the batch's documents on the model's fixed
+ * topics, on the device (csrc/cvb0_kernels.h, whose header is the contract), one wave64 per
+ * document, K <= 1024 (more: TRLDA_ERR_ARG before anything is allocated or launched).  No reference
+ * counterpart: Asuncion, Welling, Smyth & Teh, "On smoothing and inference for topic models" (UAI
+ * 2009), with the document-side update of Foulds, Boyles, DuBois, Smyth & Welling, "Stochastic
+ * collapsed variational Bayesian inference for latent Dirichlet allocation" (KDD 2013).  It is the
+ * deterministic form of the conditional trlda_model_gibbs samples from,
+ * phi_ik ~ (alpha_k + sum_{j != i} phi_jk) e[k, w_i], on the Gibbs path's normalised table e
+ * (trlda_debug_gibbs_table returns what the call read).
+ *   theta0_dev  K x B, the weights the documents' phi start from (phi_p ~ theta0 e[:, w_p]), or
+ *               NULL: alpha
+ *   theta_dev   out: K x B, (alpha + n) / (sum alpha + N_d), n the expected topic counts
+ *   sstats_dev  out: K x V, expected tokens per (topic, word), sum over the word's entries of
+ *               c_p phi_p in document order; not multiplied by exp E[log beta]; 0 outside the batch
+ *   max_iter    Gauss-Seidel sweeps over a document's entries, at most (0: the init state)
+ *   threshold   a document stops after the sweep whose mean |change of n| is below it (0: never)
+ *   iters_dev   out, or NULL: B sweeps done per document
+ * One phi per entry (word type) with a ONE-token self-exclusion.  No random numbers (the library's
+ * stream is not advanced), no atomics: two calls give bitwise the same result, whatever the launch
+ * geometry, the lanes or the slab cap.  A token whose weights sum to 0 or are not finite fails the
+ * call with TRLDA_ERR_VALUE.  max_iter < 0: TRLDA_ERR_ARG.  Flushes the deferred work first and
+ * touches none of the VI path's state: trlda_model_get_sstats, the deferred statistics, the lanes
+ * and the prefetch announcements keep what they held.  Workspaces -- the Gibbs path's K x V table,
+ * phi as entries x K doubles of a slab (trlda_model_set_cvb0_slab_bytes), two int32 per entry and
+ * document -- stay allocated until trlda_model_destroy.  Synchronises. */
+int trlda_model_cvb0(trlda_model *model, const trlda_batch *batch, const double *theta0_dev,
+                     double *theta_dev, double *sstats_dev, int max_iter, double threshold,
+                     int32_t *iters_dev);
+
+/* Host-pointer convenience around trlda_model_cvb0: theta (K x B host) holds theta0 when
+ * use_latents != 0 and receives theta; sstats (K x V host) and iters (B host, or NULL) receive the
+ * statistics and the sweeps done.  Staged through trlda_model_gibbs_host's buffers.  No reference
+ * counterpart (Asuncion et al. 2009; Foulds et al. 2013). */
+int trlda_model_cvb0_host(trlda_model *model, const trlda_batch *batch, double *theta, int use_latents,
+                          double *sstats, int max_iter, double threshold, int32_t *iters);
+
+/* A/B switch for tests: the cap in bytes on trlda_model_cvb0's phi scratch (0: the default, 1 GiB
+ * -- a chosen number, not a measured one).  The batch's documents are worked off in slabs, in batch
+ * order, whose entries x K doubles fit the cap (a document that alone exceeds it is a slab of its
+ * own); results are bitwise independent of it.  No reference counterpart. */
+int trlda_model_set_cvb0_slab_bytes(trlda_model *model, size_t bytes);
+
 /* ---- sampling documents: LDA::sample, src/lda.cpp:88-115, python/src/ldainterface.cpp:218-262 ----
  * Topics beta_k ~ Dirichlet(lambda_k) are drawn once per call; per document d, its length
  * n_d ~ Poisson(length), theta_d ~ Dirichlet(alpha) and, per token, a topic z ~ theta_d and a

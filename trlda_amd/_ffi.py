@@ -114,6 +114,9 @@ _SIGNATURES = {
     "trlda_gibbs": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, f64p, f64p, f64p, C.c_int,
                               f64p, C.c_int, C.c_int, C.c_int]),
     "trlda_debug_gibbs_table": (C.c_int, [vp, f64p]),
+    "trlda_model_cvb0": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_double, vp]),
+    "trlda_model_cvb0_host": (C.c_int, [vp, vp, f64p, C.c_int, f64p, C.c_int, C.c_double, vp]),
+    "trlda_model_set_cvb0_slab_bytes": (C.c_int, [vp, C.c_size_t]),
     "trlda_rng_draw_key": (C.c_int, [C.POINTER(C.c_uint64)]),
     "trlda_sample_lengths": (C.c_int, [C.c_int, C.c_double, C.c_uint64, i32p]),
     "trlda_model_sample": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64]),

@@ -44,6 +44,7 @@
 #include "rng_kernels.h"
 #include "dp_kernels.h"
 #include "gibbs_kernels.h"
+#include "cvb0_kernels.h"
 #include "sample_kernels.h"
 #include "heldout_kernels.h"
 #include "coherence_kernels.h"
@@ -639,7 +640,7 @@ struct trlda_model {
         DevBuf<int64_t> tokens, tok_off;
         DevBuf<int32_t> order;
         DevBuf<int> flag;
-        DevBuf<double> theta_in, theta, sstats; // trlda_model_gibbs_host's
+        DevBuf<double> theta_in, theta, sstats; // trlda_model_gibbs_host's (and trlda_model_cvb0_host's)
         // the plan (token offsets, document order) of the batch it was made for
         uint64_t plan_batch = 0;
         int64_t total_tokens = 0;
@@ -650,6 +651,21 @@ struct trlda_model {
         DevBuf<double> rs, mpart;
         DevBuf<int> nonpos;
     } gibbs;
+    // collapsed variational Bayes (cvb0_kernels.h, trlda_model_cvb0): it reads the Gibbs path's table
+    // (gibbs.eeb and its preamble buffers) and stages the host form through gibbs.theta_in / theta /
+    // sstats; its own are the phi scratch of a slab of documents, the slabs' plan and the flag
+    struct {
+        DevBuf<double> phi;                     // [entries of the largest slab][K]
+        DevBuf<int32_t> order;                  // B: the slabs' documents, each slab's most entries first
+        DevBuf<int32_t> wpos;                   // nnz: rank in word-major order -> CSR position
+        DevBuf<int32_t> iters;                  // trlda_model_cvb0_host's
+        DevBuf<int> flag;
+        size_t slab_bytes = (size_t)1 << 30;    // the cap on phi (trlda_model_set_cvb0_slab_bytes)
+        // the plan of the batch it was made for, under the rows a slab may hold
+        uint64_t plan_batch = 0;
+        int64_t plan_rows = 0;
+        std::vector<int32_t> slabs;             // first document of each slab, then B
+    } cvb0;
     // sampling documents (sample_kernels.h, trlda_model_sample): the K x V prefix table lives in
     // gibbs.eeb (per-call scratch of either path, behind a flush); the rest is its own
     struct {
@@ -6446,6 +6462,209 @@ int trlda_debug_gibbs_table(trlda_model *m, double *host_eeb)
     HIP_TRY(hipMemcpyAsync(host_eeb, m->gibbs.eeb, (size_t)m->K * m->V * sizeof(double), hipMemcpyDeviceToHost,
                            m->stream));
     return sync_model(m);
+}
+
+// ---- collapsed variational Bayes, zero order (cvb0_kernels.h; no reference counterpart) ----
+}  // extern "C"
+
+namespace {
+
+// The slabs of batch `b` -- consecutive documents whose entries number at most `rows` (a longer
+// document is a slab of its own) -- each slab's documents by decreasing length, and the inverse of
+// the batch index's word-major ranks; made once per batch and cap.
+int cvb0_plan(trlda_model *m, const trlda_batch *b, int64_t rows)
+{
+    auto &c = m->cvb0;
+    if (c.plan_batch == b->id && c.plan_rows == rows)
+        return TRLDA_OK;
+    c.plan_batch = 0;
+    const int B = b->B;
+    const std::vector<int32_t> &ip = b->indptr_host;
+    if (B > 0 && (int)ip.size() != B + 1)
+        return fail(TRLDA_ERR_ARG, "CVB0: the batch carries no host copy of its offsets");
+    int rc = c.order.grow((size_t)std::max(B, 1));
+    if (!rc) rc = c.wpos.grow((size_t)std::max<int64_t>(b->nnz, 1));
+    if (rc)
+        return rc;
+    c.slabs.assign(1, 0);
+    for (int d = 0; d < B; ++d)
+        if (d > c.slabs.back() && (int64_t)ip[(size_t)d + 1] - ip[(size_t)c.slabs.back()] > rows)
+            c.slabs.push_back(d);
+    c.slabs.push_back(B);
+    std::vector<int32_t> order((size_t)B);
+    std::iota(order.begin(), order.end(), 0);
+    for (size_t s = 0; s + 1 < c.slabs.size(); ++s)
+        std::stable_sort(order.begin() + c.slabs[s], order.begin() + c.slabs[s + 1],
+                         [&ip](int32_t x, int32_t y) {
+                             return ip[(size_t)x + 1] - ip[(size_t)x] > ip[(size_t)y + 1] - ip[(size_t)y];
+                         });
+    if (b->nnz > 0) {
+        const int nnz = (int)b->nnz;
+        hipLaunchKernelGGL(trlda::cvb0_wpos_kernel<256>, dim3((nnz + 255) / 256), dim3(256), 0, m->stream, nnz,
+                           b->wrank, c.wpos);
+        HIP_TRY(hipGetLastError());
+    }
+    if (B > 0) {
+        HIP_TRY(hipMemcpyAsync(c.order, order.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice,
+                               m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));       // (the host vector goes out of scope)
+    }
+    c.plan_batch = b->id;
+    c.plan_rows = rows;
+    return TRLDA_OK;
+}
+
+template <int KPL>
+int cvb0_launch_docs(trlda_model *m, const trlda::Cvb0Args &a)
+{
+    hipLaunchKernelGGL(trlda::cvb0_docs_kernel<KPL>, dim3((a.n_docs + trlda::kGibbsWaves - 1) / trlda::kGibbsWaves),
+                       dim3(trlda::kGibbsWaves * trlda::kWave), 0, m->stream, a);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the whole call on the model's stream; waits for the device at the end (the failure flag)
+int cvb0_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, double *theta_dev,
+                double *sstats_dev, int max_iter, double threshold, int32_t *iters_dev)
+{
+    using namespace trlda;
+    const int K = m->K, V = m->V, B = b->B;
+    const size_t KV = (size_t)K * V;
+    if (b->V != V)
+        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    if (K > kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "CVB0 supports at most 1024 topics (the Gibbs path's limit)");
+    if (max_iter < 0)
+        return fail(TRLDA_ERR_ARG, "max_iter should not be negative");
+    if (!sstats_dev || (B > 0 && !theta_dev))
+        return fail(TRLDA_ERR_ARG, "NULL theta / sstats");
+    auto &c = m->cvb0;
+    const int64_t rows = std::max<int64_t>(1, (int64_t)(c.slab_bytes / ((size_t)K * sizeof(double))));
+    int rc = batch_begin(m, b);
+    if (!rc) rc = cvb0_plan(m, b, rows);
+    if (!rc && !c.flag) rc = c.flag.alloc(1);
+    if (rc)
+        return rc;
+    int64_t slab_rows = 0;
+    for (size_t s = 0; s + 1 < c.slabs.size(); ++s)
+        slab_rows = std::max<int64_t>(slab_rows, (int64_t)b->indptr_host[(size_t)c.slabs[s + 1]] -
+                                                     b->indptr_host[(size_t)c.slabs[s]]);
+    if ((rc = c.phi.grow((size_t)std::max<int64_t>(slab_rows, 1) * K)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(c.flag, 0, sizeof(int), m->stream));
+    if (KV)
+        HIP_TRY(hipMemsetAsync(sstats_dev, 0, KV * sizeof(double), m->stream));
+    if (B > 0 && b->nnz > 0 && (rc = gibbs_preamble(m, b)))
+        return rc;
+    const int kpl = (K + kWave - 1) / kWave;
+    int gsz = 1;
+    while (gsz < kWave && gsz < K)
+        gsz <<= 1;
+    constexpr int TS = 256;
+    const int per = TS / gsz;
+    const int GS = std::max(1, std::min((b->n_active + per - 1) / per, 4096));
+    for (size_t s = 0; s + 1 < c.slabs.size(); ++s) {
+        const int d0 = c.slabs[s], d1 = c.slabs[s + 1];
+        if (d1 <= d0)
+            continue;
+        const int32_t j0 = b->indptr_host[(size_t)d0], j1 = b->indptr_host[(size_t)d1];
+        Cvb0Args a;
+        a.K = K; a.n_docs = d1 - d0; a.max_iter = max_iter; a.threshold = threshold;
+        a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
+        a.order = c.order + d0; a.j0 = j0;
+        a.eeb = m->gibbs.eeb; a.alpha = m->alpha; a.theta0 = theta0_dev; a.theta = theta_dev;
+        a.iters = iters_dev; a.phi = c.phi; a.flag = c.flag;
+        rc = kpl <= 1 ? cvb0_launch_docs<1>(m, a) : kpl <= 2 ? cvb0_launch_docs<2>(m, a)
+           : kpl <= 4 ? cvb0_launch_docs<4>(m, a) : kpl <= 8 ? cvb0_launch_docs<8>(m, a)
+           : cvb0_launch_docs<16>(m, a);
+        if (rc)
+            return rc;
+        if (j1 > j0 && b->n_active > 0) {
+            hipLaunchKernelGGL(cvb0_stats_kernel<TS>, dim3(GS), dim3(TS), 0, m->stream, K, b->n_active, gsz,
+                               b->active, b->wptr, c.wpos, b->cnts, j0, j1, c.phi, sstats_dev);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    (void)batch_end(m, b);
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, c.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "CVB0: a token's topic weights sum to zero or are not finite.");
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_cvb0(trlda_model *m, const trlda_batch *b, const double *theta0_dev, double *theta_dev,
+                     double *sstats_dev, int max_iter, double threshold, int32_t *iters_dev)
+{
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b)
+        return fail(TRLDA_ERR_ARG, "NULL batch");
+    return cvb0_device(m, b, theta0_dev, theta_dev, sstats_dev, max_iter, threshold, iters_dev);
+}
+
+int trlda_model_cvb0_host(trlda_model *m, const trlda_batch *b, double *theta, int use_latents, double *sstats,
+                          int max_iter, double threshold, int32_t *iters)
+{
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (!b || !sstats || (b->B > 0 && !theta))
+        return fail(TRLDA_ERR_ARG, "NULL batch / theta / sstats");
+    if (max_iter < 0)
+        return fail(TRLDA_ERR_ARG, "max_iter should not be negative");
+    if (m->K > trlda::kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, "CVB0 supports at most 1024 topics (the Gibbs path's limit)");
+    auto &g = m->gibbs;
+    const size_t tcount = (size_t)m->K * std::max(b->B, 1);
+    const size_t KV = (size_t)m->K * m->V;
+    rc = g.theta.grow(tcount);
+    if (!rc && use_latents) rc = g.theta_in.grow(tcount);
+    if (!rc) rc = g.sstats.grow(std::max<size_t>(KV, 1));
+    if (!rc && iters) rc = m->cvb0.iters.grow((size_t)std::max(b->B, 1));
+    if (rc)
+        return rc;
+    const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
+    if (use_latents && tbytes)
+        HIP_TRY(hipMemcpyAsync(g.theta_in, theta, tbytes, hipMemcpyHostToDevice, m->stream));
+    rc = cvb0_device(m, b, use_latents ? g.theta_in : nullptr, g.theta, g.sstats, max_iter, threshold,
+                     iters ? m->cvb0.iters : nullptr);
+    if (rc)
+        return rc;
+    if (tbytes)
+        HIP_TRY(hipMemcpyAsync(theta, g.theta, tbytes, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(sstats, g.sstats, KV * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (iters && b->B > 0)
+        HIP_TRY(hipMemcpyAsync(iters, m->cvb0.iters, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost,
+                               m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    m->d2h_bytes += (int64_t)(tbytes + KV * sizeof(double));
+    return TRLDA_OK;
+}
+
+int trlda_model_set_cvb0_slab_bytes(trlda_model *m, size_t bytes)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    m->cvb0.slab_bytes = bytes ? bytes : (size_t)1 << 30;
+    return TRLDA_OK;
 }
 
 // ---- Gibbs inside the update loops: OnlineLDA::updateParameters (src/onlinelda.cpp:53-179) and

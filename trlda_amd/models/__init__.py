@@ -50,18 +50,25 @@ def _alpha_vector(alpha, num_topics):
     return arr.shape[0], np.ascontiguousarray(arr[:, 0])
 
 
+_INFERENCE_METHODS = "`inference_method` should be one of 'VI', 'GIBBS' or 'CVB0'."
+_CVB0_NO_TRAINING = "Training from CVB0 statistics is not built yet: use 'VI' or 'GIBBS' here."
+
+
 def _inference_method(name):
-    """ldainterface.cpp:343-359: first letter decides; returns 'VI' or 'GIBBS'."""
+    """ldainterface.cpp:343-359: first letter decides; returns 'VI', 'GIBBS' or -- beyond the
+    reference -- 'CVB0'."""
     if name is None:
         return "VI"
     if not isinstance(name, str):
-        raise TypeError("`inference_method` should be either 'GIBBS' or 'VI'.")
+        raise TypeError(_INFERENCE_METHODS)
     first = name[:1]
     if first in ("v", "V"):
         return "VI"
     if first in ("g", "G"):
         return "GIBBS"
-    raise TypeError("`inference_method` should be either 'GIBBS' or 'VI'.")
+    if first in ("c", "C"):
+        return "CVB0"
+    raise TypeError(_INFERENCE_METHODS)
 
 
 def _coherence(measure, doc_freq, co, num_docs):
@@ -297,8 +304,20 @@ class LDA(Distribution):
         the random numbers are Philox4x32-10 keyed by two draws of the seeded stream, so
         ``trlda.seed`` makes a call reproducible and results do not depend on the launch; the
         statistics are exact counts scaled once; theta's gamma draws are Marsaglia-Tsang in log
-        space.  ``return_iterations`` does not apply to Gibbs sampling (TypeError)."""
+        space.  ``return_iterations`` does not apply to Gibbs sampling (TypeError).
+
+        ``inference_method='CVB0'`` (no reference counterpart; csrc/cvb0_kernels.h, K <= 1024)
+        returns ``(theta K x N, sstats K x V[, iters])``: collapsed variational Bayes, zero order
+        (Asuncion et al. 2009; Foulds et al. 2013) -- the deterministic form of the Gibbs
+        conditional, each token's topic count replaced by its expectation.  At most ``max_iter``
+        sweeps per document, ended once the mean change of its expected topic counts is below
+        ``threshold``; ``latents`` is the weight vector the documents' responsibilities start
+        from (default: alpha).  ``theta = (alpha + n) / (sum alpha + N_d)``; the statistics are
+        expected counts, not multiplied by exp E[log beta] (like Gibbs).  No seed is involved:
+        calls repeat bitwise.  ``num_samples`` and ``burn_in`` are ignored, as VI ignores them."""
         method = _inference_method(inference_method)
+        if method == "CVB0":
+            return self._update_variables_cvb0(docs, latents, max_iter, threshold, return_iterations)
         if method == "GIBBS":
             if return_iterations:
                 raise TypeError("`return_iterations` applies to VI only.")
@@ -336,6 +355,21 @@ class LDA(Distribution):
 
     do_e_step = update_variables                                     # module.cpp:103-106
 
+    def _initial_theta(self, latents, B):
+        """The K x B in/out array of the Gibbs and CVB0 entry points: a checked copy of ``latents``,
+        or zeros for the result."""
+        if latents is None:
+            return np.zeros((self._K, B), dtype=np.float64, order="F")
+        try:
+            t = np.array(latents, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`latents` should be of type `ndarray`.")
+        if t.ndim == 1:
+            t = t.reshape(-1, 1, order="F")
+        if t.ndim != 2 or t.shape != (self._K, B):
+            raise RuntimeError("Initial theta has wrong dimensionality.")  # lda.cpp:229-230
+        return np.asfortranarray(t)
+
     def _update_variables_gibbs(self, docs, latents, num_samples, burn_in):
         """lda.cpp:224-293 through trlda_model_gibbs_host (include/trlda_hip.h)."""
         num_samples, burn_in = int(num_samples), int(burn_in)
@@ -345,18 +379,7 @@ class LDA(Distribution):
         try:
             self._settle()
             B = len(batch)
-            if latents is not None:
-                try:
-                    t = np.array(latents, dtype=np.float64, order="F", copy=True)
-                except (TypeError, ValueError):
-                    raise TypeError("`latents` should be of type `ndarray`.")
-                if t.ndim == 1:
-                    t = t.reshape(-1, 1, order="F")
-                if t.ndim != 2 or t.shape != (self._K, B):
-                    raise RuntimeError("Initial theta has wrong dimensionality.")  # lda.cpp:229-230
-                theta = np.asfortranarray(t)
-            else:
-                theta = np.zeros((self._K, B), dtype=np.float64, order="F")
+            theta = self._initial_theta(latents, B)
             sstats = np.empty((self._K, self._V), dtype=np.float64, order="F")
             _ffi.check(_ffi.lib().trlda_model_gibbs_host(self._handle, batch.handle, theta,
                                                          int(latents is not None), sstats,
@@ -364,6 +387,26 @@ class LDA(Distribution):
         finally:
             if owned:
                 batch.close()
+        return theta, sstats
+
+    def _update_variables_cvb0(self, docs, latents, max_iter, threshold, return_iterations):
+        """CVB0 through trlda_model_cvb0_host (include/trlda_hip.h)."""
+        batch, owned = self._batch(docs)
+        try:
+            self._settle()
+            B = len(batch)
+            theta = self._initial_theta(latents, B)
+            sstats = np.empty((self._K, self._V), dtype=np.float64, order="F")
+            iters = np.zeros(B, dtype=np.int32)
+            _ffi.check(_ffi.lib().trlda_model_cvb0_host(self._handle, batch.handle, theta,
+                                                        int(latents is not None), sstats,
+                                                        int(max_iter), float(threshold),
+                                                        iters.ctypes.data))
+        finally:
+            if owned:
+                batch.close()
+        if return_iterations:
+            return theta, sstats, iters
         return theta, sstats
 
     # -- the variational lower bound (ldainterface.cpp:394-470 -> lda.cpp:297-360) ----------
@@ -385,6 +428,8 @@ class LDA(Distribution):
         ``inference_method='GIBBS'`` raises NotImplementedError: the reference's bound would plug
         the sampled theta in as gamma, which does not bound anything."""
         method = _inference_method(inference_method)
+        if method == "CVB0":
+            raise NotImplementedError(_CVB0_NO_TRAINING + "  (No bound is defined on them either.)")
         if method != "VI":
             raise NotImplementedError(
                 "A lower bound from Gibbs samples (lda.cpp:224-293) is outside the accelerated path.")
@@ -963,6 +1008,8 @@ class OnlineLDA(LDA):
         stochastic inference of Mimno, Hoffman & Blei (2012), K <= 1024.  ``max_iter_inference``
         does not apply to it; ``update_alpha`` is not supported with it (NotImplementedError)."""
         method = _inference_method(inference_method)
+        if method == "CVB0":
+            raise NotImplementedError(_CVB0_NO_TRAINING)
         if method == "GIBBS":
             num_samples, burn_in = _gibbs_args(update_alpha, num_samples, burn_in)
         else:
@@ -1130,6 +1177,8 @@ class BatchLDA(LDA):
         ``inference_method='GIBBS'``: every epoch's E-step is collapsed Gibbs sampling from a
         fresh theta (see OnlineLDA.update_parameters); ``update_alpha`` is not supported with it."""
         method = _inference_method(inference_method)
+        if method == "CVB0":
+            raise NotImplementedError(_CVB0_NO_TRAINING)
         if method == "GIBBS":
             num_samples, burn_in = _gibbs_args(update_alpha, num_samples, burn_in)
         else:
