@@ -129,7 +129,9 @@ def main():
     rng = np.random.RandomState(cfg["lambda_seed"])
     lam = np.asfortranarray(rng.gamma(100., .01, (K, V)))
     _ffi.check(L.trlda_model_set_lambda(model, lam))
-    _ffi.check(L.trlda_model_set_alpha(model, np.full(K, cfg["alpha"])))
+    # (a scalar, or a list of K: lda.cpp:194 adds a per-topic alpha)
+    _ffi.check(L.trlda_model_set_alpha(model, np.array(np.broadcast_to(np.asarray(cfg["alpha"], dtype=np.float64),
+                                                                        (K,)))))
     if cfg.get("plain"):
         _ffi.check(L.trlda_model_set_fused_update(model, 0))
         _ffi.check(L.trlda_model_set_carry_rowsums(model, 0))

@@ -3,7 +3,7 @@ sizes, document lengths (empty documents, single words, every tier of the K <= 1
 documents, documents beyond the split range), duplicate ids, zero counts, iteration limits and
 thresholds, both statistics modes, split documents on and off.
 
-    python tests/fuzz_estep.py [--cases 60] [--seed 1]        (tests/test_gpu_fuzz.py runs a short one)
+    python tests/fuzz_estep.py [--cases 60] [--seed 1] [--asymmetric]   (tests/test_gpu_fuzz.py runs short ones)
 """
 import argparse
 import os
@@ -25,6 +25,9 @@ def main(argv=None):
     ap.add_argument("--two-kernel-preamble", type=int, default=0)
     ap.add_argument("--passes", default="", help="mode:split_docs:merged:split_lists,... instead of the four "
                                                  "standard passes over a case (diagnosis)")
+    ap.add_argument("--asymmetric", action="store_true",
+                    help="the same cases with a per-topic alpha log-spaced over [2e-3, 4] in a random order and "
+                         "peaked topics, lambda = 200 Gamma(0.05, 1) + 0.01")
     args = ap.parse_args(argv)
     from oracle.pyoracle import Oracle                 # the checker
     from trlda_amd import _ffi
@@ -33,6 +36,8 @@ def main(argv=None):
     L = _ffi.lib()
     orc = Oracle()
     rng = np.random.RandomState(args.seed)
+    # (a generator of its own: everything a case draws today comes from `rng` as before)
+    rng_asym = np.random.RandomState(args.seed + 7919)
     worst_g = worst_s = 0.0
     for case in range(args.cases):
         K = int(rng.choice([3, 7, 31, 64, 65, 100, 128, 129, 200, 257, 500]))
@@ -62,6 +67,9 @@ def main(argv=None):
         max_iter = int(rng.choice([0, 1, 2, 20, 60]))
         thr = float(rng.choice([0., 1e-3, 1e-2]))
         alpha = float(rng.choice([.01, .1, 1.]))
+        if args.asymmetric:
+            lam = np.asfortranarray(200. * rng_asym.gamma(.05, 1., (K, V)) + .01)
+            alpha = np.logspace(np.log10(2e-3), np.log10(4.), K)[rng_asym.permutation(K)]
         if args.only >= 0 and case != args.only:
             continue
         if args.run and case not in [int(x) for x in args.run.split(",")]:
@@ -132,9 +140,10 @@ def main(argv=None):
                     bool((s[~nz] < 1e-149).all()) and bool(np.isfinite(s).all())
                 worst_g, worst_s = max(worst_g, eg), max(worst_s, es)
                 if not ok:
-                    print("MISMATCH case %d K=%d V=%d B=%d kind=%d max_iter=%d thr=%g alpha=%g mode=%d "
+                    print("MISMATCH case %d K=%d V=%d B=%d kind=%d max_iter=%d thr=%g alpha=%s mode=%d "
                           "split=%d merged=%d split_lists=%d: gamma %.2e sstats %.2e iters_equal %s kernel %s split_wgs %d lens %s"
-                          % (case, K, V, B, kind, max_iter, thr, alpha, mode, split, merged, split_lists, eg, es,
+                          % (case, K, V, B, kind, max_iter, thr, "per topic" if args.asymmetric else "%g" % alpha, mode, split,
+                             merged, split_lists, eg, es,
                              np.array_equal(it, ito), L.trlda_model_last_doc_kernel(m._handle).decode(),
                              L.trlda_model_last_split_workgroups(m._handle), sorted(lens)[-5:]))
                     bad = np.nonzero((np.abs(s - so) > 1e-7 * np.abs(so)).any(axis=0))[0]

@@ -30,6 +30,25 @@ def seeded_gamma(sampler, seed, K, B):
     return sampler.sample_gamma(int(K), int(B), 100) / 100.
 
 
+def asymmetric_case(K, V, lens, seed, zero_counts=False):
+    """Inputs that tell the topics apart (pure NumPy, no sampler): lambda = 200 Gamma(0.05, 1) + 0.01
+    -- peaked topics, entries over five decades -- and a per-topic alpha log-spaced over [2e-3, 4] in
+    a random topic order (lda.cpp:194 adds alpha_k, a K-vector).  Documents of `lens` distinct words
+    with counts 1 + randint(4); `zero_counts` sets about one entry in twenty to 0 (legal:
+    onlinelda_test.py:57).  -> lambda (K x V, F-order), alpha (K), indptr, ids, cnts, gamma0 (K x B)."""
+    rng = np.random.RandomState(int(seed))
+    lam = np.asfortranarray(200. * rng.gamma(.05, 1., (int(K), int(V))) + .01)
+    alpha = np.logspace(np.log10(2e-3), np.log10(4.), int(K))[rng.permutation(int(K))]
+    lens = [int(n) for n in lens]
+    ip = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ids = np.concatenate([rng.permutation(int(V))[:n] for n in lens] + [np.zeros(0, int)]).astype(np.int32)
+    cnts = (1 + rng.randint(4, size=int(ip[-1]))).astype(np.int32)
+    if zero_counts:
+        cnts[rng.rand(len(cnts)) < .05] = 0
+    g0 = np.asfortranarray(rng.gamma(100., .01, (int(K), len(lens))))
+    return lam, alpha, ip, ids, cnts, g0
+
+
 class HipSampler(object):
     """seed()/sample_gamma() through the product's C ABI (host-side, no GPU needed)."""
 

@@ -163,6 +163,41 @@ def test_estep_factor_exchange_equals_one_gpu(hip, oracle, tmp_path, world):
     assert int(cuts[-1]) == B
 
 
+def test_estep_factor_exchange_with_a_vector_alpha(hip, oracle, tmp_path):
+    """The same over two ranks with a per-topic alpha over three decades (lda.cpp:194 adds alpha_k;
+    every other case here has alpha = .1 for every topic, where a rank may read alpha at any topic's
+    index): gamma, iteration counts and statistics against the oracle, and bitwise the one-GPU E-step."""
+    from trlda_amd import _ffi
+    K, V, B, world = 100, 3000, 90, 2
+    csr = corpus(B, V, seed=811)
+    lam = random_lambda(K, V, 17)
+    alpha = np.logspace(np.log10(2e-3), np.log10(4.), K)[np.random.RandomState(4).permutation(K)]
+    g0 = np.asfortranarray(np.random.RandomState(3).gamma(100., .01, (K, B)))
+    np.save(str(tmp_path / "g0.npy"), g0)
+    cfg = dict(K=K, V=V, D=5000, alpha=alpha.tolist(), eta=.3, lambda_seed=17,
+               max_count=slot_bound([csr], K, world),
+               calls=[dict(kind="estep", B=B, corpus_seed=811, gamma0=str(tmp_path / "g0.npy"), max_iter=20)])
+    res = run_ranks(tmp_path, cfg, world)
+    g_ref, s_ref, it_ref = oracle.estep(lam, alpha, csr.indptr, csr.ids, csr.cnts, g0, 20, 1e-3, nthreads=8)
+    g_uni, _, it_uni = oracle.estep(lam, .1, csr.indptr, csr.ids, csr.cnts, g0, 20, 1e-3, nthreads=8)
+    assert relerr(g_uni, g_ref) > 1. and (it_uni != it_ref).any()        # (alpha matters here)
+    gamma = np.concatenate([r["gamma0"] for r in res], axis=1)
+    iters = np.concatenate([r["iters0"] for r in res])
+    assert np.array_equal(iters, it_ref)
+    assert relerr(gamma, g_ref) < TIGHT_RTOL
+    for r in res:
+        assert np.array_equal(r["sstats0"], res[0]["sstats0"])      # replicas: bitwise
+        assert int(r["exchanges"][0]) == 1
+    assert relerr(res[0]["sstats0"], s_ref, floor=1e-12) < TIGHT_RTOL
+    assert int(np.max(np.diff(csr.indptr))) <= 128                  # (the same document-kernel variant)
+    g_one = np.asfortranarray(g0.copy())
+    s_one = np.empty((K, V), order="F")
+    _ffi.check(hip.trlda_estep(K, V, B, csr.indptr, csr.ids, csr.cnts, lam, alpha, g_one, s_one, 20, 1e-3,
+                               None, 0))
+    assert np.array_equal(g_one, gamma)
+    assert np.array_equal(s_one, res[0]["sstats0"])
+
+
 @pytest.mark.parametrize("world,max_iter_tr", [(2, 3), (3, 0)])
 def test_online_update_dp_processes(hip, tmp_path, world, max_iter_tr):
     """OnlineLDA::updateParameters (onlinelda.cpp:53-111) twice over `world` ranks: every rank's

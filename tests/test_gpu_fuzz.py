@@ -26,6 +26,14 @@ def test_random_shapes_agree_with_the_oracle(hip, seed):
     assert worst_g < 1e-8 and worst_s < 1e-7
 
 
+def test_random_shapes_with_a_vector_alpha_and_peaked_topics(hip):
+    """the same random shapes with --asymmetric: alpha per topic over three decades and lambda with
+    entries over five, where the cases above have one alpha for every topic"""
+    import fuzz_estep
+    worst_g, worst_s = fuzz_estep.main(["--cases", "12", "--seed", "7", "--asymmetric"])
+    assert worst_g < 1e-8 and worst_s < 1e-7
+
+
 def test_a_batch_after_a_closed_model_leaves_the_callers_arrays_alone(hip):
     """Round 4's long fuzz run (seed 101): a model that owns its stream is closed, a later model's first
     batch reuses a device allocation whose guard event that stream had recorded -- the runtime followed
