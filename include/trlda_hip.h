@@ -626,6 +626,40 @@ int trlda_docindex_read_rows(trlda_docindex *index, int64_t first, int64_t count
 int trlda_docindex_set_slab_rows(trlda_docindex *index, int rows);
 int trlda_docindex_destroy(trlda_docindex *index);
 
+/* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
+ * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
+ * trlda_model_estep_host), then per document d and word w of the vocabulary
+ *   s(d, w) = sum_k (gamma_dk / sum_j gamma_dj) / rs_k * lambda_kw,  rs_k = sum_v lambda_kv,
+ * which is p(w | d) under the point estimates of trlda_model_predictive, formed on the matrix cores
+ * from lambda where it lies (no B x V matrix and no copy of lambda exist).  words_out (int32) and
+ * probs_out (fp64), host, B x top_n row-major: per document the first top_n words in the total order
+ * (s descending, word id ascending) and their s.  With exclude_seen != 0 the words document d has
+ * seen -- an entry (w, c) with c > 0, the rule of trlda_cooc_add; repeated entries count once,
+ * c <= 0 does not count -- are left out of its ranking; a document with fewer than top_n candidates
+ * pads its row with (-1, 0.0).  A document without entries is ranked from its gamma like any other;
+ * an empty batch writes nothing.  s depends on gamma_d, column w of lambda, the row sums and K alone:
+ * a document's row is bitwise the same alone and inside any batch, whatever the slab width, and two
+ * calls agree bitwise (the only atomics are the ORs that set the seen bits).
+ * TRLDA_ERR_ARG, before anything is waited for, copied or launched: K above TRLDA_VI_MAX_TOPICS,
+ * top_n outside [1, min(V, 100)], a batch of another V or device.  lambda, alpha and the counters are
+ * left alone; pending deferred statistics and stream lanes are settled first; afterwards
+ * trlda_model_get_sstats holds that E-step's statistics, as after trlda_model_word_topics.
+ * Synchronises.  No reference counterpart. */
+int trlda_model_recommend(trlda_model *model, const trlda_batch *batch, double *gamma, int top_n,
+                          int exclude_seen, int max_iter, double threshold, int32_t *words_out,
+                          double *probs_out);
+/* The same rows from B gamma columns the caller keeps on the device (K x B, read only, not validated;
+ * any K >= 1): no E-step runs, nothing is drawn, the model's statistics keep what they held.  With a
+ * batch, which must hold B documents (else TRLDA_ERR_SHAPE), its seen words are left out; with NULL
+ * every word is ranked.  words_dev / probs_dev: device arrays of B x top_n elements.  The same checks
+ * otherwise.  Enqueued on the model's stream; does not synchronise.  On the same gamma bitwise the
+ * rows of trlda_model_recommend.  No reference counterpart. */
+int trlda_model_recommend_dev(trlda_model *model, const trlda_batch *batch_or_null, const double *gamma_dev,
+                              int B, int top_n, int32_t *words_dev, double *probs_dev);
+/* A/B switch for tests and measurements: words per workgroup of the ranking (a positive multiple of
+ * 16; 0: the default, 2048).  The results do not depend on it.  No reference counterpart. */
+int trlda_model_set_recommend_slab_words(trlda_model *model, int words);
+
 /* Distances between topics (csrc/topicdist_kernels.h).  A topic is p_i = lambda_i /
  * S_i, S_i = sum_v lambda_iv; the second lambda, mu (K2 x V), gives q_j = mu_j / T_j.  dist_out (K x K2
  * column-major, host: [i + K * j]) =

@@ -155,6 +155,9 @@ _SIGNATURES = {
     "trlda_model_left_to_right": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, vp]),
     "trlda_model_word_topics": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp]),
     "trlda_model_word_topics_dev": (C.c_int, [vp, vp, vp, C.c_int, vp, vp]),
+    "trlda_model_recommend": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
+    "trlda_model_recommend_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "trlda_model_set_recommend_slab_words": (C.c_int, [vp, C.c_int]),
     "trlda_model_top_words": (C.c_int, [vp, C.c_int, i32p]),
     "trlda_cooc_create": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
     "trlda_cooc_add": (C.c_int, [vp, vp]),

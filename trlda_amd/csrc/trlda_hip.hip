@@ -54,6 +54,7 @@
 #include "l2r_kernels.h"
 #include "wordtopics_kernels.h"
 #include "docindex_kernels.h"
+#include "recommend_kernels.h"
 #include "topicdist_kernels.h"
 
 namespace {
@@ -695,6 +696,14 @@ struct trlda_model {
         DevBuf<double> probs;
         DevBuf<int32_t> topics;
     } wordtopics;
+    // the ranked words of a document (recommend_kernels.h, trlda_model_recommend): the documents' q
+    // rows, the seen bits (B x ceil(V / 32)), the slabs' lists, and the host form's output staging
+    struct {
+        DevBuf<double> qrows, cand_s, probs;
+        DevBuf<int32_t> cand_i, words;
+        DevBuf<unsigned int> seen;
+        int slab_words = 0;                     // 0: kRecommendSlabWords (trlda_model_set_recommend_slab_words)
+    } recommend;
 };
 
 namespace {
@@ -6092,6 +6101,187 @@ int trlda_docindex_destroy(trlda_docindex *x)
         (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
     delete x;
     return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the words a document most likely holds next (csrc/recommend_kernels.h) ----
+
+namespace {
+
+int recommend_slab_words(const trlda_model *m)
+{
+    return m->recommend.slab_words > 0 ? m->recommend.slab_words : trlda::kRecommendSlabWords;
+}
+
+// what both forms check before anything is waited for, drawn, copied or launched
+int recommend_checks(const trlda_model *m, const trlda_batch *b, int top_n)
+{
+    if (top_n < 1 || top_n > trlda::kRecommendMaxTop || top_n > m->V)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
+    const int sw = recommend_slab_words(m);
+    if ((m->V + sw - 1) / sw > 65535)                    // (grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_model_set_recommend_slab_words");
+    if (b) {
+        if (b->V != m->V)
+            return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+        if (b->device != m->device)
+            return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    }
+    return TRLDA_OK;
+}
+
+template <int SW>
+int recommend_launch_query(trlda_model *m, int B, int top_n, int slab_words, int slabs, const unsigned int *seen,
+                           int nw)
+{
+    auto &g = m->recommend;
+    const size_t lds = trlda::recommend_query_lds(SW, top_n);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::recommend_query_kernel<SW>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::recommend_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
+                       dim3(trlda::kRecommendThreads), lds, m->stream, m->K, (m->K + 3) / 4 * 4, m->V, B, top_n,
+                       slab_words, m->lambda, g.qrows, seen, nw, g.cand_s, g.cand_i);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The ranking on the model's stream for the B gamma columns at gamma_dev, into words_dev / probs_dev
+// (B x top_n): the row sums of lambda formed from lambda itself as in trlda_model_word_topics (both
+// forms must give the same bits), the q rows, the seen bits of `seen_of` (nullptr: nothing is left
+// out; else a batch of B documents that has been begun), the slabs' lists and their merge.  The
+// checks have been made; B > 0.
+int recommend_device(trlda_model *m, const trlda_batch *seen_of, const double *gamma_dev, int B, int top_n,
+                     int32_t *words_dev, double *probs_dev)
+{
+    auto &g = m->recommend;
+    const int K = m->K, V = m->V, Kp = (K + 3) / 4 * 4;
+    const int sw = recommend_slab_words(m);
+    const int slabs = (V + sw - 1) / sw;
+    const int nw = (V + 31) / 32;
+    const size_t cells = (size_t)B * top_n;
+    const bool exclude = seen_of && seen_of->nnz > 0;
+    const double *rs = nullptr;
+    int rc = lambda_rowsums(m, &rs);
+    if (!rc) rc = g.qrows.grow((size_t)B * Kp);
+    if (!rc) rc = g.cand_s.grow(cells * slabs);
+    if (!rc) rc = g.cand_i.grow(cells * slabs);
+    if (!rc && exclude) rc = g.seen.grow((size_t)B * nw);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kRecommendThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::recommend_rows_kernel, dim3((B + per_wg - 1) / per_wg), dim3(trlda::kRecommendThreads),
+                       0, m->stream, K, Kp, B, gamma_dev, rs, g.qrows);
+    HIP_TRY(hipGetLastError());
+    if (exclude) {
+        HIP_TRY(hipMemsetAsync(g.seen, 0, (size_t)B * nw * sizeof(unsigned int), m->stream));
+        hipLaunchKernelGGL(trlda::recommend_seen_kernel, dim3((B + per_wg - 1) / per_wg),
+                           dim3(trlda::kRecommendThreads), 0, m->stream, B, V, nw, seen_of->indptr, seen_of->ids,
+                           seen_of->cnts, g.seen);
+        HIP_TRY(hipGetLastError());
+    }
+    const unsigned int *seen = exclude ? (const unsigned int *)g.seen : nullptr;
+    // (128 documents per workgroup while their lists fit beside the operands, 64 beyond)
+    rc = top_n <= trlda::kRecommendWideMaxTop ? recommend_launch_query<2>(m, B, top_n, sw, slabs, seen, nw)
+                                              : recommend_launch_query<1>(m, B, top_n, sw, slabs, seen, nw);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::recommend_merge_kernel, dim3(B), dim3(trlda::kRecommendThreads), 0, m->stream, B,
+                       top_n, slabs, g.cand_s, g.cand_i, words_dev, probs_dev);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_set_recommend_slab_words(trlda_model *m, int words)
+{
+    if (!m || words < 0 || words % 16)
+        return fail(TRLDA_ERR_ARG, "slab words: 0 (default) or a positive multiple of 16");
+    m->recommend.slab_words = words;
+    return TRLDA_OK;
+}
+
+// The ranked words from a gamma that is already on the device (no E-step): enqueued on the model's
+// stream, not synchronised
+int trlda_model_recommend_dev(trlda_model *m, const trlda_batch *b, const double *gamma_dev, int B, int top_n,
+                              int32_t *words_dev, double *probs_dev)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "a negative number of documents");
+    if (int rc_arg = recommend_checks(m, b, top_n))
+        return rc_arg;
+    if (b && b->B != B)
+        return fail(TRLDA_ERR_SHAPE, "the batch holds another number of documents than gamma");
+    if (B > 0 && (!gamma_dev || !words_dev || !probs_dev))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / words / probs");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc || B == 0)
+        return rc;
+    const bool exclude = b && b->nnz > 0;
+    if (exclude)
+        rc = batch_begin(m, b);
+    if (!rc) rc = recommend_device(m, exclude ? b : nullptr, gamma_dev, B, top_n, words_dev, probs_dev);
+    if (rc)
+        return rc;
+    if (exclude)
+        (void)batch_end(m, b);
+    return TRLDA_OK;
+}
+
+// The E-step of trlda_model_estep_host on the batch, then the ranking with its gamma
+int trlda_model_recommend(trlda_model *m, const trlda_batch *b, double *gamma, int top_n, int exclude_seen,
+                          int max_iter, double threshold, int32_t *words_out, double *probs_out)
+{
+    if (!m || !b)
+        return fail(TRLDA_ERR_ARG, "NULL model / batch");
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (int rc_arg = recommend_checks(m, b, top_n))
+        return rc_arg;
+    if (b->B > 0 && (!gamma || !words_out || !probs_out))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / words / probs");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int K = m->K, B = b->B;
+    if (B <= 0)
+        return TRLDA_OK;
+    rc = ensure_update_workspace(m, B);
+    if (rc)
+        return rc;
+    auto &g = m->recommend;
+    const size_t cells = (size_t)B * top_n;
+    rc = g.words.grow(cells);
+    if (!rc) rc = g.probs.grow(cells);
+    if (rc)
+        return rc;
+    const size_t gbytes = (size_t)K * B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc) rc = recommend_device(m, exclude_seen ? b : nullptr, m->gamma, B, top_n, g.words, g.probs);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(words_out, g.words, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipMemcpyAsync(probs_out, g.probs, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
 }
 
 }  // extern "C"

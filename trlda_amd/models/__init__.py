@@ -128,6 +128,46 @@ def _greedy_match(dist):
     return match, best
 
 
+RECOMMEND_MAX_TOP_N = 100
+
+
+def _seen_keys(indptr, ids, cnts, num_words):
+    """The sorted distinct keys ``d * num_words + w`` of the entries ``(w, c)`` with ``c > 0`` of a
+    CSR: the (document, word) pairs a part has seen."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    ids = np.asarray(ids, dtype=np.int64)
+    doc = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    keep = np.asarray(cnts) > 0
+    return np.unique(doc[keep] * np.int64(num_words) + ids[keep])
+
+
+def _recall_at(words, observed, heldout, num_words):
+    """Recall of recommended word ids against held-out words (LDA.recall_at): host arithmetic on
+    B x top_n ids.  ``words``: int B x top_n, -1 where a row is padded; ``observed`` and ``heldout``:
+    the two parts as CSR triples ``(indptr, ids, cnts)`` of B documents each.  A word is relevant
+    to document d when ``heldout_d`` has it with a positive count and ``observed_d`` has not seen it
+    (no entry with a positive count); repeated entries count once.  Returns ``(recall, hits,
+    relevant)``: per document the number of relevant words and how many of them are among its
+    recommended ids (int64, length B), and the mean of ``hits / relevant`` over the documents with
+    ``relevant > 0``, added in document order.  RuntimeError when there is no such document."""
+    words = np.asarray(words, dtype=np.int64)
+    B = words.shape[0]
+    V = np.int64(num_words)
+    if len(observed[0]) - 1 != B or len(heldout[0]) - 1 != B:
+        raise RuntimeError("Observed and held-out documents should be equal in number.")
+    want = np.setdiff1d(_seen_keys(*heldout, num_words=V), _seen_keys(*observed, num_words=V),
+                        assume_unique=True)
+    relevant = np.bincount(want // V, minlength=B).astype(np.int64)
+    row = np.repeat(np.arange(B, dtype=np.int64), words.shape[1]).reshape(words.shape)
+    given = np.unique((row * V + words)[words >= 0])
+    hits = np.bincount(np.intersect1d(given, want, assume_unique=True) // V, minlength=B).astype(np.int64)
+    keep = relevant > 0
+    if not keep.any():
+        raise RuntimeError("There are no held-out words that the observed parts have not seen.")
+    ratio = hits[keep] / relevant[keep].astype(np.float64)
+    return float(np.cumsum(ratio)[-1] / ratio.size), hits, relevant
+
+
 class Distribution(object):
     """Abstract base (reference include/distribution.h, distributioninterface.cpp)."""
 
@@ -707,6 +747,153 @@ class LDA(Distribution):
         if return_gamma:
             return indptr, topics, probs, gamma
         return indptr, topics, probs
+
+    # -- the words a document most likely holds next (csrc/recommend_kernels.h) --------------------
+    def _recommend_top_n(self, top_n):
+        top_n = operator.index(top_n)
+        if not 1 <= top_n <= min(self._V, RECOMMEND_MAX_TOP_N):
+            raise RuntimeError("`top_n` should lie between 1 and min(num_words, %d)." % RECOMMEND_MAX_TOP_N)
+        return top_n
+
+    def recommend(self, docs, top_n=10, exclude_seen=True, latents=None, max_iter=100, threshold=0.001,
+                  return_gamma=False):
+        """The ``top_n`` words each document of ``docs`` most likely holds next.  VI on ``docs`` (a
+        list, ``DocumentList`` or ``DeviceBatch``) with lambda fixed (from ``latents`` as gamma0,
+        else a random gamma drawn from the seeded stream as ``update_variables`` draws it), then
+        per document d and word w of the vocabulary, on the GPU,
+
+            p(w | d) = sum_k (gamma_dk / sum_j gamma_dj) (lambda_kw / sum_v lambda_kv),
+
+        the quantity ``predictive_log_likelihood`` scores held-out words by, ranked per document.
+        With users as documents and items as words (``trlda.utils.load_users``) these are the
+        items a user does not have yet and most likely wants.
+
+        Returns ``(words, probs)``, int32 and float64 of shape (B, top_n): per document the words
+        in decreasing p(w | d), equal values by smaller word id first, and their p.  With
+        ``exclude_seen`` (default) the words a document has seen -- a pair ``(w, c)`` with
+        ``c > 0``; repeated pairs count once, ``c <= 0`` does not count -- are left out of its
+        ranking; a document with fewer than ``top_n`` words left pads its row with ``(-1, 0.0)``.
+        An empty document is ranked from its gamma like any other.  ``1 <= top_n <= min(num_words,
+        100)``, else RuntimeError.  With ``return_gamma=True`` gamma (K x B) is appended.  A
+        document's row does not depend on the other documents of ``docs``, and two calls agree
+        bitwise.  lambda, alpha, eta and the update counters stay as they are."""
+        top_n = self._recommend_top_n(top_n)
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        batch, owned = self._batch(docs)
+        try:
+            self._settle()
+            B = len(batch)
+            L = _ffi.lib()
+            if latents is not None:
+                try:
+                    g = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if g.ndim == 1:
+                    g = g.reshape(-1, 1, order="F")
+                if g.ndim != 2 or g.shape != (self._K, B):
+                    raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+                gamma = np.asfortranarray(g)
+            else:
+                gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                L.trlda_sample_gamma_init(self._K, B, gamma)          # lda.cpp:135
+            words = np.empty((B, top_n), dtype=np.int32)
+            probs = np.empty((B, top_n), dtype=np.float64)
+            _ffi.check(L.trlda_model_recommend(self._handle, batch.handle, gamma.ctypes.data, top_n,
+                                               1 if exclude_seen else 0, int(max_iter), float(threshold),
+                                               words.ctypes.data, probs.ctypes.data))
+        finally:
+            if owned:
+                batch.close()
+        if return_gamma:
+            return words, probs, gamma
+        return words, probs
+
+    def recommend_gamma(self, gamma, top_n=10, docs=None):
+        """The ranking of ``recommend`` for documents given by their ``gamma`` (K x B, every value
+        finite and positive, else RuntimeError; not an array, TypeError): no E-step runs and
+        nothing is drawn, so any number of topics is taken, and any positive K x B array serves
+        -- the ``alpha + n`` of a Gibbs or CVB0 run as well.  ``docs`` (a list, ``DocumentList``
+        or ``DeviceBatch`` of B documents) gives the seen words that are left out; without it
+        every word is ranked.  Returns ``(words, probs)`` as ``recommend`` does -- the same
+        formula, tie rule (smaller word id first) and pad ``(-1, 0.0)`` -- and on the gamma
+        ``recommend`` returned the same bits.  lambda, alpha, eta, the update counters, the
+        model's statistics and the seeded stream stay as they are."""
+        top_n = self._recommend_top_n(top_n)
+        try:
+            g = np.array(gamma, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`gamma` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Gamma has wrong dimensionality.")
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise RuntimeError("Gamma should be finite and positive.")
+        g = np.asfortranarray(g)
+        B = g.shape[1]
+        if docs is not None and len(docs) != B:
+            raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+        words = np.empty((B, top_n), dtype=np.int32)
+        probs = np.empty((B, top_n), dtype=np.float64)
+        if B == 0:
+            return words, probs
+        batch, owned = self._batch(docs) if docs is not None else (None, False)
+        L = _ffi.lib()
+        ptrs = []
+        try:
+            self._settle()
+            for nbytes in (g.nbytes, words.nbytes, probs.nbytes):
+                ptr = _ffi.vp()
+                _ffi.check(L.trlda_dev_alloc(self._device, nbytes, C.byref(ptr)))
+                ptrs.append(ptr)
+            _ffi.check(L.trlda_dev_upload(self._device, ptrs[0], g.ctypes.data, g.nbytes))
+            _ffi.check(L.trlda_model_recommend_dev(self._handle, None if batch is None else batch.handle,
+                                                   ptrs[0], B, top_n, ptrs[1], ptrs[2]))
+            _ffi.check(L.trlda_model_synchronize(self._handle))
+            _ffi.check(L.trlda_dev_download(self._device, words.ctypes.data, ptrs[1], words.nbytes))
+            _ffi.check(L.trlda_dev_download(self._device, probs.ctypes.data, ptrs[2], probs.nbytes))
+        finally:
+            for ptr in ptrs:
+                L.trlda_dev_free(self._device, ptr)
+            if owned:
+                batch.close()
+        return words, probs
+
+    def recall_at(self, observed, heldout, top_n=20, latents=None, max_iter=100, threshold=0.001,
+                  return_documents=False):
+        """Recall@``top_n`` of the recommendations against held-out words.  ``observed`` and
+        ``heldout`` hold the same documents' two parts (``trlda_amd.utils.split_documents``) as
+        lists, ``DocumentList`` or ``DeviceBatch``, equal in number (else RuntimeError).
+        ``recommend(observed, top_n, exclude_seen=True, ...)`` ranks p(w | d) on the GPU, equal
+        values by smaller word id first and short rows padded with -1; then per document, on the
+        host,
+
+            relevant_d = distinct words with a positive count in heldout_d that observed_d has not seen,
+            hits_d     = how many of them are among the recommended ids,
+            recall     = mean of hits_d / relevant_d over the documents with relevant_d > 0.
+
+        RuntimeError when no document has a relevant word.  With ``return_documents=True`` returns
+        ``(recall, hits, relevant)``, the last two int64 of length B.  lambda, alpha, eta and the
+        update counters stay as they are."""
+        top_n = self._recommend_top_n(top_n)
+        if len(observed) != len(heldout):
+            raise RuntimeError("Observed and held-out documents should be equal in number.")
+        _ffi.check_vi_topics(self._K)                               # (before the upload and the draw)
+        held = as_csr(heldout)
+        batch, owned = self._batch(observed)
+        try:
+            words, _ = self.recommend(batch, top_n=top_n, exclude_seen=True, latents=latents,
+                                      max_iter=max_iter, threshold=threshold)
+            obs = batch.csr
+        finally:
+            if owned:
+                batch.close()
+        recall, hits, relevant = _recall_at(words, (obs.indptr, obs.ids, obs.cnts),
+                                            (held.indptr, held.ids, held.cnts), self._V)
+        if return_documents:
+            return recall, hits, relevant
+        return recall
 
     # -- nearest documents in topic space (csrc/docindex_kernels.h) ---------------------------------
     def _register_index(self, index):
