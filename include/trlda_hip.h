@@ -660,6 +660,59 @@ int trlda_model_recommend_dev(trlda_model *model, const trlda_batch *batch_or_nu
  * 16; 0: the default, 2048).  The results do not depend on it.  No reference counterpart. */
 int trlda_model_set_recommend_slab_words(trlda_model *model, int words);
 
+/* Topic words by relevance, corpus terms by saliency, and the topic prevalence of a corpus
+ * (csrc/relevance_kernels.h).  With R_k = sum_w lambda_kw and topic weights pi
+ * (topic_weights == NULL: pi_k = R_k / sum_j R_j; else K host values, finite and > 0, normalised to
+ * sum 1 on the host):
+ *   p_w = sum_k c_k lambda_kw, c_k = pi_k / R_k          the marginal word probability
+ *   r_kw = log lambda_kw - log R_k - (1 - weight) log p_w  relevance (Sievert & Shirley 2014)
+ *   D_w = sum_k q_kw (log q_kw - log pi_k), q_kw = c_k lambda_kw / p_w   distinctiveness, KL(p(k|w) || pi)
+ *   S_w = p_w D_w                                        saliency (Chuang, Manning & Heer 2012)
+ * The sums over k run in an order that depends on K alone, the row sums in an order that depends on K
+ * and V; no atomics: every result repeats bitwise.  A lambda with an element <= 0 or not finite fails
+ * each of the three calls with TRLDA_ERR_VALUE ("relevance needs a positive, finite lambda") and
+ * nothing is written to the outputs.  TRLDA_ERR_ARG, before anything is allocated or launched: a NULL
+ * output, a weight that is not finite or <= 0, top_n outside [1, min(V, 100)], weight outside [0, 1].
+ * lambda, alpha, the counters, the statistics and the seeded stream are left alone; pending deferred
+ * statistics and stream lanes are settled first.  Each call synchronises.  No reference counterpart. */
+
+/* p_out, distinct_out, saliency_out (V each, host) = p_w, D_w, S_w. */
+int trlda_model_word_stats(trlda_model *model, const double *topic_weights, double *p_out,
+                           double *distinct_out, double *saliency_out);
+/* words_out (K x top_n int32, host, topic-major: [k * top_n + r]) = the top_n word ids of each topic
+ * in decreasing r_kw, equal values by smaller id first -- np.lexsort((arange(V), -r[k]))[:top_n], the
+ * tie rule of trlda_model_top_words, whose order weight = 1 reproduces wherever log keeps distinct
+ * lambda apart; scores_out (K x top_n fp64, or NULL) = their r_kw. */
+int trlda_model_relevant_words(trlda_model *model, int top_n, double weight, const double *topic_weights,
+                               int32_t *words_out, double *scores_out);
+/* words_out (top_n int32, host) = the top_n word ids in decreasing S_w, equal values by smaller id
+ * first; saliency_out (top_n fp64, or NULL) = their S_w. */
+int trlda_model_salient_words(trlda_model *model, int top_n, const double *topic_weights,
+                              int32_t *words_out, double *saliency_out);
+
+/* A prevalence accumulator for `model`: pi_k ~ sum_d N_d gamma_dk / sum_j gamma_dj over the documents
+ * added, N_d = the sum of document d's positive counts (weight_by_length == 0: 1); a document without
+ * a positive count is skipped.  K fp64 sums stay on the device between batches: one addition per
+ * document per topic in the order the documents are added, each document's sum_j gamma_dj in an order
+ * that depends on K alone, so the result is bitwise independent of how the documents are cut into
+ * batches.  It runs on the model's stream and must be destroyed before the model. */
+typedef struct trlda_prevalence trlda_prevalence;
+int trlda_prevalence_create(trlda_model *model, int weight_by_length, trlda_prevalence **out);
+/* An E-step on the batch as trlda_model_estep_host runs it (gamma: K x B host, in: gamma0, out:
+ * gamma; afterwards trlda_model_get_sstats holds that E-step's statistics), then its documents are
+ * added.  TRLDA_ERR_ARG, before anything is waited for, copied or launched: K above
+ * TRLDA_VI_MAX_TOPICS, a batch of another V or device.  Synchronises. */
+int trlda_prevalence_add(trlda_prevalence *prevalence, const trlda_batch *batch, double *gamma, int max_iter,
+                         double threshold);
+/* Adds the batch's documents with a gamma the caller keeps on the device (K x B, read only, not
+ * validated; any K >= 1): no E-step runs, nothing is drawn.  Enqueued on the model's stream; does not
+ * synchronise.  On the same gamma bitwise the sums of trlda_prevalence_add. */
+int trlda_prevalence_add_dev(trlda_prevalence *prevalence, const trlda_batch *batch, const double *gamma_dev);
+/* prevalence_out (K, host) = the sums so far normalised to sum 1 (on the host, one rounding each);
+ * *num_docs = the documents that contributed.  None: TRLDA_ERR_VALUE.  Synchronises. */
+int trlda_prevalence_read(trlda_prevalence *prevalence, double *prevalence_out, int64_t *num_docs);
+int trlda_prevalence_destroy(trlda_prevalence *prevalence);
+
 /* Distances between topics (csrc/topicdist_kernels.h).  A topic is p_i = lambda_i /
  * S_i, S_i = sum_v lambda_iv; the second lambda, mu (K2 x V), gives q_j = mu_j / T_j.  dist_out (K x K2
  * column-major, host: [i + K * j]) =

@@ -159,6 +159,14 @@ _SIGNATURES = {
     "trlda_model_recommend_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "trlda_model_set_recommend_slab_words": (C.c_int, [vp, C.c_int]),
     "trlda_model_top_words": (C.c_int, [vp, C.c_int, i32p]),
+    "trlda_model_word_stats": (C.c_int, [vp, vp, vp, vp, vp]),
+    "trlda_model_relevant_words": (C.c_int, [vp, C.c_int, C.c_double, vp, vp, vp]),
+    "trlda_model_salient_words": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "trlda_prevalence_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "trlda_prevalence_add": (C.c_int, [vp, vp, vp, C.c_int, C.c_double]),
+    "trlda_prevalence_add_dev": (C.c_int, [vp, vp, vp]),
+    "trlda_prevalence_read": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
+    "trlda_prevalence_destroy": (C.c_int, [vp]),
     "trlda_cooc_create": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
     "trlda_cooc_add": (C.c_int, [vp, vp]),
     "trlda_cooc_read": (C.c_int, [vp, i64p, i64p, C.POINTER(C.c_int64)]),

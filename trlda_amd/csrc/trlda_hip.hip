@@ -55,6 +55,7 @@
 #include "wordtopics_kernels.h"
 #include "docindex_kernels.h"
 #include "recommend_kernels.h"
+#include "relevance_kernels.h"
 #include "topicdist_kernels.h"
 
 namespace {
@@ -704,6 +705,15 @@ struct trlda_model {
         DevBuf<unsigned int> seen;
         int slab_words = 0;                     // 0: kRecommendSlabWords (trlda_model_set_recommend_slab_words)
     } recommend;
+    // relevance and saliency (relevance_kernels.h, trlda_model_relevant_words, _salient_words,
+    // _word_stats): the given weights, c | log R | log pi, p | D | S | log p, the bad-lambda flag, the
+    // levels' candidates and the ranked ids and scores
+    struct {
+        DevBuf<double> pi, coef, stats, scores;
+        DevBuf<uint64_t> keys;
+        DevBuf<int32_t> ids;
+        DevBuf<int> flag;
+    } relevance;
 };
 
 namespace {
@@ -6282,6 +6292,417 @@ int trlda_model_recommend(trlda_model *m, const trlda_batch *b, double *gamma, i
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
     HIP_TRY(hipGetLastError());
     return check_split_exchange(m);
+}
+
+}  // extern "C"
+
+// ---- relevance, saliency and topic prevalence (csrc/relevance_kernels.h) ----
+
+namespace {
+
+int relevance_topn_check(const trlda_model *m, int top_n)
+{
+    if (top_n < 1 || top_n > trlda::kTopnMax || top_n > m->V)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
+    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    if (m->K > 65535 || tiles > 65535)                   // (grid dimensions y)
+        return fail(TRLDA_ERR_ARG, "num_topics or num_words too large for the top-word kernels");
+    return TRLDA_OK;
+}
+
+// the given topic weights, checked and normalised to sum 1 (in long double: one rounding each) into
+// `pi`; no weights: `pi` stays empty
+int relevance_weights(const trlda_model *m, const double *topic_weights, std::vector<double> &pi)
+{
+    pi.clear();
+    if (!topic_weights)
+        return TRLDA_OK;
+    long double sum = 0.0L;
+    for (int k = 0; k < m->K; ++k) {
+        const double w = topic_weights[k];
+        if (!(w > 0.0) || !std::isfinite(w))
+            return fail(TRLDA_ERR_ARG, "topic weights should be finite and positive");
+        sum += w;
+    }
+    if (!std::isfinite((double)sum))
+        return fail(TRLDA_ERR_ARG, "topic weights should be finite and positive");
+    pi.resize((size_t)m->K);
+    for (int k = 0; k < m->K; ++k)
+        pi[(size_t)k] = (double)((long double)topic_weights[k] / sum);
+    return TRLDA_OK;
+}
+
+// The column pass on the model's stream: the row sums of lambda formed from lambda itself
+// (lambda_rowsums: an order that depends on K and V only, whatever an E-step left behind), c, log R
+// and log pi, then p, D, S and log p of every word into relevance.stats and the flag.
+int relevance_stats(trlda_model *m, const std::vector<double> &pi)
+{
+    auto &g = m->relevance;
+    const int K = m->K, V = m->V;
+    const double *rs = nullptr;
+    int rc = lambda_rowsums(m, &rs);
+    if (!rc) rc = g.coef.grow(3 * (size_t)K);
+    if (!rc) rc = g.stats.grow(4 * (size_t)V);
+    if (!rc) rc = g.flag.grow(1);
+    if (!rc && !pi.empty()) rc = g.pi.grow((size_t)K);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
+    if (!pi.empty()) {
+        // (waited for here: `pi` is the caller's and need not outlive an early return)
+        hipError_t e1 = hipMemcpyAsync(g.pi, pi.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, m->stream);
+        hipError_t e2 = hipStreamSynchronize(m->stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+    }
+    hipLaunchKernelGGL(trlda::relevance_coef_kernel, dim3(1), dim3(trlda::kWave), 0, m->stream, K, rs,
+                       pi.empty() ? (const double *)nullptr : (const double *)g.pi, g.coef.get());
+    HIP_TRY(hipGetLastError());
+    constexpr int per_wg = trlda::kRelevanceThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::relevance_column_kernel, dim3((V + per_wg - 1) / per_wg),
+                       dim3(trlda::kRelevanceThreads), 0, m->stream, K, V, m->lambda, g.coef.get(), g.stats.get(),
+                       g.flag.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// waits for the stream and fails when the column pass met a bad lambda
+int relevance_settle(trlda_model *m)
+{
+    int flag = 0;
+    hipError_t e1 = hipMemcpyAsync(&flag, m->relevance.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    if (flag)
+        return fail(TRLDA_ERR_VALUE, "relevance needs a positive, finite lambda");
+    return TRLDA_OK;
+}
+
+// room for the selection of `rows` rows: the first level's candidates and the later levels'
+// (ping-pong) as in trlda_model_top_words, the ranked ids behind them, and the scores
+int relevance_select_room(trlda_model *m, int rows, int n, size_t &off_b, size_t &cap)
+{
+    auto &g = m->relevance;
+    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    const size_t c1 = (size_t)tiles * n;
+    const size_t c2 = (c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;
+    off_b = (size_t)rows * c1;
+    cap = off_b + (size_t)rows * c2;
+    int rc = g.keys.grow(cap);
+    if (!rc) rc = g.ids.grow(cap + (size_t)rows * n);
+    if (!rc) rc = g.scores.grow((size_t)rows * n);
+    return rc;
+}
+
+// the levels after the first: topn_merge_kernel while a row has more than 1024 candidates, then the
+// level that ranks and gives the scores (ids at relevance.ids + cap, scores at relevance.scores)
+int relevance_select_levels(trlda_model *m, int rows, int n, size_t off_b, size_t cap)
+{
+    auto &g = m->relevance;
+    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    uint64_t *ik = g.keys, *ok = g.keys + off_b;
+    int32_t *ii = g.ids, *oi = g.ids + off_b;
+    size_t c = (size_t)tiles * n;
+    while (c > (size_t)trlda::kTopnGroup) {
+        const size_t groups = (c + trlda::kTopnGroup - 1) / trlda::kTopnGroup;
+        hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3((unsigned)groups, rows), dim3(trlda::kWave), 0,
+                           m->stream, n, (int)c, ik, ii, ok, oi, (int32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+        std::swap(ik, ok);
+        std::swap(ii, oi);
+        c = groups * n;
+    }
+    hipLaunchKernelGGL(trlda::relevance_final_kernel, dim3(rows), dim3(trlda::kWave), 0, m->stream, n, (int)c,
+                       ik, ii, g.ids + cap, g.scores.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// the ranked ids (and scores, unless null) of `rows` rows to the host, once the flag has been read
+int relevance_results(trlda_model *m, size_t cells, size_t cap, int32_t *words_out, double *scores_out)
+{
+    auto &g = m->relevance;
+    hipError_t e1 = hipMemcpyAsync(words_out, g.ids + cap, cells * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = scores_out ? hipMemcpyAsync(scores_out, g.scores, cells * sizeof(double),
+                                                hipMemcpyDeviceToHost, m->stream)
+                               : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_word_stats(trlda_model *m, const double *topic_weights, double *p_out, double *distinct_out,
+                           double *saliency_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!p_out || !distinct_out || !saliency_out)
+        return fail(TRLDA_ERR_ARG, "NULL output");
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    int rc = check_model(m);
+    if (!rc) rc = relevance_stats(m, pi);
+    if (!rc) rc = relevance_settle(m);
+    if (rc)
+        return rc;
+    const size_t V = (size_t)m->V, bytes = V * sizeof(double);
+    const double *st = m->relevance.stats;
+    hipError_t e1 = hipMemcpyAsync(p_out, st, bytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(distinct_out, st + V, bytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipMemcpyAsync(saliency_out, st + 2 * V, bytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    return TRLDA_OK;
+}
+
+int trlda_model_relevant_words(trlda_model *m, int top_n, double weight, const double *topic_weights,
+                               int32_t *words_out, double *scores_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!words_out)
+        return fail(TRLDA_ERR_ARG, "words_out is NULL");
+    if (int rc_arg = relevance_topn_check(m, top_n))
+        return rc_arg;
+    if (!(weight >= 0.0 && weight <= 1.0))
+        return fail(TRLDA_ERR_ARG, "weight must lie in [0, 1]");
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    auto &g = m->relevance;
+    const int K = m->K, V = m->V, n = top_n;
+    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    size_t off_b = 0, cap = 0;
+    rc = relevance_select_room(m, K, n, off_b, cap);
+    if (!rc) rc = relevance_stats(m, pi);
+    if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::relevance_tile_kernel),
+                                     (size_t)trlda::kRelevanceTileLds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::relevance_tile_kernel,
+                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, tiles),
+                       dim3(trlda::kTopnThreads), (size_t)trlda::kRelevanceTileLds, m->stream, K, V, n, 1.0 - weight,
+                       m->lambda, g.coef + (size_t)K, g.stats + 3 * (size_t)V, g.keys.get(), g.ids.get());
+    HIP_TRY(hipGetLastError());
+    rc = relevance_select_levels(m, K, n, off_b, cap);
+    if (!rc) rc = relevance_settle(m);
+    if (rc)
+        return rc;
+    return relevance_results(m, (size_t)K * n, cap, words_out, scores_out);
+}
+
+int trlda_model_salient_words(trlda_model *m, int top_n, const double *topic_weights, int32_t *words_out,
+                              double *saliency_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!words_out)
+        return fail(TRLDA_ERR_ARG, "words_out is NULL");
+    if (int rc_arg = relevance_topn_check(m, top_n))
+        return rc_arg;
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    auto &g = m->relevance;
+    const int V = m->V, n = top_n;
+    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    size_t off_b = 0, cap = 0;
+    rc = relevance_select_room(m, 1, n, off_b, cap);
+    if (!rc) rc = relevance_stats(m, pi);
+    const size_t lds = (size_t)trlda::kTopnTileTopics * trlda::kTopnTileStride * sizeof(uint64_t);
+    if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topn_tile_kernel), lds);
+    if (rc)
+        return rc;
+    // (the 1 x V vector S as a one-topic lambda)
+    hipLaunchKernelGGL(trlda::topn_tile_kernel, dim3(1, tiles), dim3(trlda::kTopnThreads), lds, m->stream, 1, V, n,
+                       g.stats + 2 * (size_t)V, g.keys.get(), g.ids.get());
+    HIP_TRY(hipGetLastError());
+    rc = relevance_select_levels(m, 1, n, off_b, cap);
+    if (!rc) rc = relevance_settle(m);
+    if (rc)
+        return rc;
+    return relevance_results(m, (size_t)n, cap, words_out, saliency_out);
+}
+
+}  // extern "C"
+
+// The prevalence accumulator: K fp64 sums and the number of documents that contributed, on the
+// device between batches, and the per-document staging of a batch
+struct trlda_prevalence {
+    trlda_model *model = nullptr;
+    int by_length = 1;
+    DevBuf<double> sums, nd, inv;
+    DevBuf<long long> docs;
+};
+
+namespace {
+
+int prevalence_checks(const trlda_prevalence *p, const trlda_batch *b)
+{
+    if (!p || !b)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
+    if (b->V != p->model->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != p->model->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    return TRLDA_OK;
+}
+
+// the two passes over a batch that has been begun (B > 0), on the model's stream
+int prevalence_device(trlda_prevalence *p, const trlda_batch *b, const double *gamma_dev)
+{
+    trlda_model *m = p->model;
+    const int K = m->K, B = b->B;
+    int rc = p->nd.grow((size_t)B);
+    if (!rc) rc = p->inv.grow((size_t)B);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kRelevanceThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::prevalence_docs_kernel, dim3((B + per_wg - 1) / per_wg),
+                       dim3(trlda::kRelevanceThreads), 0, m->stream, K, B, p->by_length, b->indptr, b->cnts,
+                       gamma_dev, p->nd.get(), p->inv.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::prevalence_add_kernel,
+                       dim3((K + trlda::kRelevanceThreads - 1) / trlda::kRelevanceThreads),
+                       dim3(trlda::kRelevanceThreads), 0, m->stream, K, B, gamma_dev, p->nd.get(), p->inv.get(),
+                       p->sums.get(), p->docs.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_prevalence_create(trlda_model *m, int weight_by_length, trlda_prevalence **out)
+{
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    trlda_prevalence *p = new trlda_prevalence();
+    p->model = m;
+    p->by_length = weight_by_length ? 1 : 0;
+    rc = p->sums.alloc((size_t)m->K);
+    if (!rc) rc = p->docs.alloc(1);
+    if (!rc) {
+        hipError_t e1 = hipMemsetAsync(p->sums, 0, (size_t)m->K * sizeof(double), m->stream);
+        hipError_t e2 = hipMemsetAsync(p->docs, 0, sizeof(long long), m->stream);
+        if (e1 != hipSuccess || e2 != hipSuccess)
+            rc = fail(TRLDA_ERR_HIP, "clearing the prevalence sums failed");
+    }
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return TRLDA_OK;
+}
+
+int trlda_prevalence_add_dev(trlda_prevalence *p, const trlda_batch *b, const double *gamma_dev)
+{
+    if (int rc_arg = prevalence_checks(p, b))
+        return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    trlda_model *m = p->model;
+    int rc = check_model(m);
+    if (rc || b->B <= 0)
+        return rc;
+    if (!gamma_dev)
+        return fail(TRLDA_ERR_ARG, "gamma is NULL");
+    rc = batch_begin(m, b);
+    if (!rc) rc = prevalence_device(p, b, gamma_dev);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    return TRLDA_OK;
+}
+
+// The E-step of trlda_model_estep_host on the batch, then the two passes with its gamma
+int trlda_prevalence_add(trlda_prevalence *p, const trlda_batch *b, double *gamma, int max_iter, double threshold)
+{
+    if (int rc_arg = prevalence_checks(p, b))
+        return rc_arg;
+    trlda_model *m = p->model;
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (b->B > 0 && !gamma)
+        return fail(TRLDA_ERR_ARG, "gamma is NULL");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc || b->B <= 0)
+        return rc;
+    rc = ensure_update_workspace(m, b->B);
+    if (rc)
+        return rc;
+    const size_t gbytes = (size_t)m->K * b->B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc) rc = prevalence_device(p, b, m->gamma);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
+}
+
+int trlda_prevalence_read(trlda_prevalence *p, double *prevalence_out, int64_t *num_docs)
+{
+    if (!p || !prevalence_out || !num_docs)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = p->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int K = m->K;
+    std::vector<double> sums((size_t)K);
+    long long docs = 0;
+    hipError_t e1 = hipMemcpyAsync(sums.data(), p->sums, (size_t)K * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipMemcpyAsync(&docs, p->docs, sizeof(long long), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    *num_docs = docs;
+    if (docs <= 0)
+        return fail(TRLDA_ERR_VALUE, "prevalence: no document with a positive count has been added");
+    long double total = 0.0L;
+    for (int k = 0; k < K; ++k)
+        total += sums[(size_t)k];
+    for (int k = 0; k < K; ++k)
+        prevalence_out[k] = (double)((long double)sums[(size_t)k] / total);
+    return TRLDA_OK;
+}
+
+int trlda_prevalence_destroy(trlda_prevalence *p)
+{
+    if (!p)
+        return TRLDA_OK;
+    if (p->model && use_device(p->model->device) == TRLDA_OK && p->model->stream)
+        (void)hipStreamSynchronize(p->model->stream);    // (its kernels may still read the buffers)
+    delete p;
+    return TRLDA_OK;
 }
 
 }  // extern "C"

@@ -1072,6 +1072,223 @@ class LDA(Distribution):
                          "num_documents": int(num_docs.value)}
         return coh
 
+    # -- relevance, saliency and topic prevalence (csrc/relevance_kernels.h) -----------------------
+    def _rank_top_n(self, top_n):
+        top_n = operator.index(top_n)
+        if not 1 <= top_n <= min(self._V, 100):
+            raise RuntimeError("`top_n` should lie between 1 and min(num_words, 100).")
+        return top_n
+
+    def _topic_weights(self, topic_weights):
+        """None, or the weights as K contiguous float64 (checked; the library normalises them)."""
+        if topic_weights is None:
+            return None
+        try:
+            w = np.array(topic_weights, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise RuntimeError("`topic_weights` should be an array of num_topics weights.")
+        if w.size != self._K:
+            raise RuntimeError("`topic_weights` should hold num_topics weights.")
+        if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+            raise RuntimeError("`topic_weights` should be finite and positive.")
+        return np.ascontiguousarray(w)
+
+    def _open_handle(self):
+        if getattr(self, "_handle", None) is None:
+            raise RuntimeError("The model has been closed.")
+        self._settle()
+        return self._handle
+
+    def relevant_words(self, top_n=10, weight=0.6, topic_weights=None, return_scores=False):
+        """The ``top_n`` word ids of each topic ranked by relevance (Sievert & Shirley 2014, the
+        ranking of LDAvis): with ``beta_kw = lambdas[k, w] / lambdas[k].sum()`` and the marginal
+        word probability ``p_w = sum_k pi_k beta_kw``,
+
+            r_kw = weight * log(beta_kw) + (1 - weight) * log(beta_kw / p_w),
+
+        a blend of a word's probability in the topic and its lift over the corpus.  ``weight = 1``
+        ranks as ``top_words`` does; smaller weights push words that every topic holds down the
+        lists (0.6 is the value the paper's user study arrived at).  Returns a K x top_n int32
+        array, best first, equal values by smaller word id: row k is
+        ``np.lexsort((np.arange(V), -r[k]))[:top_n]``; with ``return_scores=True`` also the K x
+        top_n float64 r_kw.  The lists go straight into ``topic_coherence(words=...)``.
+
+        ``topic_weights`` (pi): None weighs each topic by its share of lambda's mass,
+        ``lambdas[k].sum() / lambdas.sum()``; else K finite, positive weights (normalised to sum
+        1), e.g. ``topic_prevalence(docs)``.  ``1 <= top_n <= min(num_words, 100)`` and ``0 <=
+        weight <= 1``, else RuntimeError, as for weights of the wrong length, not finite or not
+        positive.  A lambda with an entry <= 0 or not finite raises RuntimeError.  Everything runs on
+        the GPU (one pass over lambda by columns, then ``top_words``' selection); only the result
+        comes back, and two calls agree bitwise.  lambda, alpha, eta, the counters and the seeded
+        stream stay as they are."""
+        top_n = self._rank_top_n(top_n)
+        try:
+            weight = float(weight)
+        except (TypeError, ValueError):
+            raise RuntimeError("`weight` should be a number between 0 and 1.")
+        if not 0.0 <= weight <= 1.0:
+            raise RuntimeError("`weight` should lie between 0 and 1.")
+        pi = self._topic_weights(topic_weights)
+        handle = self._open_handle()
+        words = np.empty((self._K, top_n), dtype=np.int32)
+        scores = np.empty((self._K, top_n), dtype=np.float64) if return_scores else None
+        _ffi.check(_ffi.lib().trlda_model_relevant_words(
+            handle, top_n, weight, None if pi is None else pi.ctypes.data, words.ctypes.data,
+            None if scores is None else scores.ctypes.data))
+        if return_scores:
+            return words, scores
+        return words
+
+    def word_statistics(self, topic_weights=None):
+        """``(p_w, distinctiveness, saliency)``, three float64 arrays of length V (Chuang, Manning &
+        Heer 2012): the marginal word probability ``p_w = sum_k pi_k beta_kw``; the distinctiveness
+        ``D_w = sum_k p(k | w) log(p(k | w) / pi_k)`` with ``p(k | w) = pi_k beta_kw / p_w`` -- the
+        Kullback-Leibler divergence of a word's topics from the topic weights, >= 0, in nats; and the
+        saliency ``S_w = p_w D_w``, which sums to the mutual information of topic and word (at most
+        log K).  ``topic_weights`` and the errors are those of ``relevant_words``.  Formed on the GPU
+        in one pass over lambda; 3 V numbers come back."""
+        pi = self._topic_weights(topic_weights)
+        handle = self._open_handle()
+        p, d, s = (np.empty(self._V, dtype=np.float64) for _ in range(3))
+        _ffi.check(_ffi.lib().trlda_model_word_stats(
+            handle, None if pi is None else pi.ctypes.data, p.ctypes.data, d.ctypes.data, s.ctypes.data))
+        return p, d, s
+
+    def salient_words(self, top_n=30, topic_weights=None):
+        """``(words, saliency)``: the ``top_n`` word ids of the vocabulary in decreasing saliency
+        (``word_statistics``), equal values by smaller word id first, int32, and their saliency,
+        float64 -- the terms that say most about which topic they came from.  ``topic_weights`` and
+        the errors are those of ``relevant_words``."""
+        top_n = self._rank_top_n(top_n)
+        pi = self._topic_weights(topic_weights)
+        handle = self._open_handle()
+        words = np.empty(top_n, dtype=np.int32)
+        sal = np.empty(top_n, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_model_salient_words(
+            handle, top_n, None if pi is None else pi.ctypes.data, words.ctypes.data, sal.ctypes.data))
+        return words, sal
+
+    def _prevalence(self, weight_by_length, feed):
+        """Runs ``feed(acc)`` and returns the normalised weights; ``acc()`` is the accumulator, made
+        when first asked for -- after the first batch has been checked, so that a batch of another
+        model or a gamma of the wrong shape raises before anything is allocated."""
+        handle = self._open_handle()
+        L = _ffi.lib()
+        made = _ffi.vp()
+
+        def acc():
+            if not made:
+                _ffi.check(L.trlda_prevalence_create(handle, 1 if weight_by_length else 0, C.byref(made)))
+            return made
+
+        try:
+            feed(acc)
+            pi = np.empty(self._K, dtype=np.float64)
+            num_docs = C.c_int64(0)
+            _ffi.check(L.trlda_prevalence_read(acc(), pi.ctypes.data, C.byref(num_docs)))
+        finally:
+            if made:
+                L.trlda_prevalence_destroy(made)
+        return pi
+
+    def topic_prevalence(self, docs, latents=None, max_iter=100, threshold=0.001, weight_by_length=True):
+        """The weight of each topic in a corpus: a float64 array of K that sums to 1,
+
+            pi_k ~ sum_d N_d gamma_dk / sum_j gamma_dj,
+
+        ``N_d`` the sum of document d's positive counts (``weight_by_length=False``: 1, every
+        document counts the same); a document without a positive count is skipped.  gamma comes
+        from ``update_variables``' E-step on each batch (lambda fixed; ``latents`` as gamma0, its
+        columns in the order of the documents, else a random gamma drawn from the seeded stream as
+        ``update_variables`` draws it); only K sums stay on the device between batches.
+
+        ``docs`` is what ``topic_coherence`` takes: a batch (a list of documents, ``DocumentList``,
+        ``CSRDocuments`` or a ``DeviceBatch`` of this model) or an iterator of batches.  The sum
+        runs over the documents in order, one addition per document per topic, so the result does
+        not depend on how the corpus is cut into batches beyond what gamma itself does.  No
+        contributing document, or a batch of another model, raises RuntimeError.  The result plugs
+        into ``topic_weights=``.  lambda, alpha, eta and the counters stay as they are (DESIGN.md
+        3.23)."""
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        g0 = None
+        if latents is not None:
+            try:
+                g0 = np.array(latents, dtype=np.float64, order="F", copy=True)
+            except (TypeError, ValueError):
+                raise TypeError("`latents` should be of type `ndarray`.")
+            if g0.ndim == 1:
+                g0 = g0.reshape(-1, 1, order="F")
+            if g0.ndim != 2 or g0.shape[0] != self._K:
+                raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+            # (one batch: its size is known before anything is uploaded or run)
+            if not hasattr(docs, "__next__") and g0.shape[1] != len(docs):
+                raise RuntimeError("Initial gamma has wrong dimensionality.")
+        L = _ffi.lib()
+
+        def feed(acc):
+            at = 0
+            for part in (docs if hasattr(docs, "__next__") else (docs,)):
+                batch, owned = self._batch(part)
+                try:
+                    B = len(batch)
+                    if g0 is not None:
+                        if at + B > g0.shape[1]:
+                            raise RuntimeError("Initial gamma has wrong dimensionality.")
+                        gamma = np.asfortranarray(g0[:, at:at + B])
+                    else:
+                        gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                        L.trlda_sample_gamma_init(self._K, B, gamma)  # lda.cpp:135
+                    _ffi.check(L.trlda_prevalence_add(acc(), batch.handle, gamma.ctypes.data, int(max_iter),
+                                                      float(threshold)))
+                    at += B
+                finally:
+                    if owned:
+                        batch.close()
+            if g0 is not None and at != g0.shape[1]:
+                raise RuntimeError("Initial gamma has wrong dimensionality.")
+
+        return self._prevalence(weight_by_length, feed)
+
+    def topic_prevalence_gamma(self, gamma, docs, weight_by_length=True):
+        """``topic_prevalence`` for documents given by their ``gamma`` (K x B, every value finite
+        and positive, else RuntimeError; not an array, TypeError): no E-step runs and nothing is
+        drawn, so any number of topics is taken and the ``alpha + n`` of a Gibbs or CVB0 run serves
+        as well.  ``docs`` (one batch of B documents) gives the lengths N_d and which documents are
+        skipped.  On the gamma ``update_variables`` returns, bitwise the result of
+        ``topic_prevalence``."""
+        try:
+            g = np.array(gamma, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`gamma` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Gamma has wrong dimensionality.")
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise RuntimeError("Gamma should be finite and positive.")
+        g = np.asfortranarray(g)
+        if len(docs) != g.shape[1]:
+            raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+        L = _ffi.lib()
+
+        def feed(acc):
+            batch, owned = self._batch(docs)
+            ptr = _ffi.vp()
+            try:
+                if g.shape[1] == 0:
+                    return
+                _ffi.check(L.trlda_dev_alloc(self._device, g.nbytes, C.byref(ptr)))
+                _ffi.check(L.trlda_dev_upload(self._device, ptr, g.ctypes.data, g.nbytes))
+                _ffi.check(L.trlda_prevalence_add_dev(acc(), batch.handle, ptr))
+                _ffi.check(L.trlda_model_synchronize(self._handle))
+            finally:
+                if ptr:
+                    L.trlda_dev_free(self._device, ptr)
+                if owned:
+                    batch.close()
+
+        return self._prevalence(weight_by_length, feed)
+
     # -- device reductions for the empirical-Bayes steps (csrc/eb_kernels.h) ----------------
     def _psi_gamma_diff_device(self, num_docs):
         """sum_d (psi(gamma_dk) - psi(sum_k gamma_dk)) over the gamma the last update / resident
