@@ -325,3 +325,29 @@ def test_gibbs_leaves_vi_alone(hipdev, deferred):
     a, b = run(False), run(True)
     for x, y in zip(a, b):
         assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+
+
+@pytest.mark.parametrize("K,V", [(3, 300), (65, 300), (200, 2100)])
+def test_table_equals_vi_split_preamble(hipdev, K, V):
+    """The sampler's table and the table of the VI E-step's two-kernel preamble (row sums from
+    lambda itself, nothing carried over) are the same computation: bitwise equal at the batch's
+    word columns.  V = 300: 9 row-sum blocks; V = 2100: the cap of 64; K V < 2^22 throughout, so
+    both hand the uncombined block partials to exp_elog_beta_kernel."""
+    from trlda_amd import _ffi
+    L = _ffi.lib()
+    rng = np.random.RandomState(K + V)
+    model = _model(K, V, alpha=.1, seed=K)
+    docs = _random_docs(rng, 4, V, max_len=8, max_cnt=3)
+    docs[0] = docs[0] + [(V - 1, 2), (0, 1)]
+    words = sorted({w for d in docs for w, _ in d})
+    _ffi.check(L.trlda_model_set_split_preamble(model._handle, 1))
+    _ffi.check(L.trlda_model_set_carry_rowsums(model._handle, 0))
+    model.update_variables(docs, max_iter=2)
+    vi = np.empty((K, V), order="F")
+    _ffi.check(L.trlda_debug_peek(model._handle, 0, vi.ctypes.data, vi.size))
+    model.update_variables(docs, inference_method="gibbs", num_samples=1, burn_in=0)
+    e = np.empty((K, V), order="F")
+    _ffi.check(L.trlda_debug_gibbs_table(model._handle, e))
+    model.close()
+    assert np.all(e[:, words] > 0)
+    assert np.array_equal(vi[:, words], e[:, words])

@@ -1773,6 +1773,78 @@ auto ks_dispatch(int ks, F &&f)
         return ks == KS ? f(std::integral_constant<int, KS>{}) : ks_dispatch<KS + 1>(ks, f);
 }
 
+// f(std::integral_constant<int, kpl>) for the wave-per-document samplers' topics per lane, K over
+// the wave rounded up to 1, 2, 4, 8 or 16 (K <= kGibbsMaxK)
+template <class F>
+auto kpl_dispatch(int K, F &&f)
+{
+    const int kpl = (K + trlda::kWave - 1) / trlda::kWave;
+    return kpl <= 1 ? f(std::integral_constant<int, 1>{}) : kpl <= 2 ? f(std::integral_constant<int, 2>{})
+         : kpl <= 4 ? f(std::integral_constant<int, 4>{}) : kpl <= 8 ? f(std::integral_constant<int, 8>{})
+         : f(std::integral_constant<int, 16>{});
+}
+
+// ---- the two-kernel table preamble (lda.cpp:172-173; estep_kernels.h, kernels 1 and 2): the
+// E-step's non-fused branch and the samplers' table, each on buffers of its own ----
+
+// G rows of K block partials -> one row, in rowsum_combine_kernel's order of additions
+int launch_rowsum_combine(trlda_model *m, int G, const double *partial, double *combined)
+{
+    hipLaunchKernelGGL(trlda::rowsum_combine_kernel<kDenseThreads>,
+                       dim3((m->K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)), dim3(kDenseThreads), 0,
+                       m->stream, m->K, G, partial, combined);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// Stage 1: at most `most` block partials of lambda's row sums, from lambda itself, into `partial`.
+// Up to kRowsumBlocks rows stay for the table kernel to add up (saves a launch); more are
+// combined into the row behind them.  rows / G: what stage 2 reads.
+int table_rowsums(trlda_model *m, int most, double *partial, const double *&rows, int &G)
+{
+    int wpb = 0;
+    G = rowsum_blocks(m->V, most, wpb);
+    hipLaunchKernelGGL(trlda::rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream,
+                       m->K, m->V, wpb, m->lambda, partial);
+    HIP_TRY(hipGetLastError());
+    rows = partial;
+    if (G <= trlda::kRowsumBlocks)
+        return TRLDA_OK;
+    rows = partial + (size_t)G * m->K;
+    const int rc = launch_rowsum_combine(m, G, partial, partial + (size_t)G * m->K);
+    G = 1;
+    return rc;
+}
+
+// Stage 2: psi_sum (psi of the row sums, the sums, exp(-psi)) and eeb = exp(psi(lambda) - psi(row
+// sum)) at the n columns `active` (nullptr: the first n), from `G` rows of sums and `lds` bytes
+template <class Kern>
+int launch_table(trlda_model *m, Kern kern, size_t lds, int G, const double *rows, double *psi_sum,
+                 double *eeb, const int *active, int n)
+{
+    const size_t total = (size_t)m->K * (size_t)n;
+    const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + 1023) / 1024, 256));
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds))
+        return rc;
+    hipLaunchKernelGGL(kern, dim3(GE), dim3(1024), lds, m->stream, m->K, total, G, m->lambda, rows, psi_sum, eeb,
+                       active);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// ... from stage 1's rows (9 K doubles of LDS: K <= 2272), or from one finished row of sums (any K)
+int table_from_partials(trlda_model *m, int G, const double *rows, double *psi_sum, double *eeb,
+                        const int *active, int n)
+{
+    return launch_table(m, trlda::exp_elog_beta_kernel<1024>, (size_t)m->K * 9 * sizeof(double), G, rows,
+                        psi_sum, eeb, active, n);
+}
+int table_from_rowsums(trlda_model *m, const double *rs, double *psi_sum, double *eeb, const int *active, int n)
+{
+    return launch_table(m, trlda::exp_elog_beta_kernel<1024, true>, (size_t)m->K * sizeof(double), 1, rs,
+                        psi_sum, eeb, active, n);
+}
+
 // LDS rows of the single-orientation body for the words past its registers: as many as the
 // longest document (max_n words) needs and fit
 int wide_lds_rows(int KS, int max_n)
@@ -2040,21 +2112,9 @@ int estep_preamble(trlda_model *m, const trlda_batch *b, const EstepPlan &p, Pre
             return rc;
         pr.partial_in = m->rs_full;
         pr.G = 1;
-    } else {
-        int wpb = 0;
-        const int G = pr.G = rowsum_blocks(V, p.big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, wpb);
-        hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0,
-                           m->stream, K, V, wpb, m->lambda, m->partial);
-        HIP_TRY(hipGetLastError());
-        if (G > kRowsumBlocks) {
-            double *combined = m->partial + (size_t)G * K;       // row G of the same buffer
-            hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>,
-                               dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
-                               dim3(kDenseThreads), 0, m->stream, K, G, m->partial, combined);
-            HIP_TRY(hipGetLastError());
-            pr.partial_in = combined;
-            pr.G = 1;
-        }
+    } else if ((rc = table_rowsums(m, p.big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, m->partial, pr.partial_in,
+                                   pr.G))) {
+        return rc;
     }
     if (m->timing && (rc = stamp(m)))
         return rc;
@@ -2067,36 +2127,24 @@ int estep_preamble(trlda_model *m, const trlda_batch *b, const EstepPlan &p, Pre
                            pr.partial_in, m->psi_sum);
         HIP_TRY(hipGetLastError());
     } else {
-        constexpr int TE = 1024;
-        const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
-        const size_t lds = (size_t)K * 9 * sizeof(double);
-        if (lds <= (size_t)kLdsDynBytes) {
-            if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds)))
-                return rc;
-            hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, pr.G,
-                               m->lambda, pr.partial_in, m->psi_sum, m->eeb_cur, active);
-            HIP_TRY(hipGetLastError());
+        const int n = dense ? V : b->n_active;
+        if ((size_t)K * 9 * sizeof(double) <= (size_t)kLdsDynBytes) {
+            rc = table_from_partials(m, pr.G, pr.partial_in, m->psi_sum, m->eeb_cur, active, n);
         } else {
             // K > 2272: 9 K doubles do not fit.  The block partials become one row first (the
             // last row of m->partial: the G <= 64 rows in use lie below it) -- the additions of
             // the kernel's own prologue in the same order -- and the kernel keeps psiSum only
             if (pr.G > 1) {
                 double *combined = m->partial + (size_t)(kMaxRowsumBlocks - 1) * K;
-                hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>,
-                                   dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
-                                   dim3(kDenseThreads), 0, m->stream, K, pr.G, pr.partial_in, combined);
-                HIP_TRY(hipGetLastError());
+                if ((rc = launch_rowsum_combine(m, pr.G, pr.partial_in, combined)))
+                    return rc;
                 pr.partial_in = combined;
                 pr.G = 1;
             }
-            const size_t lds1 = (size_t)K * sizeof(double);
-            auto kern = exp_elog_beta_kernel<TE, true>;
-            if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds1)))
-                return rc;
-            hipLaunchKernelGGL(kern, dim3(GE), dim3(TE), lds1, m->stream, K, total, pr.G, m->lambda,
-                               pr.partial_in, m->psi_sum, m->eeb_cur, active);
-            HIP_TRY(hipGetLastError());
+            rc = table_from_rowsums(m, pr.partial_in, m->psi_sum, m->eeb_cur, active, n);
         }
+        if (rc)
+            return rc;
     }
     return m->timing && (rc = stamp(m)) ? rc : TRLDA_OK;
 }
@@ -5243,6 +5291,53 @@ int launch_l2r(trlda_model *m, const trlda::L2rArgs &a)
     return TRLDA_OK;
 }
 
+// The token plan of the wave-per-document samplers: the B > 0 documents' token counts into
+// `tokens` (gibbs_tokens_kernel) and down into `tok`, and the documents by decreasing count into
+// `order` (equal counts: by index).  One small launch, one download, one wait on the stream.
+int token_plan(trlda_model *m, const trlda_batch *b, DevBuf<int64_t> &tokens, std::vector<int64_t> &tok,
+               std::vector<int32_t> &order)
+{
+    const int B = b->B;
+    tok.resize((size_t)B);
+    order.resize((size_t)B);
+    hipLaunchKernelGGL(trlda::gibbs_tokens_kernel<256>, dim3((B + 255) / 256), dim3(256), 0, m->stream, B,
+                       b->indptr, b->cnts, tokens);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tok.data(), tokens, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(),
+                     [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
+    return TRLDA_OK;
+}
+
+// the argument checks the Gibbs and CVB0 device entry points share, in the order they report
+int sampler_checks(const trlda_model *m, const trlda_batch *b, const char *limit_message)
+{
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
+    if (m->eb.active)
+        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
+                                   "yet): trlda_model_online_eb_finish first");
+    if (m->K > trlda::kGibbsMaxK)
+        return fail(TRLDA_ERR_ARG, limit_message);
+    return TRLDA_OK;
+}
+
+// the end of a sampling call: its sticky failure flag read, the one wait for the device
+int sampler_finish(trlda_model *m, const int *flag_dev, const char *message)
+{
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (int rc_sync = sync_model(m))
+        return rc_sync;
+    return flag ? fail(TRLDA_ERR_VALUE, message) : (int)TRLDA_OK;
+}
+
+constexpr const char *kHistogramFailure = "Something went wrong while sampling from histogram.";
+
 // token-particles a document group may hold: kL2rBudget, or what TRLDA_L2R_BUDGET says (read per
 // call: the tests force small groups with it)
 long long l2r_budget()
@@ -5307,16 +5402,10 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     if (rc)
         return rc;
     // the plan: tokens per document, the longest first, groups of documents under the budget
-    std::vector<int64_t> tok((size_t)B), off((size_t)B);
-    std::vector<int32_t> order((size_t)B);
-    hipLaunchKernelGGL(gibbs_tokens_kernel<256>, dim3((B + 255) / 256), dim3(256), 0, m->stream, B, b->indptr,
-                       b->cnts, g.tokens);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(tok.data(), g.tokens, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(),
-                     [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
+    std::vector<int64_t> tok, off((size_t)B);
+    std::vector<int32_t> order;
+    if ((rc = token_plan(m, b, g.tokens, tok, order)))
+        return rc;
     const long long budget = l2r_budget();
     if (tok[(size_t)order[0]] > budget / R) {
         (void)batch_end(m, b);
@@ -5357,14 +5446,11 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     a.off = g.off; a.tokens = g.tokens;
     a.lambda = m->lambda; a.rowsum = rs; a.alpha = m->alpha; a.asum = g.asum;
     a.z = g.z; a.p = g.p; a.flag = g.flag;
-    const int kpl = (K + kWave - 1) / kWave;
     for (size_t gi = 0; gi + 1 < starts.size(); ++gi) {
         const int s0 = starts[gi], nd = starts[gi + 1] - s0;
         a.docs = g.order + s0;
         a.items = (long long)nd * R;
-        rc = kpl <= 1 ? launch_l2r<1>(m, a) : kpl <= 2 ? launch_l2r<2>(m, a) : kpl <= 4 ? launch_l2r<4>(m, a)
-           : kpl <= 8 ? launch_l2r<8>(m, a) : launch_l2r<16>(m, a);
-        if (rc)
+        if ((rc = kpl_dispatch(K, [&](auto kpl) { return launch_l2r<decltype(kpl)::value>(m, a); })))
             return rc;
         hipLaunchKernelGGL(l2r_finish_kernel, dim3(nd), dim3(kWave), 0, m->stream, R,
                            combine == TRLDA_L2R_POSITION ? 1 : 0, a.docs, g.off, g.tokens, g.p, g.out);
@@ -5381,7 +5467,7 @@ int trlda_model_left_to_right(trlda_model *m, const trlda_batch *b, int num_part
     if (int rc_x = check_split_exchange(m))
         return rc_x;
     if (flag)
-        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+        return fail(TRLDA_ERR_VALUE, kHistogramFailure);
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     if (tokens_out)
         for (int d = 0; d < B; ++d)
@@ -6821,7 +6907,6 @@ int trlda_model_topic_distances(trlda_model *m, trlda_model *other, const double
 
 namespace {
 
-
 // token offsets and the longest-first document order of batch `b`, made once per batch (the
 // counts live on the device only: one small launch, one download)
 int gibbs_plan(trlda_model *m, const trlda_batch *b)
@@ -6837,16 +6922,10 @@ int gibbs_plan(trlda_model *m, const trlda_batch *b)
     if (!rc) rc = g.order.grow(nb);
     if (rc)
         return rc;
-    std::vector<int64_t> tok((size_t)B), off((size_t)B);
-    std::vector<int32_t> order((size_t)B);
-    if (B > 0) {
-        hipLaunchKernelGGL(trlda::gibbs_tokens_kernel<256>, dim3((B + 255) / 256), dim3(256), 0, m->stream, B,
-                           b->indptr, b->cnts, g.tokens);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(tok.data(), g.tokens, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost,
-                               m->stream));
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
+    std::vector<int64_t> tok, off((size_t)B);
+    std::vector<int32_t> order;
+    if (B > 0 && (rc = token_plan(m, b, g.tokens, tok, order)))
+        return rc;
     int64_t total = 0;
     for (int d = 0; d < B; ++d) {
         off[(size_t)d] = total;
@@ -6856,9 +6935,6 @@ int gibbs_plan(trlda_model *m, const trlda_batch *b)
     // are 32-bit counts)
     if (total > (int64_t)UINT32_MAX)
         return fail(TRLDA_ERR_ARG, "Gibbs sampling: the batch holds more than 2^32 - 1 tokens");
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(),
-                     [&tok](int32_t x, int32_t y) { return tok[(size_t)x] > tok[(size_t)y]; });
     rc = g.z.grow((size_t)std::max<int64_t>(total, 1));
     if (rc)
         return rc;
@@ -6874,66 +6950,75 @@ int gibbs_plan(trlda_model *m, const trlda_batch *b)
     return TRLDA_OK;
 }
 
-// e = exp(psi(lambda) - psi(rowsum(lambda))) of the batch's active words into m->gibbs.eeb: the
-// non-fused preamble of the E-step (estep_kernels.h, kernels 1 and 2) on buffers of its own.  The
-// table is normalised -- the fused variants' exp(psi(lambda)) without the topic factors would
-// change the conditional -- and the row sums are formed from lambda itself, not taken from what
-// an update left behind, so that nothing of the VI path's state is read or resolved here.
+// The samplers' table: e = exp(psi(lambda) - psi(rowsum(lambda))) of the batch's active words into
+// m->gibbs.eeb by the table preamble's two stages (table_rowsums, table_from_partials: what the
+// E-step's non-fused branch runs) on the Gibbs family's own buffers.  The table is normalised --
+// the fused variants' exp(psi(lambda)) without the topic factors would change the conditional --
+// and the row sums are formed from lambda itself, not taken from what an update left behind, so
+// that nothing of the VI path's state is read or resolved here.  Gibbs, CVB0 and the first E-step
+// of the Gibbs update loops use it; the loops' later E-steps have finished sums (gibbs_table).
 int gibbs_preamble(trlda_model *m, const trlda_batch *b)
 {
-    using namespace trlda;
     auto &g = m->gibbs;
     const int K = m->K, V = m->V;
     const size_t KV = (size_t)K * V;
-    const bool big = KV >= ((size_t)1 << 22);
-    int G = std::min(big ? kMaxRowsumBlocks - 1 : kRowsumBlocks, std::max(1, V / 32));
-    const int wpb = (V + G - 1) / G;
-    G = (V + wpb - 1) / wpb;
+    const int most = KV >= ((size_t)1 << 22) ? kMaxRowsumBlocks - 1 : trlda::kRowsumBlocks;
+    int wpb = 0;
     int rc = g.eeb.grow(KV);
-    if (!rc) rc = g.partial.grow(((size_t)G + 1) * K);
+    if (!rc) rc = g.partial.grow(((size_t)rowsum_blocks(V, most, wpb) + 1) * K);
     if (!rc) rc = g.psi_sum.grow(3 * (size_t)K);
     if (rc)
         return rc;
     g.table_user = 1;
-    hipLaunchKernelGGL(rowsum_partial_kernel<kDenseThreads>, dim3(G), dim3(kDenseThreads), 0, m->stream, K, V,
-                       wpb, m->lambda, g.partial);
-    HIP_TRY(hipGetLastError());
-    const double *partial_in = g.partial;
-    int G_in = G;
-    if (G > kRowsumBlocks) {
-        double *combined = g.partial + (size_t)G * K;
-        hipLaunchKernelGGL(rowsum_combine_kernel<kDenseThreads>, dim3((K + kDenseThreads / 8 - 1) / (kDenseThreads / 8)),
-                           dim3(kDenseThreads), 0, m->stream, K, G, g.partial, combined);
-        HIP_TRY(hipGetLastError());
-        partial_in = combined;
-        G_in = 1;
-    }
-    if (b->n_active <= 0)
-        return TRLDA_OK;
-    constexpr int TE = 1024;
-    const size_t total = (size_t)K * (size_t)b->n_active;
-    const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
-    const size_t lds = (size_t)K * 9 * sizeof(double);
-    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE>), lds);
+    const double *rows = nullptr;
+    int G = 0;
+    if ((rc = table_rowsums(m, most, g.partial, rows, G)) || b->n_active <= 0)
+        return rc;
+    return table_from_partials(m, G, rows, g.psi_sum, g.eeb, b->active, b->n_active);
+}
+
+// the sweeps' counters (cleared on first use) and sticky flag (the callers reset it), after gibbs_plan
+int gibbs_workspace(trlda_model *m, int num_samples)
+{
+    auto &g = m->gibbs;
+    const size_t KV = (size_t)m->K * m->V;
+    if (g.total_tokens * (int64_t)std::max(num_samples, 1) > (int64_t)UINT32_MAX)
+        return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
+                                   "counters; split the batch");
+    const bool fresh_cnt = !g.cnt || g.cnt.cap() < KV;
+    int rc = g.cnt.grow(std::max<size_t>(KV, 1));
+    if (!rc && !g.flag) rc = g.flag.alloc(1);
     if (rc)
         return rc;
-    hipLaunchKernelGGL(exp_elog_beta_kernel<TE>, dim3(GE), dim3(TE), lds, m->stream, K, total, G_in, m->lambda,
-                       partial_in, g.psi_sum, g.eeb, b->active);
-    HIP_TRY(hipGetLastError());
+    if (fresh_cnt)
+        HIP_TRY(hipMemsetAsync(g.cnt, 0, KV * sizeof(uint32_t), m->stream));
     return TRLDA_OK;
 }
 
-template <int KPL>
-int gibbs_launch_docs(trlda_model *m, const trlda::GibbsArgs &a)
+// `sweeps` Gibbs sweeps over the batch in one launch, a wave per document (plan, table and
+// workspace in place): theta0 (or nullptr) -> theta, the counts past burn_in into g.cnt
+int gibbs_sweeps(trlda_model *m, const trlda_batch *b, uint64_t key, const double *theta0, double *theta,
+                 int sweeps, int burn_in)
 {
-    const size_t lds = (size_t)trlda::kGibbsWaves * (size_t)a.K * (sizeof(double) + sizeof(int));
-    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::gibbs_docs_kernel<KPL>), lds);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(trlda::gibbs_docs_kernel<KPL>, dim3((a.B + trlda::kGibbsWaves - 1) / trlda::kGibbsWaves),
-                       dim3(trlda::kGibbsWaves * trlda::kWave), lds, m->stream, a);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    using namespace trlda;
+    auto &g = m->gibbs;
+    GibbsArgs a;
+    a.K = m->K; a.B = b->B; a.sweeps = sweeps; a.burn_in = burn_in;
+    a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
+    a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
+    a.order = g.order; a.tok_off = g.tok_off;
+    a.eeb = g.eeb; a.alpha = m->alpha; a.theta0 = theta0; a.theta = theta;
+    a.z = g.z; a.cnt = g.cnt; a.flag = g.flag;
+    const size_t lds = (size_t)kGibbsWaves * (size_t)a.K * (sizeof(double) + sizeof(int));
+    return kpl_dispatch(a.K, [&](auto kpl) {
+        auto kern = gibbs_docs_kernel<decltype(kpl)::value>;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds))
+            return rc;
+        hipLaunchKernelGGL(kern, dim3((a.B + kGibbsWaves - 1) / kGibbsWaves), dim3(kGibbsWaves * kWave), lds,
+                           m->stream, a);
+        HIP_TRY(hipGetLastError());
+        return (int)TRLDA_OK;
+    });
 }
 
 // the whole call on the model's stream; waits for the device at the end (the sampling-failure flag)
@@ -6943,52 +7028,23 @@ int gibbs_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev,
     using namespace trlda;
     const int K = m->K, V = m->V, B = b->B;
     const size_t KV = (size_t)K * V;
-    if (b->V != V)
-        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
-    if (m->eb.active)
-        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
-                                   "yet): trlda_model_online_eb_finish first");
-    if (K > kGibbsMaxK)
-        return fail(TRLDA_ERR_ARG, "Gibbs sampling supports at most 1024 topics");
+    if (int rc = sampler_checks(m, b, "Gibbs sampling supports at most 1024 topics"))
+        return rc;
     if (num_samples < 0 || burn_in < 0 || (long long)num_samples + burn_in > INT32_MAX)
         return fail(TRLDA_ERR_ARG, "num_samples and burn_in should not be negative");
     if (!sstats_dev || (B > 0 && !theta_dev))
         return fail(TRLDA_ERR_ARG, "NULL theta / sstats");
     int rc = batch_begin(m, b);
     if (!rc) rc = gibbs_plan(m, b);
+    if (!rc) rc = gibbs_workspace(m, num_samples);
     if (rc)
         return rc;
     auto &g = m->gibbs;
-    if (g.total_tokens * (int64_t)std::max(num_samples, 1) > (int64_t)UINT32_MAX)
-        return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
-                                   "counters; split the batch");
-    const bool fresh_cnt = !g.cnt || g.cnt.cap() < KV;
-    rc = g.cnt.grow(std::max<size_t>(KV, 1));
-    if (!rc && !g.flag) rc = g.flag.alloc(1);
-    if (rc)
-        return rc;
-    if (fresh_cnt)
-        HIP_TRY(hipMemsetAsync(g.cnt, 0, KV * sizeof(uint32_t), m->stream));
     HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
     if (B > 0 && g.total_tokens > 0 && (rc = gibbs_preamble(m, b)))
         return rc;
-    if (B > 0) {
-        GibbsArgs a;
-        a.K = K; a.B = B; a.sweeps = num_samples + burn_in; a.burn_in = burn_in;
-        a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
-        a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
-        a.order = g.order; a.tok_off = g.tok_off;
-        a.eeb = g.eeb; a.alpha = m->alpha; a.theta0 = theta0_dev; a.theta = theta_dev;
-        a.z = g.z; a.cnt = g.cnt; a.flag = g.flag;
-        const int kpl = (K + kWave - 1) / kWave;
-        rc = kpl <= 1 ? gibbs_launch_docs<1>(m, a) : kpl <= 2 ? gibbs_launch_docs<2>(m, a)
-           : kpl <= 4 ? gibbs_launch_docs<4>(m, a) : kpl <= 8 ? gibbs_launch_docs<8>(m, a)
-           : gibbs_launch_docs<16>(m, a);
-        if (rc)
-            return rc;
-    }
+    if (B > 0 && (rc = gibbs_sweeps(m, b, key, theta0_dev, theta_dev, num_samples + burn_in, burn_in)))
+        return rc;
     if (KV) {
         constexpr int TF = 256;
         const int GF = (int)std::max<size_t>(1, std::min<size_t>((KV + TF - 1) / TF, 4096));
@@ -6997,12 +7053,41 @@ int gibbs_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev,
         HIP_TRY(hipGetLastError());
     }
     (void)batch_end(m, b);
-    int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    return sampler_finish(m, g.flag, kHistogramFailure);
+}
+
+// The host forms of Gibbs and CVB0 stage theta (K x B), the statistics (K x V) and CVB0's iteration
+// counts in m->gibbs / m->cvb0.  In: the buffers, and theta up when the call starts from latents.
+int sampler_stage_in(trlda_model *m, const trlda_batch *b, const double *theta, int use_latents, bool iters)
+{
+    auto &g = m->gibbs;
+    const size_t tcount = (size_t)m->K * std::max(b->B, 1);
+    int rc = g.theta.grow(tcount);
+    if (!rc && use_latents) rc = g.theta_in.grow(tcount);
+    if (!rc) rc = g.sstats.grow(std::max<size_t>((size_t)m->K * m->V, 1));
+    if (!rc && iters) rc = m->cvb0.iters.grow((size_t)std::max(b->B, 1));
+    if (rc)
+        return rc;
+    const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
+    if (use_latents && tbytes)
+        HIP_TRY(hipMemcpyAsync(g.theta_in, theta, tbytes, hipMemcpyHostToDevice, m->stream));
+    return TRLDA_OK;
+}
+
+// Out: theta, the statistics and (iters: CVB0) the iteration counts down, one wait
+int sampler_stage_out(trlda_model *m, const trlda_batch *b, double *theta, double *sstats, int32_t *iters)
+{
+    auto &g = m->gibbs;
+    const size_t tbytes = (size_t)m->K * b->B * sizeof(double), sbytes = (size_t)m->K * m->V * sizeof(double);
+    if (tbytes)
+        HIP_TRY(hipMemcpyAsync(theta, g.theta, tbytes, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(sstats, g.sstats, sbytes, hipMemcpyDeviceToHost, m->stream));
+    if (iters && b->B > 0)
+        HIP_TRY(hipMemcpyAsync(iters, m->cvb0.iters, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost,
+                               m->stream));
     if (int rc_sync = sync_model(m))
         return rc_sync;
-    if (flag)
-        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
+    m->d2h_bytes += (int64_t)(tbytes + sbytes);
     return TRLDA_OK;
 }
 
@@ -7038,27 +7123,11 @@ int trlda_model_gibbs_host(trlda_model *m, const trlda_batch *b, double *theta, 
     if (m->K > trlda::kGibbsMaxK)
         return fail(TRLDA_ERR_ARG, "Gibbs sampling supports at most 1024 topics");
     auto &g = m->gibbs;
-    const size_t tcount = (size_t)m->K * std::max(b->B, 1);
-    const size_t KV = (size_t)m->K * m->V;
-    rc = g.theta.grow(tcount);
-    if (!rc && use_latents) rc = g.theta_in.grow(tcount);
-    if (!rc) rc = g.sstats.grow(std::max<size_t>(KV, 1));
-    if (rc)
+    if ((rc = sampler_stage_in(m, b, theta, use_latents, false)))
         return rc;
-    const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
-    if (use_latents && tbytes)
-        HIP_TRY(hipMemcpyAsync(g.theta_in, theta, tbytes, hipMemcpyHostToDevice, m->stream));
     const uint64_t key = trlda_host::rng_draw_key();
     rc = gibbs_device(m, b, use_latents ? g.theta_in : nullptr, g.theta, g.sstats, num_samples, burn_in, key);
-    if (rc)
-        return rc;
-    if (tbytes)
-        HIP_TRY(hipMemcpyAsync(theta, g.theta, tbytes, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipMemcpyAsync(sstats, g.sstats, KV * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    if (int rc_sync = sync_model(m))
-        return rc_sync;
-    m->d2h_bytes += (int64_t)(tbytes + KV * sizeof(double));
-    return TRLDA_OK;
+    return rc ? rc : sampler_stage_out(m, b, theta, sstats, nullptr);
 }
 
 // the table the last Gibbs call sampled from (K x V; the batch's active columns), for the tests'
@@ -7141,15 +7210,8 @@ int cvb0_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, 
     using namespace trlda;
     const int K = m->K, V = m->V, B = b->B;
     const size_t KV = (size_t)K * V;
-    if (b->V != V)
-        return fail(TRLDA_ERR_SHAPE, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch and model live on different devices");
-    if (m->eb.active)
-        return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
-                                   "yet): trlda_model_online_eb_finish first");
-    if (K > kGibbsMaxK)
-        return fail(TRLDA_ERR_ARG, "CVB0 supports at most 1024 topics (the Gibbs path's limit)");
+    if (int rc = sampler_checks(m, b, "CVB0 supports at most 1024 topics (the Gibbs path's limit)"))
+        return rc;
     if (max_iter < 0)
         return fail(TRLDA_ERR_ARG, "max_iter should not be negative");
     if (!sstats_dev || (B > 0 && !theta_dev))
@@ -7172,7 +7234,6 @@ int cvb0_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, 
         HIP_TRY(hipMemsetAsync(sstats_dev, 0, KV * sizeof(double), m->stream));
     if (B > 0 && b->nnz > 0 && (rc = gibbs_preamble(m, b)))
         return rc;
-    const int kpl = (K + kWave - 1) / kWave;
     int gsz = 1;
     while (gsz < kWave && gsz < K)
         gsz <<= 1;
@@ -7190,10 +7251,7 @@ int cvb0_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, 
         a.order = c.order + d0; a.j0 = j0;
         a.eeb = m->gibbs.eeb; a.alpha = m->alpha; a.theta0 = theta0_dev; a.theta = theta_dev;
         a.iters = iters_dev; a.phi = c.phi; a.flag = c.flag;
-        rc = kpl <= 1 ? cvb0_launch_docs<1>(m, a) : kpl <= 2 ? cvb0_launch_docs<2>(m, a)
-           : kpl <= 4 ? cvb0_launch_docs<4>(m, a) : kpl <= 8 ? cvb0_launch_docs<8>(m, a)
-           : cvb0_launch_docs<16>(m, a);
-        if (rc)
+        if ((rc = kpl_dispatch(K, [&](auto kpl) { return cvb0_launch_docs<decltype(kpl)::value>(m, a); })))
             return rc;
         if (j1 > j0 && b->n_active > 0) {
             hipLaunchKernelGGL(cvb0_stats_kernel<TS>, dim3(GS), dim3(TS), 0, m->stream, K, b->n_active, gsz,
@@ -7202,13 +7260,7 @@ int cvb0_device(trlda_model *m, const trlda_batch *b, const double *theta0_dev, 
         }
     }
     (void)batch_end(m, b);
-    int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, c.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if (int rc_sync = sync_model(m))
-        return rc_sync;
-    if (flag)
-        return fail(TRLDA_ERR_VALUE, "CVB0: a token's topic weights sum to zero or are not finite.");
-    return TRLDA_OK;
+    return sampler_finish(m, c.flag, "CVB0: a token's topic weights sum to zero or are not finite.");
 }
 
 }  // namespace
@@ -7243,31 +7295,11 @@ int trlda_model_cvb0_host(trlda_model *m, const trlda_batch *b, double *theta, i
     if (m->K > trlda::kGibbsMaxK)
         return fail(TRLDA_ERR_ARG, "CVB0 supports at most 1024 topics (the Gibbs path's limit)");
     auto &g = m->gibbs;
-    const size_t tcount = (size_t)m->K * std::max(b->B, 1);
-    const size_t KV = (size_t)m->K * m->V;
-    rc = g.theta.grow(tcount);
-    if (!rc && use_latents) rc = g.theta_in.grow(tcount);
-    if (!rc) rc = g.sstats.grow(std::max<size_t>(KV, 1));
-    if (!rc && iters) rc = m->cvb0.iters.grow((size_t)std::max(b->B, 1));
-    if (rc)
+    if ((rc = sampler_stage_in(m, b, theta, use_latents, iters != nullptr)))
         return rc;
-    const size_t tbytes = (size_t)m->K * b->B * sizeof(double);
-    if (use_latents && tbytes)
-        HIP_TRY(hipMemcpyAsync(g.theta_in, theta, tbytes, hipMemcpyHostToDevice, m->stream));
     rc = cvb0_device(m, b, use_latents ? g.theta_in : nullptr, g.theta, g.sstats, max_iter, threshold,
                      iters ? m->cvb0.iters : nullptr);
-    if (rc)
-        return rc;
-    if (tbytes)
-        HIP_TRY(hipMemcpyAsync(theta, g.theta, tbytes, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipMemcpyAsync(sstats, g.sstats, KV * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    if (iters && b->B > 0)
-        HIP_TRY(hipMemcpyAsync(iters, m->cvb0.iters, (size_t)b->B * sizeof(int32_t), hipMemcpyDeviceToHost,
-                               m->stream));
-    if (int rc_sync = sync_model(m))
-        return rc_sync;
-    m->d2h_bytes += (int64_t)(tbytes + KV * sizeof(double));
-    return TRLDA_OK;
+    return rc ? rc : sampler_stage_out(m, b, theta, sstats, iters);
 }
 
 int trlda_model_set_cvb0_slab_bytes(trlda_model *m, size_t bytes)
@@ -7288,27 +7320,15 @@ namespace {
 // row sums `rs` (K): the sweeps that follow read it
 int gibbs_table(trlda_model *m, const trlda_batch *b, const double *rs)
 {
-    using namespace trlda;
     auto &g = m->gibbs;
-    const int K = m->K;
-    int rc = g.eeb.grow(std::max<size_t>((size_t)K * m->V, 1));
-    if (!rc) rc = g.psi_sum.grow(3 * (size_t)K);
+    int rc = g.eeb.grow(std::max<size_t>((size_t)m->K * m->V, 1));
+    if (!rc) rc = g.psi_sum.grow(3 * (size_t)m->K);
     if (rc)
         return rc;
     g.table_user = 1;
     if (b->n_active <= 0)
         return TRLDA_OK;
-    constexpr int TE = 1024;
-    const size_t total = (size_t)K * (size_t)b->n_active;
-    const int GE = (int)std::max<size_t>(1, std::min<size_t>((total + TE - 1) / TE, 256));
-    const size_t lds = (size_t)K * sizeof(double);
-    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(exp_elog_beta_kernel<TE, true>), lds);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL((exp_elog_beta_kernel<TE, true>), dim3(GE), dim3(TE), lds, m->stream, K, total, 1,
-                       m->lambda, rs, g.psi_sum, g.eeb, b->active);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return table_from_rowsums(m, rs, g.psi_sum, g.eeb, b->active, b->n_active);
 }
 
 // one M-step over the batch's active columns (gibbs_mstep_kernel), then rs = base + its block rows
@@ -7357,16 +7377,9 @@ int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate 
     int rc = ensure_update_workspace(m, B);
     if (!rc) rc = batch_begin(m, b);
     if (!rc) rc = gibbs_plan(m, b);
-    if (rc)
-        return rc;
+    if (!rc) rc = gibbs_workspace(m, u.num_samples);
     auto &g = m->gibbs;
-    if (g.total_tokens * (int64_t)std::max(u.num_samples, 1) > (int64_t)UINT32_MAX)
-        return fail(TRLDA_ERR_ARG, "Gibbs sampling: tokens x num_samples exceeds the 32-bit statistics "
-                                   "counters; split the batch");
-    const bool fresh_cnt = !g.cnt || g.cnt.cap() < KV;
     const size_t tcount = (size_t)K * std::max(B, 1);
-    rc = g.cnt.grow(std::max<size_t>(KV, 1));
-    if (!rc && !g.flag) rc = g.flag.alloc(1);
     if (!rc && !g.nonpos) rc = g.nonpos.alloc(1);
     if (!rc) rc = g.rs.grow(2 * (size_t)K);
     if (!rc) rc = g.mpart.grow((size_t)kGibbsMstepMaxBlocks * K);
@@ -7391,8 +7404,6 @@ int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate 
     m->lambda_positive = false;
     m->rs_floor = 0.0;
 
-    if (fresh_cnt)
-        HIP_TRY(hipMemsetAsync(g.cnt, 0, KV * sizeof(uint32_t), m->stream));
     HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
     HIP_TRY(hipMemsetAsync(g.nonpos, 0, sizeof(int), m->stream));
     const bool keep = m->keep_sstats;      // adaptive rate: whole lambda' and the statistics stay
@@ -7443,20 +7454,9 @@ int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate 
         return rc;
 
     double *th[2] = {g.theta, g.theta_in};
-    const int kpl = (K + kWave - 1) / kWave;
     for (int i = 0; i < esteps; ++i) {
-        GibbsArgs a;
-        a.K = K; a.B = B; a.sweeps = u.num_samples + u.burn_in; a.burn_in = u.burn_in;
-        a.key0 = (uint32_t)keys[(size_t)i]; a.key1 = (uint32_t)(keys[(size_t)i] >> 32);
-        a.indptr = b->indptr; a.ids = b->ids; a.cnts = b->cnts;
-        a.order = g.order; a.tok_off = g.tok_off;
-        a.eeb = g.eeb; a.alpha = m->alpha;
-        a.theta0 = (u.online && u.init_theta && i > 0) ? th[(i - 1) & 1] : nullptr;   // lda.cpp:123-128
-        a.theta = th[i & 1];
-        a.z = g.z; a.cnt = g.cnt; a.flag = g.flag;
-        rc = kpl <= 1 ? gibbs_launch_docs<1>(m, a) : kpl <= 2 ? gibbs_launch_docs<2>(m, a)
-           : kpl <= 4 ? gibbs_launch_docs<4>(m, a) : kpl <= 8 ? gibbs_launch_docs<8>(m, a)
-           : gibbs_launch_docs<16>(m, a);
+        const double *theta0 = (u.online && u.init_theta && i > 0) ? th[(i - 1) & 1] : nullptr;   // lda.cpp:123-128
+        rc = gibbs_sweeps(m, b, keys[(size_t)i], theta0, th[i & 1], u.num_samples + u.burn_in, u.burn_in);
         if (!rc)
             rc = gibbs_mstep(m, b, omr, rho, u.eta, scale, unit, lambda_prime, sstats, rs_static, rs);
         if (!rc && i + 1 < esteps)
@@ -7492,9 +7492,7 @@ int gibbs_update_device(trlda_model *m, const trlda_batch *b, const GibbsUpdate 
         m->rs_floor = lo > 0.0 ? 0.999 * lo : 0.0;
     }
     ++m->lambda_version;
-    if (flag)
-        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
-    return TRLDA_OK;
+    return flag ? fail(TRLDA_ERR_VALUE, kHistogramFailure) : (int)TRLDA_OK;
 }
 
 int gibbs_update_checks(trlda_model *m, const trlda_batch *b, int num_samples, int burn_in)
@@ -7682,13 +7680,7 @@ int sample_device(trlda_model *m, int B, const int32_t *indptr_dev, int32_t *ids
                            m->stream, K, V, B, k0, k1, indptr_dev, s.pre, g.eeb, ids_dev);
         HIP_TRY(hipGetLastError());
     }
-    int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if (int rc_sync = sync_model(m))
-        return rc_sync;
-    if (flag)
-        return fail(TRLDA_ERR_VALUE, "Something went wrong while sampling from histogram.");
-    return TRLDA_OK;
+    return sampler_finish(m, g.flag, kHistogramFailure);
 }
 
 }  // namespace
