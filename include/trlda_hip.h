@@ -626,6 +626,32 @@ int trlda_docindex_read_rows(trlda_docindex *index, int64_t first, int64_t count
 int trlda_docindex_set_slab_rows(trlda_docindex *index, int rows);
 int trlda_docindex_destroy(trlda_docindex *index);
 
+/* Topic summaries of an indexed corpus (csrc/topicdocs_kernels.h).  theta^ is theta
+ * recovered from the stored row r: r_k * r_k (hellinger, one IEEE multiply) or r_k / sum_j r_j (cosine,
+ * IEEE division, the sum in the order the rows' kernel adds sum gamma); it depends on the row and K
+ * alone.  Every call below runs on the model's stream, synchronises, keeps its temporaries to itself
+ * and leaves the index, lambda, alpha, the model's statistics and the generator as they were; nothing
+ * is atomic: two calls agree bitwise, however the index was filled.  TRLDA_ERR_ARG, before anything is
+ * waited for, copied or launched: a NULL index or required output, an empty index, top_n outside
+ * [1, min(size, 100)].
+ *
+ * Per topic k the first top_n documents in the total order (theta^_dk descending, id ascending):
+ * ids_out (int64) and, unless NULL, theta_out (fp64, their theta^_dk), host, topic-major
+ * [k * top_n + r].  The result does not depend on trlda_docindex_set_slab_rows.  No reference
+ * counterpart. */
+int trlda_docindex_topic_documents(trlda_docindex *index, int top_n, int64_t *ids_out,
+                                   double *theta_out /* may be NULL */);
+/* The mean m_k = (sum_d theta^_dk) / N (mean_out, K) and the centred scatter
+ * S_ij = sum_d (theta^_di - m_i)(theta^_dj - m_j) (scatter_out, K x K, bitwise symmetric) of the N
+ * indexed documents, in two passes: centring before the product avoids the cancellation of
+ * sum theta theta^T / N - m m^T.  The covariance is S / (N - ddof).  No reference counterpart. */
+int trlda_docindex_topic_moments(trlda_docindex *index, double *mean_out /* K */,
+                                 double *scatter_out /* K x K */);
+/* A/B switch for tests and measurements: index rows per chunk of the scatter's sum over N (0: the
+ * default, a function of (K, N) alone).  Results with a forced chunk agree within rounding, not
+ * bitwise.  No reference counterpart. */
+int trlda_docindex_set_moment_chunk(trlda_docindex *index, int rows);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

@@ -182,6 +182,9 @@ _SIGNATURES = {
     "trlda_docindex_read_rows": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
     "trlda_docindex_set_slab_rows": (C.c_int, [vp, C.c_int]),
     "trlda_docindex_destroy": (C.c_int, [vp]),
+    "trlda_docindex_topic_documents": (C.c_int, [vp, C.c_int, vp, vp]),
+    "trlda_docindex_topic_moments": (C.c_int, [vp, vp, vp]),
+    "trlda_docindex_set_moment_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

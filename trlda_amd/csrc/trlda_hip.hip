@@ -57,6 +57,7 @@
 #include "recommend_kernels.h"
 #include "relevance_kernels.h"
 #include "topicdist_kernels.h"
+#include "topicdocs_kernels.h"
 
 namespace {
 
@@ -5856,6 +5857,7 @@ struct trlda_docindex {
     DevBuf<double> rows;                 // (its capacity: Kp doubles per row the table holds)
     int64_t n = 0;                       // rows in use: the next id
     int slab_rows = 0;                   // 0: kDocIndexSlabRows
+    int moment_chunk = 0;                // rows per chunk of trlda_docindex_topic_moments (0: automatic)
     DevBuf<double> qrows, gstage, cand_s, out_s;
     DevBuf<long long> cand_i, out_i;
 };
@@ -6196,6 +6198,131 @@ int trlda_docindex_destroy(trlda_docindex *x)
     if (x->model && use_device(x->model->device) == TRLDA_OK && x->model->stream)
         (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
     delete x;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- topic summaries of an indexed corpus (csrc/topicdocs_kernels.h) ----
+
+namespace {
+
+// The rows' sums into `scale` (N doubles) on the model's stream: what theta^ of a cosine index divides
+// by.  A hellinger index needs none: `scale` stays empty.
+int topicdocs_scale(trlda_docindex *x, DevBuf<double> &scale)
+{
+    if (x->measure == 0)
+        return TRLDA_OK;
+    int rc = scale.alloc((size_t)x->n);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((unsigned)((x->n + per_wg - 1) / per_wg)),
+                       dim3(trlda::kTopicDocsThreads), 0, x->model->stream, x->K, x->Kp, (long long)x->n,
+                       x->rows.get(), scale.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_topic_documents(trlda_docindex *x, int top_n, int64_t *ids_out, double *theta_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!x || !ids_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / ids");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (top_n < 1 || top_n > trlda::kDocIndexMaxTop || (int64_t)top_n > x->n)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(number of indexed documents, 100)]");
+    const int sr = docindex_slab_rows(x), K = x->K;
+    const int64_t slabs = (x->n + sr - 1) / sr;
+    const int ktiles = (K + trlda::kTopicDocsSelTopics - 1) / trlda::kTopicDocsSelTopics;
+    if (slabs * top_n > INT_MAX || ktiles > 65535)       // (the merge's candidate count; grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs or topics: raise trlda_docindex_set_slab_rows");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const size_t cells = (size_t)K * top_n;
+    DevBuf<double> scale, cand_v, out_v;
+    DevBuf<long long> cand_i, out_i;
+    if ((rc = topicdocs_scale(x, scale)) || (rc = cand_v.alloc(cells * slabs)) || (rc = cand_i.alloc(cells * slabs)) ||
+        (rc = out_v.alloc(cells)) || (rc = out_i.alloc(cells)))
+        return rc;
+    const size_t lds = trlda::topicdocs_select_lds(top_n);
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topicdocs_select_kernel), lds)))
+        return rc;
+    hipLaunchKernelGGL(trlda::topicdocs_select_kernel, dim3((unsigned)slabs, ktiles), dim3(trlda::kTopicDocsThreads),
+                       lds, m->stream, K, x->Kp, (long long)x->n, x->measure, top_n, sr, x->rows.get(), scale.get(),
+                       cand_v.get(), cand_i.get());
+    HIP_TRY(hipGetLastError());
+    // (the slabs' lists have the layout of a query's with one query row per topic)
+    hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(K), dim3(trlda::kDocIndexThreads), 0, m->stream, K, top_n,
+                       (int)slabs, cand_v.get(), cand_i.get(), out_i.get(), out_v.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(ids_out, out_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = theta_out ? hipMemcpyAsync(theta_out, out_v, cells * sizeof(double), hipMemcpyDeviceToHost,
+                                               m->stream)
+                              : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    return TRLDA_OK;
+}
+
+int trlda_docindex_set_moment_chunk(trlda_docindex *x, int rows)
+{
+    if (!x || rows < 0)
+        return fail(TRLDA_ERR_ARG, "NULL index, or rows per chunk below 0 (0: automatic)");
+    x->moment_chunk = rows;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_topic_moments(trlda_docindex *x, double *mean_out, double *scatter_out)
+{
+    if (!x || !mean_out || !scatter_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / mean / scatter");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    const int K = x->K;
+    const long long N = x->n;
+    const long long cr = x->moment_chunk > 0 ? x->moment_chunk : trlda::topicdocs_chunk_rows(K, N);
+    const long long chunks = (N + cr - 1) / cr, pairs = trlda::topicdocs_tile_pairs(K);
+    const long long mblocks = (N + trlda::kTopicDocsMeanRows - 1) / trlda::kTopicDocsMeanRows;
+    const size_t n = (size_t)K * K;
+    if (chunks > 65535 || pairs > INT_MAX || mblocks > INT_MAX ||
+        (n + trlda::kTopicDocsThreads - 1) / trlda::kTopicDocsThreads > (size_t)INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many topics or chunks of rows: raise trlda_docindex_set_moment_chunk");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    const dim3 block(trlda::kTopicDocsThreads);
+    DevBuf<double> scale, mpart, mean, part, out;
+    if ((rc = topicdocs_scale(x, scale)) || (rc = mpart.alloc((size_t)mblocks * K)) || (rc = mean.alloc(K)) ||
+        (rc = part.alloc((size_t)chunks * n)) || (rc = out.alloc(n)))
+        return rc;
+    hipLaunchKernelGGL(trlda::topicdocs_mean_kernel, dim3((unsigned)mblocks), block, 0, stream, K, x->Kp, N,
+                       x->measure, x->rows.get(), scale.get(), mpart.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdocs_mean_sum_kernel,
+                       dim3((K + trlda::kTopicDocsThreads - 1) / trlda::kTopicDocsThreads), block, 0, stream, K,
+                       mblocks, (double)N, mpart.get(), mean.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdocs_scatter_kernel, dim3((unsigned)pairs, (unsigned)chunks), block, 0, stream, K,
+                       x->Kp, N, cr, x->measure, x->rows.get(), scale.get(), mean.get(), part.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdocs_finish_kernel,
+                       dim3((unsigned)((n + trlda::kTopicDocsThreads - 1) / trlda::kTopicDocsThreads)), block, 0,
+                       stream, K, (int)chunks, part.get(), out.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(mean_out, mean, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(scatter_out, out, n * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     return TRLDA_OK;
 }
 

@@ -1,7 +1,9 @@
 """Nearest documents in topic space: ``DocumentIndex`` (csrc/docindex_kernels.h).
 
 A device-resident table of the documents' topic proportions theta = gamma / sum(gamma) and the
-ranked search over it.  No counterpart in the reference package.
+ranked search over it; the topic summaries of the indexed corpus -- per topic its most representative
+documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h).  No
+counterpart in the reference package.
 """
 import ctypes as C
 import operator
@@ -207,3 +209,63 @@ class DocumentIndex(object):
         _ffi.check(_ffi.lib().trlda_docindex_query_gamma(handle, g.ctypes.data, B, top_n, ids.ctypes.data,
                                                          sim.ctypes.data))
         return self._result(ids, sim, return_similarity)
+
+    # -- topic summaries (csrc/topicdocs_kernels.h) ---------------------------------
+    def set_moment_chunk(self, rows):
+        """A/B switch: index rows per chunk of the scatter's sum over the documents (0: default).
+        Results with a forced chunk agree within rounding, not bitwise."""
+        rows = operator.index(rows)
+        _ffi.check(_ffi.lib().trlda_docindex_set_moment_chunk(self._live(), rows))
+
+    def topic_documents(self, top_n=10, return_theta=False):
+        """Per topic the ``top_n`` indexed documents that hold most of it: ``ids``, int64 of shape
+        (K, top_n), in the total order (theta descending, id ascending); with ``return_theta=True``
+        also their theta (float64, K x top_n).  theta is recovered from the stored rows: ``r * r``
+        (hellinger) or ``r / sum(r)`` (cosine).  ``1 <= top_n <= min(len(index), 100)``, else
+        RuntimeError."""
+        top_n = self._top_n(top_n)
+        handle = self._live()
+        ids = np.empty((self._K, top_n), dtype=np.int64)
+        theta = np.empty((self._K, top_n), dtype=np.float64) if return_theta else None
+        _ffi.check(_ffi.lib().trlda_docindex_topic_documents(handle, top_n, ids.ctypes.data,
+                                                             theta.ctypes.data if return_theta else None))
+        return (ids, theta) if return_theta else ids
+
+    def _moments(self):
+        """(mean K, scatter K x K) of theta over the indexed documents, from the device."""
+        handle = self._live()
+        mean = np.empty(self._K, dtype=np.float64)
+        scatter = np.empty((self._K, self._K), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_topic_moments(handle, mean.ctypes.data, scatter.ctypes.data))
+        return mean, scatter
+
+    def topic_covariance(self, ddof=1, return_mean=False):
+        """The K x K covariance of theta over the indexed documents, ``S / (N - ddof)`` with the
+        centred scatter ``S = sum_d (theta_d - m)(theta_d - m)^T`` (with ``return_mean=True`` also
+        the mean m, K).  ``N - ddof <= 0`` is a ValueError."""
+        rest = len(self) - ddof
+        if not rest > 0:
+            raise ValueError("`ddof` leaves no degrees of freedom (%d documents)." % len(self))
+        mean, scatter = self._moments()
+        cov = scatter / float(rest)
+        return (cov, mean) if return_mean else cov
+
+    def topic_correlations(self):
+        """The K x K correlations of theta over the indexed documents, ``S_ij / (sqrt(S_ii)
+        sqrt(S_jj))`` clamped to [-1, 1]: an exact 1 on the diagonal, and NaN wherever one of the
+        two variances is 0 (the diagonal included), as ``np.corrcoef`` gives."""
+        return _correlation(self._moments()[1])
+
+
+def _correlation(scatter):
+    """The closing arithmetic of ``topic_correlations`` on the scatter matrix S (host, K x K)."""
+    var = np.diag(scatter)
+    sd = np.sqrt(np.maximum(var, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        # (the two roots apart: S_ii S_jj underflows where sqrt(S_ii) sqrt(S_jj) does not)
+        corr = np.clip(scatter / (sd[:, None] * sd[None, :]), -1.0, 1.0)
+    flat = ~(var > 0.0)
+    corr[np.arange(len(var)), np.arange(len(var))] = 1.0
+    corr[flat, :] = np.nan
+    corr[:, flat] = np.nan
+    return corr
