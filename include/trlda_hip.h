@@ -652,6 +652,28 @@ int trlda_docindex_topic_moments(trlda_docindex *index, double *mean_out /* K */
  * bitwise.  No reference counterpart. */
 int trlda_docindex_set_moment_chunk(trlda_docindex *index, int rows);
 
+/* Indexed documents by query likelihood (csrc/querylik_kernels.h; the LDA term of Wei &
+ * Croft's LBDM, SIGIR 2006).  Nothing is inferred for a query: document d scores
+ *   score(q, d) = sum_i c_i log P(d, w_i),  P(d, w) = sum_k theta^_dk lambda_kw / R_k,  R_k = sum_v lambda_kv
+ * over the batch's entries (w_i, c_i) of query q, in nats, with theta^ as above, the model's lambda at the
+ * time of the call and the row sums formed from it as trlda_model_recommend forms them.  An entry with
+ * c_i <= 0 adds nothing; a query without entries scores 0.0 everywhere; P = 0 gives -inf (ranked last, by
+ * id); no NaN arises.  Per query the first top_n documents in the total order (score descending, id
+ * ascending): ids_out (int64) and loglik_out (fp64), host, B x top_n row-major.  Every P is one chain of
+ * v_mfma_f64_16x16x4_f64 over ascending k and the terms of a score are added in an order that depends
+ * on the entry's position within its query alone; nothing is atomic: a query's result is bitwise the
+ * same alone and inside any batch, whatever trlda_docindex_set_slab_rows says and however the index was
+ * filled, and a document's score does not depend on the other rows of the index.  TRLDA_ERR_ARG, before
+ * anything is waited for, copied or launched: a NULL index, an empty index, top_n outside
+ * [1, min(size, 100)], a batch of another V or device; and, after the row-sum pass and before any other
+ * kernel, a row sum of lambda that is not finite and positive.  Any K >= 1: no E-step runs.  Nothing is
+ * drawn; the index, lambda, alpha, the counters and the model's statistics are left alone; pending
+ * deferred statistics and stream lanes are settled first; the temporaries are the call's own.  The index
+ * stores theta, not lambda: rows added before lambda changed are stale, which is not detected.
+ * Synchronises.  No reference counterpart. */
+int trlda_docindex_query_likelihood(trlda_docindex *index, const trlda_batch *batch, int top_n,
+                                    int64_t *ids_out, double *loglik_out);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

@@ -185,6 +185,7 @@ _SIGNATURES = {
     "trlda_docindex_topic_documents": (C.c_int, [vp, C.c_int, vp, vp]),
     "trlda_docindex_topic_moments": (C.c_int, [vp, vp, vp]),
     "trlda_docindex_set_moment_chunk": (C.c_int, [vp, C.c_int]),
+    "trlda_docindex_query_likelihood": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

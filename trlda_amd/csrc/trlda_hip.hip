@@ -58,6 +58,7 @@
 #include "relevance_kernels.h"
 #include "topicdist_kernels.h"
 #include "topicdocs_kernels.h"
+#include "querylik_kernels.h"
 
 namespace {
 
@@ -6323,6 +6324,103 @@ int trlda_docindex_topic_moments(trlda_docindex *x, double *mean_out, double *sc
     hipError_t e2 = hipMemcpyAsync(scatter_out, out, n * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e3 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- indexed documents by query likelihood (csrc/querylik_kernels.h) ----
+
+extern "C" {
+
+int trlda_docindex_query_likelihood(trlda_docindex *x, const trlda_batch *b, int top_n, int64_t *ids_out,
+                                    double *loglik_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!x)
+        return fail(TRLDA_ERR_ARG, "NULL index");
+    trlda_model *m = x->model;
+    if (int rc_arg = docindex_query_checks(x, top_n))
+        return rc_arg;
+    if (int rc_arg = docindex_batch_checks(m, b))
+        return rc_arg;
+    const int sr = docindex_slab_rows(x);
+    const int64_t slabs = (x->n + sr - 1) / sr, lists = slabs * trlda::kQueryLikWaves;
+    if (lists * top_n > INT_MAX)                         // (the merge's candidate count)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
+    const size_t lds = trlda::querylik_score_lds(top_n);
+    if (lds > 160 * 1024)
+        return fail(TRLDA_ERR_ARG, "the lists do not fit the LDS");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int B = b->B, K = x->K, Kp = x->Kp;
+    if (B <= 0)
+        return TRLDA_OK;
+    if (!ids_out || !loglik_out)
+        return fail(TRLDA_ERR_ARG, "NULL ids / loglik");
+    // every query's rows of the word table start on a tile of 16: tile_off[q] tiles lie before them
+    std::vector<int> tile_off((size_t)B + 1, 0);
+    for (int q = 0; q < B; ++q) {
+        const int64_t n = (int64_t)b->indptr_host[(size_t)q + 1] - b->indptr_host[(size_t)q];
+        const int64_t next = tile_off[(size_t)q] + (n + trlda::kQueryLikWordTile - 1) / trlda::kQueryLikWordTile;
+        if (next > INT_MAX / trlda::kQueryLikWordTile)
+            return fail(TRLDA_ERR_ARG, "too many query words");
+        tile_off[(size_t)q + 1] = (int)next;
+    }
+    const size_t wrows = (size_t)tile_off[(size_t)B] * trlda::kQueryLikWordTile;
+    // the row sums of lambda, looked at on the host before any kernel of the search is launched
+    const double *rs = nullptr;
+    if ((rc = lambda_rowsums(m, &rs)))
+        return rc;
+    std::vector<double> rs_host((size_t)K);
+    {
+        hipError_t e1 = hipMemcpyAsync(rs_host.data(), rs, (size_t)K * sizeof(double), hipMemcpyDeviceToHost,
+                                       m->stream);
+        hipError_t e2 = hipStreamSynchronize(m->stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+    }
+    for (int k = 0; k < K; ++k)
+        if (!(rs_host[(size_t)k] > 0.0) || !std::isfinite(rs_host[(size_t)k]))
+            return fail(TRLDA_ERR_ARG, "query likelihood needs finite, positive row sums of lambda");
+    const size_t cells = (size_t)B * top_n;
+    DevBuf<int> toff;
+    DevBuf<double> wtab, wcnt, scale, cand_s, out_s;
+    DevBuf<long long> cand_i, out_i;
+    if ((rc = toff.alloc((size_t)B + 1)) || (rc = wtab.alloc(wrows * Kp)) || (rc = wcnt.alloc(wrows)) ||
+        (rc = topicdocs_scale(x, scale)) || (rc = cand_s.alloc(cells * lists)) || (rc = cand_i.alloc(cells * lists)) ||
+        (rc = out_s.alloc(cells)) || (rc = out_i.alloc(cells)))
+        return rc;
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::querylik_score_kernel), lds)))
+        return rc;
+    if ((rc = batch_begin(m, b)))
+        return rc;
+    hipStream_t stream = m->stream;
+    // (tile_off lives until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(toff, tile_off.data(), ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+    if (wrows > 0) {
+        hipLaunchKernelGGL(trlda::querylik_words_kernel, dim3((unsigned)B), dim3(trlda::kQueryLikThreads), 0, stream,
+                           K, Kp, m->V, b->indptr, b->ids, b->cnts, toff.get(), m->lambda, rs, wtab.get(),
+                           wcnt.get());
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(trlda::querylik_score_kernel, dim3((unsigned)B, (unsigned)slabs),
+                       dim3(trlda::kQueryLikThreads), lds, stream, Kp, (long long)x->n, B, x->measure, top_n, sr,
+                       x->rows.get(), scale.get(), toff.get(), wtab.get(), wcnt.get(), cand_s.get(), cand_i.get());
+    HIP_TRY(hipGetLastError());
+    // (a wave's list has the layout of a slab's: slabs * 4 of them)
+    hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3((unsigned)B), dim3(trlda::kDocIndexThreads), 0, stream, B,
+                       top_n, (int)lists, cand_s.get(), cand_i.get(), out_i.get(), out_s.get());
+    HIP_TRY(hipGetLastError());
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(ids_out, out_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(loglik_out, out_s, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
 

@@ -2,8 +2,9 @@
 
 A device-resident table of the documents' topic proportions theta = gamma / sum(gamma) and the
 ranked search over it; the topic summaries of the indexed corpus -- per topic its most representative
-documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h).  No
-counterpart in the reference package.
+documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h, DESIGN.md 3.24);
+and the indexed documents that best explain a query's words (csrc/querylik_kernels.h).
+No counterpart in the reference package.
 """
 import ctypes as C
 import operator
@@ -209,6 +210,49 @@ class DocumentIndex(object):
         _ffi.check(_ffi.lib().trlda_docindex_query_gamma(handle, g.ctypes.data, B, top_n, ids.ctypes.data,
                                                          sim.ctypes.data))
         return self._result(ids, sim, return_similarity)
+
+    def query_likelihood(self, queries, top_n=10, per_word=False):
+        """The ``top_n`` indexed documents that best explain each query's words (the query-likelihood
+        document model; Wei & Croft 2006): ``score(q, d) = sum_i c_i log sum_k theta_dk beta_k,w_i``
+        over the query's ``(id, count)`` pairs, in nats, with ``beta_kw = lambda_kw / sum_v lambda_kv``
+        and theta recovered from the stored rows as in ``topic_documents``.  ``queries`` is a list of
+        ``[(id, count), ...]``, a ``DocumentList`` or a ``DeviceBatch``.  Nothing is inferred for a
+        query, so there is no gamma0, nothing is drawn from the seeded stream and any number of
+        topics will do.
+
+        Returns ``(ids, loglik)``, int64 and float64 of shape (B, top_n), in the total order (score
+        descending, id ascending); ``per_word=True`` divides each returned score by the query's
+        ``sum_i c_i`` (the ranking is the same; a query without words keeps 0.0).  A query without
+        words scores 0.0 everywhere, so its ids are ``0 .. top_n - 1``; a document that gives a
+        word no probability scores ``-inf`` and ranks last, by id.  ``1 <= top_n <= min(len(index),
+        100)``, else RuntimeError.
+
+        The call uses the model's lambda as it is now and the stored theta: the index stores theta,
+        not lambda, so after the model's lambda changes, the rows added before are stale.  This is
+        not detected."""
+        handle = self._live()
+        model = self._model
+        top_n = self._top_n(top_n)
+        batch, owned = model._batch(queries)
+        try:
+            model._settle()
+            B = len(batch)
+            ids = np.empty((B, top_n), dtype=np.int64)
+            loglik = np.empty((B, top_n), dtype=np.float64)
+            _ffi.check(_ffi.lib().trlda_docindex_query_likelihood(handle, batch.handle, top_n, ids.ctypes.data,
+                                                                  loglik.ctypes.data))
+            if per_word:
+                csr = batch.csr
+                # (counts <= 0 add nothing on the device either)
+                run = np.concatenate(([0], np.cumsum(np.maximum(np.asarray(csr.cnts, dtype=np.int64), 0))))
+                indptr = np.asarray(csr.indptr, dtype=np.int64)
+                total = (run[indptr[1:]] - run[indptr[:-1]]).astype(np.float64)
+                words = total > 0
+                loglik[words] /= total[words, None]
+        finally:
+            if owned:
+                batch.close()
+        return ids, loglik
 
     # -- topic summaries (csrc/topicdocs_kernels.h, DESIGN.md 3.24) ---------------------------------
     def set_moment_chunk(self, rows):
