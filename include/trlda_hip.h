@@ -674,6 +674,46 @@ int trlda_docindex_set_moment_chunk(trlda_docindex *index, int rows);
 int trlda_docindex_query_likelihood(trlda_docindex *index, const trlda_batch *batch, int top_n,
                                     int64_t *ids_out, double *loglik_out);
 
+/* The document groups of an indexed corpus (csrc/cluster_kernels.h): spherical k-means
+ * on the stored rows, which is Lloyd's algorithm for the index's own measure -- both measures store
+ * unit-length rows x, so the squared Hellinger distance, like the cosine distance, is 1 - <x, m>.
+ * Centroids are given and returned as K x C positive, finite topic proportions laid out like a gamma;
+ * a column's row is the row trlda_docindex_add_gamma would store for it, bitwise.
+ *   s(n, c) = sum_k x_nk m_ck   one chain of v_mfma_f64_16x16x4_f64 over ascending k: the two rows and
+ *                               K alone decide it
+ *   label(n)                    the first c in the total order (s descending, c ascending);
+ *                               sim(n) = s(n, label(n))
+ *   m_c = S_c / |S_c|           S_c = the sum of the rows labelled c, ids ascending, in chunks of 256
+ *                               members added in chunk order; |S_c|^2 in the order the rows' kernel adds
+ *                               its sums: the member set and K alone decide it.  A cluster without
+ *                               members keeps its row.
+ * Nothing is atomic in floating point: two calls agree bitwise, whatever trlda_docindex_set_slab_rows
+ * says and however the index was filled.  TRLDA_CLUSTER_MAX_CLUSTERS (4096) bounds C.  TRLDA_ERR_ARG,
+ * before anything is waited for, copied or launched: a NULL index or required output, an empty index,
+ * C outside [1, min(size, 4096)], max_iter < 0, B < 1 with a gamma; TRLDA_ERR_VALUE, with nothing
+ * changed: a centroid or gamma value that is not finite and positive.  Any K >= 1: no E-step runs.
+ * Nothing is drawn; the index, lambda, alpha, the counters and the model's statistics are left alone;
+ * pending deferred statistics and stream lanes are settled first; the temporaries are the call's own.
+ * Both calls synchronise.
+ *
+ * One assignment.  With gamma_host NULL the N indexed documents are labelled (B is ignored), otherwise
+ * the B columns of gamma_host (K x B), whose rows are formed as trlda_docindex_query_gamma forms them:
+ * labels_out (int32) and, unless NULL, sim_out (fp64), one per document.  No reference counterpart. */
+int trlda_docindex_assign(trlda_docindex *index, const double *centroids_host /* K x C */, int C,
+                          const double *gamma_host /* K x B or NULL */, int B, int32_t *labels_out,
+                          double *sim_out /* may be NULL */);
+/* The loop: assign; if this is not the first assignment and no label changed, stop (*converged_out = 1);
+ * otherwise, if fewer than max_iter updates have run, update the centroids and assign again.  The last
+ * step is an assignment, so labels_out (int32, N) and sim_out (fp64, N) are the assignment under the
+ * returned centroids; *iterations_out is the number of updates that ran; max_iter = 0 is one
+ * assignment.  The count of changed labels is an integer formed on the device, read once per
+ * iteration.  sizes_out (int64, C): the members of each cluster under labels_out.  centroids (K x C
+ * host; in: the initial ones, out: the final ones) returns theta^ of the final rows, recovered as
+ * trlda_docindex_topic_documents recovers it.  No reference counterpart. */
+int trlda_docindex_cluster(trlda_docindex *index, int C, double *centroids /* K x C */, int max_iter,
+                           int32_t *labels_out, double *sim_out /* may be NULL */,
+                           int64_t *sizes_out /* may be NULL */, int *iterations_out, int *converged_out);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

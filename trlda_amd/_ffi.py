@@ -186,6 +186,9 @@ _SIGNATURES = {
     "trlda_docindex_topic_moments": (C.c_int, [vp, vp, vp]),
     "trlda_docindex_set_moment_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_docindex_query_likelihood": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "trlda_docindex_assign": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "trlda_docindex_cluster": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

@@ -58,6 +58,7 @@
 #include "relevance_kernels.h"
 #include "topicdist_kernels.h"
 #include "topicdocs_kernels.h"
+#include "cluster_kernels.h"
 #include "querylik_kernels.h"
 
 namespace {
@@ -6421,6 +6422,256 @@ int trlda_docindex_query_likelihood(trlda_docindex *x, const trlda_batch *b, int
     hipError_t e3 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the document groups of an indexed corpus (csrc/cluster_kernels.h) ----
+
+namespace {
+
+// what both calls check before anything is waited for, copied or launched
+int cluster_checks(const trlda_docindex *x, int C)
+{
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (C < 1 || C > trlda::kClusterMaxClusters || (int64_t)C > x->n)
+        return fail(TRLDA_ERR_ARG, "the number of clusters must lie in [1, min(number of indexed documents, " +
+                                       std::to_string(trlda::kClusterMaxClusters) + ")]");
+    return TRLDA_OK;
+}
+
+// The temporaries of one call, freed when it returns
+struct ClusterWork {
+    DevBuf<double> gstage, crows, sim, part, scale, theta;
+    DevBuf<int> label[2], changed, count;
+    DevBuf<long long> total, off, start, size, cstart, order;
+    int cur = 0;                         // label[cur]: the latest assignment
+};
+
+// gamma (K x B host, checked) -> rows (B x Kp) on the model's stream, through `stage`
+int cluster_rows(trlda_docindex *x, const double *gamma, int B, DevBuf<double> &stage, DevBuf<double> &rows)
+{
+    const size_t count = (size_t)x->K * B;
+    int rc = stage.alloc(count);
+    if (!rc) rc = rows.alloc((size_t)B * x->Kp);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(stage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
+    return docindex_launch_rows(x, stage, B, rows);
+}
+
+// One assignment of the n rows at `docs` to the C centroid rows on the model's stream: into the other
+// label buffer, which becomes the latest; with `count` the labels that differ from the latest so far
+// are counted into w.total.  w.sim, both label buffers and w.changed hold n / n / n / slabs entries.
+int cluster_assign(trlda_docindex *x, ClusterWork &w, const double *docs, long long n, int C, bool count)
+{
+    const int sr = docindex_slab_rows(x);
+    const long long slabs = (n + sr - 1) / sr;
+    const size_t lds = trlda::cluster_assign_lds();
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::cluster_assign_kernel), lds);
+    if (rc)
+        return rc;
+    hipStream_t stream = x->model->stream;
+    const int next = 1 - w.cur;
+    hipLaunchKernelGGL(trlda::cluster_assign_kernel, dim3((unsigned)slabs), dim3(trlda::kClusterThreads), lds, stream,
+                       x->Kp, n, C, sr, docs, w.crows.get(), count ? w.label[w.cur].get() : (const int *)nullptr,
+                       w.label[next].get(), w.sim.get(), w.changed.get());
+    HIP_TRY(hipGetLastError());
+    w.cur = next;
+    if (count) {
+        hipLaunchKernelGGL(trlda::cluster_changed_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, slabs,
+                           w.changed.get(), w.total.get());
+        HIP_TRY(hipGetLastError());
+    }
+    return TRLDA_OK;
+}
+
+int cluster_assign_buffers(trlda_docindex *x, ClusterWork &w, long long n)
+{
+    const int sr = docindex_slab_rows(x);
+    int rc = w.label[0].alloc((size_t)n);
+    if (!rc) rc = w.label[1].alloc((size_t)n);
+    if (!rc) rc = w.sim.alloc((size_t)n);
+    if (!rc) rc = w.changed.alloc((size_t)((n + sr - 1) / sr));
+    if (!rc) rc = w.total.alloc(1);
+    return rc;
+}
+
+// The first two passes of the counting sort of the index's ids by the latest labels: the blocks'
+// counts and their prefix sums (w.count, w.off) and the clusters' runs and chunks (w.start, w.size,
+// w.cstart).
+int cluster_count(trlda_docindex *x, ClusterWork &w, int C)
+{
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    hipStream_t stream = x->model->stream;
+    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
+                       (size_t)C * sizeof(int), stream, N, C, nb, w.label[w.cur].get(), w.count.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::cluster_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, N, C, nb,
+                       w.count.get(), w.off.get(), w.start.get(), w.size.get(), w.cstart.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The stable counting sort itself: after cluster_count the ids take their places in w.order.
+int cluster_sort(trlda_docindex *x, ClusterWork &w, int C)
+{
+    int rc = cluster_count(x, w, C);
+    if (rc)
+        return rc;
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
+                       (size_t)C * sizeof(long long), x->model->stream, N, C, nb, w.label[w.cur].get(), w.off.get(),
+                       w.order.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// m_c = S_c / |S_c| from the latest labels, into w.crows
+int cluster_update(trlda_docindex *x, ClusterWork &w, int C)
+{
+    int rc = cluster_sort(x, w, C);
+    if (rc)
+        return rc;
+    hipStream_t stream = x->model->stream;
+    const long long chunks = trlda::cluster_max_chunks(x->n, C);
+    hipLaunchKernelGGL(trlda::cluster_sum_kernel, dim3((unsigned)chunks), dim3(trlda::kClusterThreads), 0, stream,
+                       x->Kp, C, x->rows.get(), w.order.get(), w.start.get(), w.size.get(), w.cstart.get(),
+                       w.part.get());
+    HIP_TRY(hipGetLastError());
+    constexpr int per_wg = trlda::kClusterThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::cluster_normalise_kernel, dim3((C + per_wg - 1) / per_wg), dim3(trlda::kClusterThreads),
+                       0, stream, x->K, x->Kp, C, w.size.get(), w.cstart.get(), w.part.get(), w.crows.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_assign(trlda_docindex *x, const double *centroids, int C, const double *gamma, int B,
+                          int32_t *labels_out, double *sim_out)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "labels are int32");
+    if (!x || !centroids || !labels_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / centroids / labels");
+    if (int rc_arg = cluster_checks(x, C))
+        return rc_arg;
+    if (gamma && B < 1)
+        return fail(TRLDA_ERR_ARG, "a gamma needs at least one document");
+    if (int rc_val = docindex_check_gamma(centroids, (size_t)x->K * C))
+        return rc_val;
+    if (gamma)
+        if (int rc_val = docindex_check_gamma(gamma, (size_t)x->K * B))
+            return rc_val;
+    const long long n = gamma ? B : x->n;
+    const int sr = docindex_slab_rows(x);
+    if ((n + sr - 1) / sr > INT_MAX)                     // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    ClusterWork w;
+    DevBuf<double> qstage, qrows;
+    if ((rc = cluster_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, n)))
+        return rc;
+    if (gamma && (rc = cluster_rows(x, gamma, B, qstage, qrows)))
+        return rc;
+    if ((rc = cluster_assign(x, w, gamma ? qrows.get() : x->rows.get(), n, C, false)))
+        return rc;
+    hipError_t e1 = hipMemcpyAsync(labels_out, w.label[w.cur], (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = sim_out ? hipMemcpyAsync(sim_out, w.sim, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                                             m->stream)
+                            : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_iter, int32_t *labels_out,
+                           double *sim_out, int64_t *sizes_out, int *iterations_out, int *converged_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "sizes are int64");
+    if (!x || !centroids || !labels_out || !iterations_out || !converged_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / centroids / labels / iterations / converged");
+    if (int rc_arg = cluster_checks(x, C))
+        return rc_arg;
+    if (max_iter < 0)
+        return fail(TRLDA_ERR_ARG, "max_iter must not be negative");
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    const int sr = docindex_slab_rows(x), K = x->K;
+    if ((N + sr - 1) / sr > INT_MAX || nb > INT_MAX)     // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
+    if (int rc_val = docindex_check_gamma(centroids, (size_t)K * C))
+        return rc_val;
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    ClusterWork w;
+    if ((rc = cluster_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, N)) ||
+        (rc = w.count.alloc((size_t)C * nb)) || (rc = w.off.alloc((size_t)C * nb)) || (rc = w.start.alloc(C)) ||
+        (rc = w.size.alloc(C)) || (rc = w.cstart.alloc((size_t)C + 1)) || (rc = w.theta.alloc((size_t)K * C)))
+        return rc;
+    // (only an update sorts the ids and sums their rows)
+    if (max_iter > 0 && ((rc = w.order.alloc((size_t)N)) ||
+                         (rc = w.part.alloc((size_t)trlda::cluster_max_chunks(N, C) * x->Kp))))
+        return rc;
+    if (x->measure != 0 && (rc = w.scale.alloc(C)))
+        return rc;
+    // assign; unless no label changed or max_iter updates have run: update and assign again
+    int iterations = 0, converged = 0;
+    if ((rc = cluster_assign(x, w, x->rows.get(), N, C, false)))
+        return rc;
+    while (iterations < max_iter) {
+        if ((rc = cluster_update(x, w, C)) || (rc = cluster_assign(x, w, x->rows.get(), N, C, true)))
+            return rc;
+        ++iterations;
+        long long changed = -1;
+        hipError_t e1 = hipMemcpyAsync(&changed, w.total, sizeof(long long), hipMemcpyDeviceToHost, stream);
+        hipError_t e2 = hipStreamSynchronize(stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+        if (changed == 0) {
+            converged = 1;
+            break;
+        }
+    }
+    // the sizes under the returned labels; theta^ of the final rows
+    if ((rc = cluster_count(x, w, C)))
+        return rc;
+    if (x->measure != 0) {
+        constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
+        hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((C + per_wg - 1) / per_wg),
+                           dim3(trlda::kTopicDocsThreads), 0, stream, K, x->Kp, (long long)C, w.crows.get(),
+                           w.scale.get());
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t cells = (size_t)K * C;
+    hipLaunchKernelGGL(trlda::cluster_theta_kernel,
+                       dim3((unsigned)((cells + trlda::kClusterThreads - 1) / trlda::kClusterThreads)),
+                       dim3(trlda::kClusterThreads), 0, stream, K, x->Kp, C, x->measure, w.crows.get(), w.scale.get(),
+                       w.theta.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(labels_out, w.label[w.cur], (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   stream);
+    hipError_t e2 = sim_out ? hipMemcpyAsync(sim_out, w.sim, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream)
+                            : hipSuccess;
+    hipError_t e3 = sizes_out ? hipMemcpyAsync(sizes_out, w.size, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                               stream)
+                              : hipSuccess;
+    hipError_t e4 = hipMemcpyAsync(centroids, w.theta, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e5 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
+    HIP_TRY(hipGetLastError());
+    *iterations_out = iterations;
+    *converged_out = converged;
     return TRLDA_OK;
 }
 

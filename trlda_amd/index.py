@@ -3,10 +3,12 @@
 A device-resident table of the documents' topic proportions theta = gamma / sum(gamma) and the
 ranked search over it; the topic summaries of the indexed corpus -- per topic its most representative
 documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h, DESIGN.md 3.24);
-and the indexed documents that best explain a query's words (csrc/querylik_kernels.h).
+the indexed documents that best explain a query's words (csrc/querylik_kernels.h); and
+the document groups of the indexed corpus (csrc/cluster_kernels.h).
 No counterpart in the reference package.
 """
 import ctypes as C
+import math
 import operator
 
 import numpy as np
@@ -15,6 +17,7 @@ from . import _ffi
 
 MEASURES = {"hellinger": 0, "cosine": 1}
 MAX_TOP_N = 100
+MAX_CLUSTERS = 4096                          # TRLDA_CLUSTER_MAX_CLUSTERS
 
 
 def _measure(name):
@@ -299,6 +302,92 @@ class DocumentIndex(object):
         sqrt(S_jj))`` clamped to [-1, 1]: an exact 1 on the diagonal, and NaN wherever one of the
         two variances is 0 (the diagonal included), as ``np.corrcoef`` gives."""
         return _correlation(self._moments()[1])
+
+    # -- document groups (csrc/cluster_kernels.h, DESIGN.md 3.26) -----------------------------------
+    def _num_clusters(self, num_clusters):
+        num_clusters = operator.index(num_clusters)
+        if not 1 <= num_clusters <= min(len(self), MAX_CLUSTERS):
+            raise RuntimeError("`num_clusters` should lie between 1 and min(len(index), %d)." % MAX_CLUSTERS)
+        return num_clusters
+
+    def _theta(self, doc_id):
+        """theta^ of one indexed document from its stored row: ``r * r`` or ``r / sum(r)``."""
+        r = self.rows(doc_id, 1)[0]
+        return r / r.sum() if self._measure else r * r
+
+    def _init_centroids(self, num_clusters, init):
+        """The initial centroids, K x C: drawn ids, given ids, or a given array."""
+        N = len(self)
+        if init is None:
+            from .utils import random_select
+            ids = random_select(num_clusters, N)
+        else:
+            a = np.asarray(init)
+            if not (a.ndim == 1 and a.dtype.kind in "iu" and a.shape[0] == num_clusters):
+                g = self._gamma(init)
+                if g.shape[1] != num_clusters:
+                    raise RuntimeError("`init` should hold `num_clusters` ids or columns.")
+                return g
+            ids = [int(i) for i in a]
+            if len(set(ids)) != len(ids) or min(ids) < 0 or max(ids) >= N:
+                raise ValueError("`init` should hold distinct ids of indexed documents.")
+        return np.asfortranarray(np.stack([self._theta(i) for i in ids], axis=1))
+
+    def cluster(self, num_clusters, init=None, max_iter=50, return_info=False):
+        """The indexed documents in ``num_clusters`` groups by spherical k-means on the stored rows,
+        which is Lloyd's algorithm for the index's own measure: a document goes to the centroid of
+        largest similarity s (the smaller cluster on a tie), a centroid becomes the normalised sum of
+        its members' rows, until no label changes or ``max_iter`` updates have run.  Returns
+        ``(labels, centroids)``: int32 (N,) and the centroids' topic proportions, float64 K x C in
+        Fortran order, ready for ``query_gamma`` (the documents nearest each centroid) or another
+        index's ``add_gamma``; the labels are the assignment under the returned centroids.  With
+        ``return_info=True`` also a dict: ``iterations`` (the updates that ran), ``converged``,
+        ``sizes`` (int64, C), ``similarity`` (float64, N: each document's s to its centroid) and
+        ``objective``, ``math.fsum(1 - similarity)``: the sum of squared Hellinger distances, or of
+        cosine distances.
+
+        ``init``: ``None`` draws ``num_clusters`` distinct ids with ``trlda_amd.utils.random_select``
+        from the seeded stream (the only draw, on the host); a sequence of ``num_clusters`` distinct
+        document ids (integers) starts from their theta; a K x C array is taken as it is (finite and
+        positive).  Duplicate initial centroids leave the later one empty at the first assignment;
+        an empty cluster keeps its centroid and reports size 0.  ``max_iter=0`` is a pure assignment.
+        ``1 <= num_clusters <= min(len(index), 4096)``, else RuntimeError.  Nothing of size N leaves
+        the device but the labels and similarities; two calls agree bitwise."""
+        handle = self._live()
+        num_clusters = self._num_clusters(num_clusters)
+        max_iter = operator.index(max_iter)
+        if max_iter < 0:
+            raise ValueError("`max_iter` should not be negative.")
+        centroids = self._init_centroids(num_clusters, init)
+        N = len(self)
+        labels = np.empty(N, dtype=np.int32)
+        sim = np.empty(N, dtype=np.float64)
+        sizes = np.empty(num_clusters, dtype=np.int64)
+        iterations, converged = C.c_int(0), C.c_int(0)
+        _ffi.check(_ffi.lib().trlda_docindex_cluster(handle, num_clusters, centroids.ctypes.data, max_iter,
+                                                     labels.ctypes.data, sim.ctypes.data, sizes.ctypes.data,
+                                                     C.byref(iterations), C.byref(converged)))
+        if not return_info:
+            return labels, centroids
+        info = {"iterations": iterations.value, "converged": bool(converged.value), "sizes": sizes,
+                "similarity": sim, "objective": math.fsum(1.0 - sim)}
+        return labels, centroids, info
+
+    def nearest_centroid(self, centroids, gamma=None, return_similarity=False):
+        """The label of each indexed document under ``centroids`` (K x C topic proportions, as
+        ``cluster`` returns them) -- or, with ``gamma`` (K x B), of each of those documents; no
+        E-step.  int32; with ``return_similarity=True`` also the similarity s to that centroid."""
+        handle = self._live()
+        c = self._gamma(centroids)
+        num_clusters = self._num_clusters(c.shape[1])
+        g = None if gamma is None else self._gamma(gamma)
+        n = len(self) if g is None else g.shape[1]
+        labels = np.empty(n, dtype=np.int32)
+        sim = np.empty(n, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_assign(handle, c.ctypes.data, num_clusters,
+                                                    None if g is None else g.ctypes.data, 0 if g is None else n,
+                                                    labels.ctypes.data, sim.ctypes.data))
+        return (labels, sim) if return_similarity else labels
 
 
 def _correlation(scatter):
