@@ -714,6 +714,35 @@ int trlda_docindex_cluster(trlda_docindex *index, int C, double *centroids /* K 
                            int32_t *labels_out, double *sim_out /* may be NULL */,
                            int64_t *sizes_out /* may be NULL */, int *iterations_out, int *converged_out);
 
+/* The exact silhouette (Rousseeuw 1987) of indexed documents under a labelling, in the index's own
+ * distance (csrc/silhouette_kernels.h).  labels_host (int32, N = the index's size) holds
+ * values in [0, C); a value without members is allowed and ignored.  With ids_host NULL the N documents
+ * are scored (M is ignored), otherwise the M rows ids_host names, in any order and with repeats, each
+ * against ALL N documents.
+ *   d(i, j)       sqrt(max(0, 1 - s_ij)) (hellinger) or max(0, 1 - s_ij) (cosine); s_ij the dot of the two
+ *                 stored rows, one chain of v_mfma_f64_16x16x4_f64 over ascending k as in
+ *                 trlda_docindex_assign.  The pair (i, i) is left out by id, not by value.
+ *   a(i)          sum_{j in own, j != i} d(i, j) / (n_own - 1)
+ *   b(i)          the smallest sum_{j in c} d(i, j) / n_c over the non-empty c != own; neighbour(i) the
+ *                 first such c in the total order (mean ascending, c ascending)
+ *   sil(i)        (b - a) / max(a, b); 0 where n_own = 1 (a = 0; b and neighbour are still reported) and
+ *                 where max(a, b) = 0
+ * A cluster's members are added by ascending id: the member of rank r joins partial sum r mod 16, the 16
+ * partial sums are added in a fixed tree, so sum_{j in c} d(i, j) depends on row i, the member set of c
+ * and K alone -- not on the other clusters, on c's number, on trlda_docindex_set_slab_rows, on which
+ * other rows are scored or on how the index was filled; two calls agree bitwise.  Nothing of size
+ * M x N or M x C exists.  sil_out, a_out, b_out (fp64) and neighbour_out (int32) hold one value per
+ * scored row.  TRLDA_ERR_ARG, before anything is waited for, copied or launched: a NULL index, labels
+ * or sil_out, an empty index, C outside [2, 4096], M < 1 with ids; TRLDA_ERR_VALUE, with nothing changed
+ * (counted on the host): a label outside [0, C), an id outside [0, N), fewer than two clusters with
+ * members.  Nothing is drawn; the index, lambda, alpha, the counters and the model's statistics are left
+ * alone; pending deferred statistics and stream lanes are settled first; the temporaries are the call's
+ * own.  Synchronises.  No reference counterpart. */
+int trlda_docindex_silhouette(trlda_docindex *index, const int32_t *labels_host /* N */, int C,
+                              const int64_t *ids_host /* M or NULL: all N */, int64_t M, double *sil_out,
+                              double *a_out /* may be NULL */, double *b_out /* may be NULL */,
+                              int32_t *neighbour_out /* may be NULL */);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

@@ -59,6 +59,7 @@
 #include "topicdist_kernels.h"
 #include "topicdocs_kernels.h"
 #include "cluster_kernels.h"
+#include "silhouette_kernels.h"
 #include "querylik_kernels.h"
 
 namespace {
@@ -6672,6 +6673,103 @@ int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_
     HIP_TRY(hipGetLastError());
     *iterations_out = iterations;
     *converged_out = converged;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the silhouette of an indexed corpus under a labelling (csrc/silhouette_kernels.h) ----
+
+extern "C" {
+
+int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int C, const int64_t *ids_host,
+                              int64_t M, double *sil_out, double *a_out, double *b_out, int32_t *neighbour_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, labels int32");
+    if (!x || !labels_host || !sil_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / labels / silhouette");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (C < 2 || C > trlda::kClusterMaxClusters)
+        return fail(TRLDA_ERR_ARG, "the number of label values must lie in [2, " +
+                                       std::to_string(trlda::kClusterMaxClusters) + "]");
+    if (ids_host && M < 1)
+        return fail(TRLDA_ERR_ARG, "a list of ids needs at least one id");
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    const long long rows = ids_host ? (long long)M : N;
+    const long long blocks = (rows + trlda::kSilhouetteRows - 1) / trlda::kSilhouetteRows;
+    if (blocks > INT_MAX || nb > INT_MAX)                // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many rows to score in one call");
+    // the labels and ids, counted on the host
+    std::vector<long long> members((size_t)C, 0);
+    for (long long d = 0; d < N; ++d) {
+        const int32_t lab = labels_host[d];
+        if (lab < 0 || lab >= C)
+            return fail(TRLDA_ERR_VALUE, "a label lies outside [0, C)");
+        ++members[(size_t)lab];
+    }
+    long long padded = 0;
+    int nonempty = 0;
+    for (int c = 0; c < C; ++c) {
+        nonempty += members[(size_t)c] > 0;
+        padded += (members[(size_t)c] + 15) / 16 * 16;
+    }
+    if (nonempty < 2)
+        return fail(TRLDA_ERR_VALUE, "a silhouette needs at least two clusters with members");
+    if (ids_host)
+        for (int64_t i = 0; i < M; ++i)
+            if (ids_host[i] < 0 || ids_host[i] >= N)
+                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
+    const long long P = trlda::silhouette_positions(padded);
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<int> label, count, flush, nbr;
+    DevBuf<long long> ids, off, size, pos;
+    DevBuf<double> sil, a, b;
+    if ((rc = label.alloc((size_t)N)) || (rc = count.alloc((size_t)C * nb)) || (rc = off.alloc((size_t)C * nb)) ||
+        (rc = size.alloc(C)) || (rc = pos.alloc((size_t)P)) || (rc = flush.alloc((size_t)(P / 16))) ||
+        (rc = sil.alloc((size_t)rows)) || (rc = a.alloc((size_t)rows)) || (rc = b.alloc((size_t)rows)) ||
+        (rc = nbr.alloc((size_t)rows)))
+        return rc;
+    if (ids_host && (rc = ids.alloc((size_t)M)))
+        return rc;
+    const size_t lds = trlda::silhouette_pairs_lds();
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::silhouette_pairs_kernel), lds)))
+        return rc;
+    // (labels_host and ids_host live until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(label, labels_host, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (ids_host)
+        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    // every position a padding one, no tile a cluster's last: all bits set is -1
+    HIP_TRY(hipMemsetAsync(pos, 0xFF, (size_t)P * sizeof(long long), stream));
+    HIP_TRY(hipMemsetAsync(flush, 0xFF, (size_t)(P / 16) * sizeof(int), stream));
+    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
+                       (size_t)C * sizeof(int), stream, N, C, nb, label.get(), count.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::silhouette_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, C, nb,
+                       count.get(), off.get(), size.get(), flush.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
+                       (size_t)C * sizeof(long long), stream, N, C, nb, label.get(), off.get(), pos.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::silhouette_pairs_kernel, dim3((unsigned)blocks), dim3(trlda::kSilhouetteThreads), lds,
+                       stream, x->Kp, rows, P, x->measure, x->rows.get(),
+                       ids_host ? ids.get() : (const long long *)nullptr, label.get(), size.get(), pos.get(),
+                       flush.get(), sil.get(), a.get(), b.get(), nbr.get());
+    HIP_TRY(hipGetLastError());
+    const size_t bytes = (size_t)rows * sizeof(double);
+    hipError_t e1 = hipMemcpyAsync(sil_out, sil, bytes, hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = a_out ? hipMemcpyAsync(a_out, a, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    hipError_t e3 = b_out ? hipMemcpyAsync(b_out, b, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    hipError_t e4 = neighbour_out ? hipMemcpyAsync(neighbour_out, nbr, (size_t)rows * sizeof(int32_t),
+                                                   hipMemcpyDeviceToHost, stream)
+                                  : hipSuccess;
+    hipError_t e5 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
+    HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
 

@@ -4,7 +4,8 @@ A device-resident table of the documents' topic proportions theta = gamma / sum(
 ranked search over it; the topic summaries of the indexed corpus -- per topic its most representative
 documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h, DESIGN.md 3.24);
 the indexed documents that best explain a query's words (csrc/querylik_kernels.h); and
-the document groups of the indexed corpus (csrc/cluster_kernels.h).
+the document groups of the indexed corpus (csrc/cluster_kernels.h) and their
+silhouettes (csrc/silhouette_kernels.h).
 No counterpart in the reference package.
 """
 import ctypes as C
@@ -388,6 +389,98 @@ class DocumentIndex(object):
                                                     None if g is None else g.ctypes.data, 0 if g is None else n,
                                                     labels.ctypes.data, sim.ctypes.data))
         return (labels, sim) if return_similarity else labels
+
+    # -- silhouettes (csrc/silhouette_kernels.h) -----------------------------------
+    def silhouette(self, labels, ids=None, return_parts=False):
+        """The exact silhouette (Rousseeuw 1987) of the indexed documents under ``labels`` -- those of
+        ``cluster`` or any grouping the caller brings -- in the index's own distance ``d``,
+        ``sqrt(max(0, 1 - s))`` (hellinger) or ``max(0, 1 - s)`` (cosine).  For document i of cluster
+        ``own``: ``a`` is its mean distance to the other members of ``own``, ``b`` the smallest mean
+        distance to the members of another non-empty cluster, ``neighbour`` that cluster (the smaller
+        label on a tie), and the silhouette ``(b - a) / max(a, b)``: 0.0 for the only member of a
+        cluster (with ``a = 0.0``) and where ``max(a, b) = 0``.  A document is left out of its own
+        mean by id, so two documents with equal rows are a pair at distance 0.
+
+        ``labels``: an integer array of length ``len(index)`` with values in ``[0, C)``,
+        ``C = max(labels) + 1 <= 4096``; values without members are ignored.  Fewer than two clusters
+        with members is a ValueError; a wrong length, a negative label or C > 4096 a RuntimeError; a
+        non-integer array a TypeError.  ``ids=None`` scores every document; otherwise ``ids`` is an
+        integer array of row ids (any order, repeats allowed; out of range: RuntimeError), each scored
+        against ALL indexed documents: an exact subsample -- ``utils.random_select`` draws one -- at
+        cost ``len(ids) * N * K``.
+
+        Returns the silhouettes, float64, one per scored document; with ``return_parts=True``
+        ``(s, a, b, neighbour)``, float64 and int32.  The corpus figure is ``math.fsum(s) / len(s)``
+        on the host.  A cluster's sum of distances depends on the document, the cluster's members and
+        K alone, so two calls agree bitwise, whatever the other clusters, their numbering, the slab
+        setting, the rows scored beside it or the way the index was filled.  Nothing is drawn."""
+        handle = self._live()
+        N = len(self)
+        lab, num_clusters = _silhouette_labels(labels, N)
+        rows = _silhouette_ids(ids, N)
+        n = N if rows is None else rows.shape[0]
+        s = np.empty(n, dtype=np.float64)
+        if return_parts:
+            a, b = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+            neighbour = np.empty(n, dtype=np.int32)
+        _ffi.check(_ffi.lib().trlda_docindex_silhouette(handle, lab.ctypes.data, num_clusters,
+                                                        None if rows is None else rows.ctypes.data,
+                                                        0 if rows is None else n, s.ctypes.data,
+                                                        a.ctypes.data if return_parts else None,
+                                                        b.ctypes.data if return_parts else None,
+                                                        neighbour.ctypes.data if return_parts else None))
+        return (s, a, b, neighbour) if return_parts else s
+
+    def select_num_clusters(self, candidates, max_iter=50, ids=None):
+        """The number of clusters among ``candidates`` of largest mean silhouette: for each C, in the
+        order given, ``cluster(C, max_iter=max_iter)`` (``init=None``: one ``random_select`` per
+        candidate from the seeded stream) and ``silhouette(labels, ids=ids)``.  Returns ``(best_C,
+        {C: mean silhouette})``, ``best_C`` the first in the order (mean descending, C ascending); a
+        candidate whose clustering leaves fewer than two clusters with members scores ``-inf``."""
+        scores = {}
+        for num_clusters in candidates:
+            num_clusters = operator.index(num_clusters)
+            labels, _ = self.cluster(num_clusters, max_iter=max_iter)
+            if len(np.unique(labels)) < 2:
+                scores[num_clusters] = -math.inf
+                continue
+            s = self.silhouette(labels, ids=ids)
+            scores[num_clusters] = math.fsum(s) / len(s)
+        if not scores:
+            raise ValueError("`candidates` should hold at least one number of clusters.")
+        return min(scores, key=lambda c: (-scores[c], c)), scores
+
+
+def _silhouette_labels(labels, N):
+    """(labels as contiguous int32, C) of ``silhouette``'s labels for an index of N documents, or the
+    documented error; no device is needed."""
+    lab = np.asarray(labels)
+    if lab.dtype.kind not in "iu":
+        raise TypeError("`labels` should be an array of integers.")
+    if N < 1:
+        raise RuntimeError("The index is empty.")
+    if lab.ndim != 1 or lab.shape[0] != N:
+        raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
+    low, high = int(lab.min()), int(lab.max())
+    if low < 0 or high >= MAX_CLUSTERS:
+        raise RuntimeError("`labels` should lie between 0 and %d." % (MAX_CLUSTERS - 1))
+    if low == high:                                          # (the smallest is also the largest: one cluster)
+        raise ValueError("A silhouette needs at least two clusters with members.")
+    return np.ascontiguousarray(lab, dtype=np.int32), high + 1
+
+
+def _silhouette_ids(ids, N):
+    """``silhouette``'s ids as contiguous int64 (None: every document), or the documented error."""
+    if ids is None:
+        return None
+    rows = np.asarray(ids)
+    if rows.dtype.kind not in "iu":
+        raise TypeError("`ids` should be an array of integers.")
+    if rows.ndim != 1 or rows.shape[0] < 1:
+        raise RuntimeError("`ids` should be a one-dimensional array of at least one id.")
+    if int(rows.min()) < 0 or int(rows.max()) >= N:
+        raise RuntimeError("`ids` should be ids of indexed documents, between 0 and %d." % (N - 1))
+    return np.ascontiguousarray(rows, dtype=np.int64)
 
 
 def _correlation(scatter):
