@@ -807,6 +807,47 @@ int trlda_model_relevant_words(trlda_model *model, int top_n, double weight, con
 int trlda_model_salient_words(trlda_model *model, int top_n, const double *topic_weights,
                               int32_t *words_out, double *saliency_out);
 
+/* The words nearest a word in topic space (csrc/wordsim_kernels.h).  With R_k, pi and
+ * c_k = pi_k / R_k as above (topic_weights: NULL or K host values, the rule of
+ * trlda_model_relevant_words), a_kw = c_k lambda_kw and p(k | w) = a_kw / sum_j a_jw, word w has the row
+ *   measure 0 (hellinger):  r_wk = sqrt(p(k | w))                 s = the Bhattacharyya coefficient
+ *   measure 1 (cosine):     r_wk = a_kw / sqrt(sum_j a_jw^2)      s = the cosine
+ * and s(q, w) = sum_k r_qk r_wk -- the two measures of trlda_docindex_create -- formed on the matrix
+ * cores from lambda where it lies: no V x K table of rows and no copy of lambda exist.  words_out
+ * (int32) and sim_out (fp64), host, B x top_n row-major: per query the first top_n words in the total
+ * order (s descending, word id ascending) and their s.  s(q, w) depends on columns q and w of lambda,
+ * on c and on K alone: a query's row is bitwise the same alone and inside any batch, whatever the slab
+ * width; s(q, w) and s(w, q) are the same bits; two calls agree bitwise (no atomics).
+ * TRLDA_ERR_ARG, before anything is allocated or launched: a NULL model or output, B < 0, top_n outside
+ * [1, min(V - e, 100)] (e = 1 with exclude_self, else 0), a measure that is not 0 or 1, a weight that
+ * is not finite or <= 0; then TRLDA_ERR_WORD_ID for an id outside [0, V) and TRLDA_ERR_VALUE for
+ * proportions that are not finite or not > 0.  A lambda with an element <= 0 or not finite fails with
+ * TRLDA_ERR_VALUE ("word similarity needs a positive, finite lambda") and nothing is written to the
+ * outputs.  B = 0 writes nothing.  lambda, alpha, the counters, the statistics and the seeded stream are
+ * left alone, nothing is drawn; pending deferred statistics and stream lanes are settled first.  Each
+ * call synchronises. */
+
+/* The words nearest the B words word_ids (host).  With exclude_self != 0 the query word itself is left
+ * out of its own ranking by id; another word with an equal column stays in, at s = 1 up to rounding.
+ * No reference counterpart. */
+int trlda_model_similar_words(trlda_model *model, const int32_t *word_ids /* B */, int B, int top_n,
+                              int measure, const double *topic_weights /* K or NULL */, int exclude_self,
+                              int32_t *words_out /* B x top_n */, double *sim_out /* B x top_n */);
+/* The words nearest B points of the topic simplex: proportions (K x B fp64 host, finite and > 0,
+ * normalised as trlda_docindex_query_gamma normalises gamma) -- a document's theta, a centroid of
+ * trlda_docindex_cluster, a topic.  There is no self to leave out.  No reference counterpart. */
+int trlda_model_similar_words_rows(trlda_model *model, const double *proportions /* K x B */, int B, int top_n,
+                                   int measure, const double *topic_weights /* K or NULL */,
+                                   int32_t *words_out /* B x top_n */, double *sim_out /* B x top_n */);
+/* out (K x B fp64 host, column-major: [b * K + k]) = p(k | word_ids[b]), the quantity the measures
+ * compare; its sum over k in the order of the ranking's column pass.  The errors of
+ * trlda_model_similar_words that apply.  No reference counterpart. */
+int trlda_model_word_topic_proportions(trlda_model *model, const int32_t *word_ids /* B */, int B,
+                                       const double *topic_weights /* K or NULL */, double *out);
+/* A/B switch for tests and measurements: words per workgroup of the ranking (a positive multiple of
+ * 16; 0: the default, 2048).  The results do not depend on it.  No reference counterpart. */
+int trlda_model_set_wordsim_slab_words(trlda_model *model, int words);
+
 /* A prevalence accumulator for `model`: pi_k ~ sum_d N_d gamma_dk / sum_j gamma_dj over the documents
  * added, N_d = the sum of document d's positive counts (weight_by_length == 0: 1); a document without
  * a positive count is skipped.  K fp64 sums stay on the device between batches: one addition per

@@ -162,6 +162,10 @@ _SIGNATURES = {
     "trlda_model_word_stats": (C.c_int, [vp, vp, vp, vp, vp]),
     "trlda_model_relevant_words": (C.c_int, [vp, C.c_int, C.c_double, vp, vp, vp]),
     "trlda_model_salient_words": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "trlda_model_similar_words": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "trlda_model_similar_words_rows": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "trlda_model_word_topic_proportions": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "trlda_model_set_wordsim_slab_words": (C.c_int, [vp, C.c_int]),
     "trlda_prevalence_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "trlda_prevalence_add": (C.c_int, [vp, vp, vp, C.c_int, C.c_double]),
     "trlda_prevalence_add_dev": (C.c_int, [vp, vp, vp]),

@@ -61,6 +61,7 @@
 #include "cluster_kernels.h"
 #include "silhouette_kernels.h"
 #include "querylik_kernels.h"
+#include "wordsim_kernels.h"
 
 namespace {
 
@@ -718,6 +719,15 @@ struct trlda_model {
         DevBuf<int32_t> ids;
         DevBuf<int> flag;
     } relevance;
+    // the words nearest a word (wordsim_kernels.h, trlda_model_similar_words*,
+    // _word_topic_proportions; c, the given weights and the flag are relevance's): the words'
+    // scales (V), the queries' ids, rows and scales, the proportions' staging (K x B, also the
+    // output of _word_topic_proportions), the slabs' lists and the ranked output
+    struct {
+        DevBuf<double> scale, qrows, qscale, stage, cand_s, out_s;
+        DevBuf<int32_t> ids, cand_i, out_w;
+        int slab_words = 0;                     // 0: kWordSimSlabWords (trlda_model_set_wordsim_slab_words)
+    } wordsim;
 };
 
 namespace {
@@ -6992,17 +7002,16 @@ int relevance_weights(const trlda_model *m, const double *topic_weights, std::ve
     return TRLDA_OK;
 }
 
-// The column pass on the model's stream: the row sums of lambda formed from lambda itself
-// (lambda_rowsums: an order that depends on K and V only, whatever an E-step left behind), c, log R
-// and log pi, then p, D, S and log p of every word into relevance.stats and the flag.
-int relevance_stats(trlda_model *m, const std::vector<double> &pi)
+// On the model's stream: the row sums of lambda formed from lambda itself (lambda_rowsums: an order
+// that depends on K and V only, whatever an E-step left behind), then c, log R and log pi into
+// relevance.coef; the flag is cleared.  Shared with the word similarities (wordsim_kernels.h).
+int relevance_coef(trlda_model *m, const std::vector<double> &pi)
 {
     auto &g = m->relevance;
-    const int K = m->K, V = m->V;
+    const int K = m->K;
     const double *rs = nullptr;
     int rc = lambda_rowsums(m, &rs);
     if (!rc) rc = g.coef.grow(3 * (size_t)K);
-    if (!rc) rc = g.stats.grow(4 * (size_t)V);
     if (!rc) rc = g.flag.grow(1);
     if (!rc && !pi.empty()) rc = g.pi.grow((size_t)K);
     if (rc)
@@ -7017,6 +7026,19 @@ int relevance_stats(trlda_model *m, const std::vector<double> &pi)
     hipLaunchKernelGGL(trlda::relevance_coef_kernel, dim3(1), dim3(trlda::kWave), 0, m->stream, K, rs,
                        pi.empty() ? (const double *)nullptr : (const double *)g.pi, g.coef.get());
     HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The column pass behind relevance_coef: p, D, S and log p of every word into relevance.stats, and
+// the flag.
+int relevance_stats(trlda_model *m, const std::vector<double> &pi)
+{
+    auto &g = m->relevance;
+    const int K = m->K, V = m->V;
+    int rc = g.stats.grow(4 * (size_t)V);
+    if (!rc) rc = relevance_coef(m, pi);
+    if (rc)
+        return rc;
     constexpr int per_wg = trlda::kRelevanceThreads / trlda::kWave;
     hipLaunchKernelGGL(trlda::relevance_column_kernel, dim3((V + per_wg - 1) / per_wg),
                        dim3(trlda::kRelevanceThreads), 0, m->stream, K, V, m->lambda, g.coef.get(), g.stats.get(),
@@ -7026,7 +7048,7 @@ int relevance_stats(trlda_model *m, const std::vector<double> &pi)
 }
 
 // waits for the stream and fails when the column pass met a bad lambda
-int relevance_settle(trlda_model *m)
+int relevance_settle(trlda_model *m, const char *what = "relevance")
 {
     int flag = 0;
     hipError_t e1 = hipMemcpyAsync(&flag, m->relevance.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
@@ -7034,7 +7056,7 @@ int relevance_settle(trlda_model *m)
     HIP_TRY(e1); HIP_TRY(e2);
     HIP_TRY(hipGetLastError());
     if (flag)
-        return fail(TRLDA_ERR_VALUE, "relevance needs a positive, finite lambda");
+        return fail(TRLDA_ERR_VALUE, std::string(what) + " needs a positive, finite lambda");
     return TRLDA_OK;
 }
 
@@ -7362,6 +7384,262 @@ int trlda_prevalence_destroy(trlda_prevalence *p)
     if (p->model && use_device(p->model->device) == TRLDA_OK && p->model->stream)
         (void)hipStreamSynchronize(p->model->stream);    // (its kernels may still read the buffers)
     delete p;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the words nearest a word in topic space (csrc/wordsim_kernels.h) ----
+
+namespace {
+
+int wordsim_slab_words(const trlda_model *m)
+{
+    return m->wordsim.slab_words > 0 ? m->wordsim.slab_words : trlda::kWordSimSlabWords;
+}
+
+// what the ranking calls check before anything is allocated or launched; e: 1 with exclude_self
+int wordsim_checks(const trlda_model *m, int B, int top_n, int measure, int e)
+{
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "a negative number of queries");
+    if (top_n < 1 || top_n > trlda::kWordSimMaxTop || top_n > m->V - e)
+        return fail(TRLDA_ERR_ARG, e ? "top_n must lie in [1, min(num_words - 1, 100)]"
+                                     : "top_n must lie in [1, min(num_words, 100)]");
+    if (measure < 0 || measure >= trlda::kDocIndexMeasures)
+        return fail(TRLDA_ERR_ARG, "unknown measure");
+    const int sw = wordsim_slab_words(m);
+    if ((m->V + sw - 1) / sw > 65535)                    // (grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_model_set_wordsim_slab_words");
+    return TRLDA_OK;
+}
+
+int wordsim_check_ids(const trlda_model *m, const int32_t *word_ids, int B)
+{
+    for (int b = 0; b < B; ++b)
+        if (word_ids[b] < 0 || word_ids[b] >= m->V)
+            return fail(TRLDA_ERR_WORD_ID, "word id outside [0, num_words)");
+    return TRLDA_OK;
+}
+
+// the B query ids onto the device (waited for: they are the caller's)
+int wordsim_upload_ids(trlda_model *m, const int32_t *word_ids, int B)
+{
+    auto &g = m->wordsim;
+    int rc = g.ids.grow((size_t)B);
+    if (rc)
+        return rc;
+    hipError_t e1 = hipMemcpyAsync(g.ids, word_ids, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    return TRLDA_OK;
+}
+
+// c (relevance_coef) and the column pass: every word's scale under `measure`, and the flag
+int wordsim_norms(trlda_model *m, const std::vector<double> &pi, int measure)
+{
+    auto &g = m->wordsim;
+    const int K = m->K, V = m->V;
+    int rc = g.scale.grow((size_t)V);
+    if (!rc) rc = relevance_coef(m, pi);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kWordSimThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::wordsim_norm_kernel, dim3((V + per_wg - 1) / per_wg), dim3(trlda::kWordSimThreads), 0,
+                       m->stream, K, V, measure, m->lambda, m->relevance.coef.get(), g.scale.get(),
+                       m->relevance.flag.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+template <int SW>
+int wordsim_launch_query(trlda_model *m, int B, int top_n, int measure, int slab_words, int slabs,
+                         const double *qscale, const int32_t *qid)
+{
+    auto &g = m->wordsim;
+    const size_t lds = trlda::wordsim_query_lds(SW, top_n);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::wordsim_query_kernel<SW>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::wordsim_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
+                       dim3(trlda::kWordSimThreads), lds, m->stream, m->K, (m->K + 3) / 4 * 4, m->V, B, top_n,
+                       slab_words, measure, m->lambda, m->relevance.coef.get(), g.scale.get(), g.qrows.get(), qscale,
+                       qid, g.cand_s.get(), g.cand_i.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// room for the ranking of B queries (the rows, the slabs' lists, the output)
+int wordsim_room(trlda_model *m, int B, int top_n)
+{
+    auto &g = m->wordsim;
+    const int Kp = (m->K + 3) / 4 * 4, sw = wordsim_slab_words(m);
+    const size_t cells = (size_t)B * top_n, slabs = (size_t)((m->V + sw - 1) / sw);
+    int rc = g.qrows.grow((size_t)B * Kp);
+    if (!rc) rc = g.cand_s.grow(cells * slabs);
+    if (!rc) rc = g.cand_i.grow(cells * slabs);
+    if (!rc) rc = g.out_s.grow(cells);
+    if (!rc) rc = g.out_w.grow(cells);
+    return rc;
+}
+
+// The ranking of the B rows in wordsim.qrows (scales qscale or 1, ids qid or none) against every
+// word, the merge, the flag, then the results to the host.  Waits.
+int wordsim_rank(trlda_model *m, int B, int top_n, int measure, const double *qscale, const int32_t *qid,
+                 int32_t *words_out, double *sim_out)
+{
+    auto &g = m->wordsim;
+    const int sw = wordsim_slab_words(m);
+    const int slabs = (m->V + sw - 1) / sw;
+    // (128 queries per workgroup while their lists fit beside the operands, 64 beyond)
+    int rc = top_n <= trlda::kWordSimWideMaxTop
+                 ? wordsim_launch_query<2>(m, B, top_n, measure, sw, slabs, qscale, qid)
+                 : wordsim_launch_query<1>(m, B, top_n, measure, sw, slabs, qscale, qid);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::recommend_merge_kernel, dim3(B), dim3(trlda::kRecommendThreads), 0, m->stream, B,
+                       top_n, slabs, g.cand_s.get(), g.cand_i.get(), g.out_w.get(), g.out_s.get());
+    HIP_TRY(hipGetLastError());
+    rc = relevance_settle(m, "word similarity");
+    if (rc)
+        return rc;
+    const size_t cells = (size_t)B * top_n;
+    hipError_t e1 = hipMemcpyAsync(words_out, g.out_w, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(sim_out, g.out_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_set_wordsim_slab_words(trlda_model *m, int words)
+{
+    if (!m || words < 0 || words % 16)
+        return fail(TRLDA_ERR_ARG, "slab words: 0 (default) or a positive multiple of 16");
+    m->wordsim.slab_words = words;
+    return TRLDA_OK;
+}
+
+int trlda_model_similar_words(trlda_model *m, const int32_t *word_ids, int B, int top_n, int measure,
+                              const double *topic_weights, int exclude_self, int32_t *words_out, double *sim_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!words_out || !sim_out)
+        return fail(TRLDA_ERR_ARG, "NULL output");
+    if (int rc_arg = wordsim_checks(m, B, top_n, measure, exclude_self ? 1 : 0))
+        return rc_arg;
+    if (B > 0 && !word_ids)
+        return fail(TRLDA_ERR_ARG, "word_ids is NULL");
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    if (int rc_id = wordsim_check_ids(m, word_ids, B))
+        return rc_id;
+    int rc = check_model(m);
+    if (rc || B == 0)
+        return rc;
+    auto &g = m->wordsim;
+    const int K = m->K, Kp = (K + 3) / 4 * 4;
+    rc = wordsim_room(m, B, top_n);
+    if (!rc) rc = g.qscale.grow((size_t)B);
+    if (!rc) rc = wordsim_upload_ids(m, word_ids, B);
+    if (!rc) rc = wordsim_norms(m, pi, measure);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kWordSimThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::wordsim_rows_kernel, dim3((B + per_wg - 1) / per_wg), dim3(trlda::kWordSimThreads), 0,
+                       m->stream, K, Kp, B, measure, m->lambda, m->relevance.coef.get(), g.ids.get(), g.scale.get(),
+                       g.qrows.get(), g.qscale.get());
+    HIP_TRY(hipGetLastError());
+    return wordsim_rank(m, B, top_n, measure, g.qscale, exclude_self ? (const int32_t *)g.ids : nullptr, words_out,
+                        sim_out);
+}
+
+int trlda_model_similar_words_rows(trlda_model *m, const double *proportions, int B, int top_n, int measure,
+                                   const double *topic_weights, int32_t *words_out, double *sim_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!words_out || !sim_out)
+        return fail(TRLDA_ERR_ARG, "NULL output");
+    if (int rc_arg = wordsim_checks(m, B, top_n, measure, 0))
+        return rc_arg;
+    if (B > 0 && !proportions)
+        return fail(TRLDA_ERR_ARG, "proportions is NULL");
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    const size_t count = (size_t)m->K * (size_t)B;
+    for (size_t i = 0; i < count; ++i)
+        if (!(proportions[i] > 0.0) || !std::isfinite(proportions[i]))
+            return fail(TRLDA_ERR_VALUE, "proportions should be finite and positive");
+    int rc = check_model(m);
+    if (rc || B == 0)
+        return rc;
+    auto &g = m->wordsim;
+    const int K = m->K, Kp = (K + 3) / 4 * 4;
+    rc = wordsim_room(m, B, top_n);
+    if (!rc) rc = g.stage.grow(count);
+    if (rc)
+        return rc;
+    {
+        hipError_t e1 = hipMemcpyAsync(g.stage, proportions, count * sizeof(double), hipMemcpyHostToDevice, m->stream);
+        hipError_t e2 = hipStreamSynchronize(m->stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+    }
+    rc = wordsim_norms(m, pi, measure);
+    if (rc)
+        return rc;
+    // (unit rows as the document index makes them: their scale is 1)
+    constexpr int per_wg = trlda::kDocIndexThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::docindex_rows_kernel, dim3((B + per_wg - 1) / per_wg), dim3(trlda::kDocIndexThreads), 0,
+                       m->stream, K, Kp, B, measure, (const double *)g.stage, g.qrows.get());
+    HIP_TRY(hipGetLastError());
+    return wordsim_rank(m, B, top_n, measure, nullptr, nullptr, words_out, sim_out);
+}
+
+int trlda_model_word_topic_proportions(trlda_model *m, const int32_t *word_ids, int B, const double *topic_weights,
+                                       double *out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "NULL output");
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "a negative number of words");
+    if (B > 0 && !word_ids)
+        return fail(TRLDA_ERR_ARG, "word_ids is NULL");
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    if (int rc_id = wordsim_check_ids(m, word_ids, B))
+        return rc_id;
+    int rc = check_model(m);
+    if (rc || B == 0)
+        return rc;
+    auto &g = m->wordsim;
+    const int K = m->K;
+    const size_t count = (size_t)K * (size_t)B;
+    rc = g.stage.grow(count);
+    if (!rc) rc = wordsim_upload_ids(m, word_ids, B);
+    if (!rc) rc = wordsim_norms(m, pi, 0);                // (the whole of lambda is checked)
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kWordSimThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::wordsim_props_kernel, dim3((B + per_wg - 1) / per_wg), dim3(trlda::kWordSimThreads), 0,
+                       m->stream, K, B, m->lambda, m->relevance.coef.get(), g.ids.get(), g.stage.get());
+    HIP_TRY(hipGetLastError());
+    rc = relevance_settle(m, "word similarity");
+    if (rc)
+        return rc;
+    hipError_t e1 = hipMemcpyAsync(out, g.stage, count * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
     return TRLDA_OK;
 }
 

@@ -16,6 +16,7 @@ import numpy as np
 
 from .. import _ffi
 from ..documents import CSRDocuments, DeviceBatch, DocumentList, as_csr
+from ..index import _measure
 
 __all__ = ["Distribution", "LDA", "OnlineLDA", "BatchLDA", "CumulativeLDA"]
 
@@ -1167,6 +1168,121 @@ class LDA(Distribution):
         _ffi.check(_ffi.lib().trlda_model_salient_words(
             handle, top_n, None if pi is None else pi.ctypes.data, words.ctypes.data, sal.ctypes.data))
         return words, sal
+
+    # -- the words nearest a word in topic space (csrc/wordsim_kernels.h) --------------------------
+    def _word_ids(self, words):
+        """The query words as B contiguous int32 ids (a single int: one query)."""
+        if isinstance(words, np.ndarray):
+            if words.dtype.kind not in "iu":
+                raise TypeError("`words` should hold integer word ids.")
+            ids = [int(w) for w in words.reshape(-1)]
+        else:
+            try:
+                ids = [operator.index(words)]
+            except TypeError:
+                try:
+                    ids = [operator.index(w) for w in words]
+                except TypeError:
+                    raise TypeError("`words` should be a word id or a sequence of word ids.")
+        if any(not 0 <= w < self._V for w in ids):
+            raise RuntimeError("Word id outside [0, num_words).")
+        return np.array(ids, dtype=np.int32)
+
+    def _wordsim_top_n(self, top_n, exclude_self):
+        top_n = operator.index(top_n)
+        if exclude_self:
+            if not 1 <= top_n <= min(self._V - 1, 100):
+                raise RuntimeError("`top_n` should lie between 1 and min(num_words - 1, 100).")
+        elif not 1 <= top_n <= min(self._V, 100):
+            raise RuntimeError("`top_n` should lie between 1 and min(num_words, 100).")
+        return top_n
+
+    @staticmethod
+    def _wordsim_result(ids, sim, measure, return_similarity):
+        if return_similarity:
+            return ids, sim
+        rest = np.maximum(0.0, 1.0 - sim)
+        return ids, (rest if measure else np.sqrt(rest))
+
+    def similar_words(self, words, top_n=10, measure="hellinger", topic_weights=None, exclude_self=True,
+                      return_similarity=False):
+        """The ``top_n`` words the model treats most like each of ``words`` (a word id or a
+        sequence of B ids): every word is the distribution over topics ``p(k | w) = pi_k beta_kw /
+        p_w`` (``word_statistics``), and two words are compared as ``DocumentIndex`` compares two
+        documents -- ``measure='hellinger'`` (default) by the Bhattacharyya coefficient ``s = sum_k
+        sqrt(p(k | q) p(k | w))`` with distance ``sqrt(max(0, 1 - s))``, ``measure='cosine'`` by the
+        cosine ``s`` of ``pi_k beta_kq`` and ``pi_k beta_kw`` with distance ``max(0, 1 - s)``.
+        Returns ``(ids, dist)``, B x top_n int32 and float64, nearest first, equal similarities by
+        smaller word id; with ``return_similarity=True`` the second array holds ``s``.  With
+        ``exclude_self`` (default) a query word is left out of its own list, by id: another word
+        with an equal column of lambda stays in, at distance 0.
+
+        ``topic_weights`` (pi) as for ``relevant_words``.  ``1 <= top_n <= min(num_words - 1, 100)``
+        (``num_words`` without ``exclude_self``), else RuntimeError; a measure that is no string is a
+        TypeError, an unknown one a ValueError; a word id that is no integer is a TypeError, one
+        outside the vocabulary a RuntimeError, as is a lambda with an entry <= 0 or not finite.  The
+        V x B x K product runs on the GPU's matrix cores against lambda where it lies; only the
+        lists come back.  A query's list does not depend on the other queries, ``s(q, w)`` and
+        ``s(w, q)`` are the same bits, and two calls agree bitwise.  lambda, alpha, eta, the counters
+        and the seeded stream stay as they are."""
+        ids = self._word_ids(words)
+        top_n = self._wordsim_top_n(top_n, exclude_self)
+        measure = _measure(measure)
+        pi = self._topic_weights(topic_weights)
+        B = ids.size
+        out = np.empty((B, top_n), dtype=np.int32)
+        sim = np.empty((B, top_n), dtype=np.float64)
+        if B:
+            handle = self._open_handle()
+            _ffi.check(_ffi.lib().trlda_model_similar_words(
+                handle, ids.ctypes.data, B, top_n, measure, None if pi is None else pi.ctypes.data,
+                1 if exclude_self else 0, out.ctypes.data, sim.ctypes.data))
+        return self._wordsim_result(out, sim, measure, return_similarity)
+
+    def words_near(self, proportions, top_n=10, measure="hellinger", topic_weights=None, return_similarity=False):
+        """The ``top_n`` words nearest points of the topic simplex: ``proportions`` is K x B or a
+        length-K vector of finite, positive values (each column is normalised) -- a document's
+        ``gamma``, a centroid of ``DocumentIndex.cluster``, a topic.  The measures, the result and
+        the errors are those of ``similar_words``; there is no self to leave out, so ``top_n`` may
+        reach ``min(num_words, 100)``.  Proportions that are not finite or not positive raise
+        RuntimeError."""
+        try:
+            g = np.array(proportions, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`proportions` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Proportions have wrong dimensionality.")
+        g = np.asfortranarray(g)
+        top_n = self._wordsim_top_n(top_n, False)
+        measure = _measure(measure)
+        pi = self._topic_weights(topic_weights)
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise RuntimeError("Proportions should be finite and positive.")
+        B = g.shape[1]
+        out = np.empty((B, top_n), dtype=np.int32)
+        sim = np.empty((B, top_n), dtype=np.float64)
+        if B:
+            handle = self._open_handle()
+            _ffi.check(_ffi.lib().trlda_model_similar_words_rows(
+                handle, g.ctypes.data, B, top_n, measure, None if pi is None else pi.ctypes.data,
+                out.ctypes.data, sim.ctypes.data))
+        return self._wordsim_result(out, sim, measure, return_similarity)
+
+    def word_topic_proportions(self, words, topic_weights=None):
+        """``p(k | w)`` of each of ``words`` (a word id or a sequence of B ids): K x B float64 in
+        Fortran order, each column summing to 1 -- the distributions ``similar_words`` compares.
+        ``topic_weights`` and the errors as there."""
+        ids = self._word_ids(words)
+        pi = self._topic_weights(topic_weights)
+        B = ids.size
+        out = np.empty((self._K, B), dtype=np.float64, order="F")
+        if B:
+            handle = self._open_handle()
+            _ffi.check(_ffi.lib().trlda_model_word_topic_proportions(
+                handle, ids.ctypes.data, B, None if pi is None else pi.ctypes.data, out.ctypes.data))
+        return out
 
     def _prevalence(self, weight_by_length, feed):
         """Runs ``feed(acc)`` and returns the normalised weights; ``acc()`` is the accumulator, made
