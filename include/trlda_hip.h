@@ -743,6 +743,41 @@ int trlda_docindex_silhouette(trlda_docindex *index, const int32_t *labels_host 
                               double *a_out /* may be NULL */, double *b_out /* may be NULL */,
                               int32_t *neighbour_out /* may be NULL */);
 
+/* The radius join of an indexed corpus (csrc/neighbors_kernels.h): for each scored row
+ * the indexed documents within distance `radius` of it, as a CSR list.  The M scored rows are the stored
+ * rows ids_host names (any order, repeats allowed; NULL with gamma_host NULL too: all N, row q is
+ * document q and M is ignored), or the rows of the M columns of gamma_host (K x M), formed as
+ * trlda_docindex_query_gamma forms them; not both.
+ *   s(i, j)       the dot of scored row i and stored row j, one chain of v_mfma_f64_16x16x4_f64 over
+ *                 ascending k as in trlda_docindex_silhouette: it depends on the two rows and K alone, and
+ *                 s(i, j) and s(j, i) are the same bits
+ *   d(i, j)       sqrt(fmax(1 - s, 0)) (hellinger) or fmax(1 - s, 0) (cosine), formed on the device
+ *   hit           d <= radius.  Where the scored rows are stored rows the pair (i, i) is left out by id, not
+ *                 by value; for gamma rows nothing is left out.
+ * Three steps on the device: the hits are counted per (scored row, slab of columns); an exclusive prefix
+ * over the counts in (row, slab) order gives every slab's place and indptr_out (int64, M + 1;
+ * indptr_out[M] is the total); the same products and the same predicate, from the same device function,
+ * then put every hit at a place that depends on the data alone.  Row q's hits are ids_out[indptr_out[q]
+ * ... indptr_out[q + 1] - 1] (int64) in ascending id, val_out (fp64, may be NULL) their d, or their s
+ * with want_similarity != 0.  The result does not depend on trlda_docindex_set_slab_rows (rounded up to
+ * a multiple of 64 columns here; 0: a default sized so that few scored rows still fill the device), on
+ * the rows scored beside a row or on how the index was filled; two calls agree bitwise.  No atomics;
+ * nothing of size M x N exists.  Any K >= 1: no E-step runs.
+ * The count and the prefix always run.  With ids_out NULL the call ends there (one product formed).  If
+ * indptr_out[M] > capacity nothing is written to ids_out / val_out and the call still returns TRLDA_OK:
+ * the caller compares the two and calls again.  Otherwise the first indptr_out[M] entries are written.
+ * TRLDA_ERR_ARG, before anything is waited for, copied or launched: a NULL index or indptr_out, an empty
+ * index, both ids_host and gamma_host, M < 1 with either, capacity < 0, val_out without ids_out;
+ * TRLDA_ERR_VALUE, with nothing changed: a radius that is not finite or is negative, an id outside
+ * [0, N), a gamma value that is not finite and positive.  Nothing is drawn; the index, lambda, alpha, the
+ * counters and the model's statistics are left alone; pending deferred statistics and stream lanes are
+ * settled first; the temporaries are the call's own.  Synchronises.  No reference counterpart. */
+int trlda_docindex_neighbors(trlda_docindex *index, double radius, const int64_t *ids_host /* M or NULL */,
+                             const double *gamma_host /* K x M or NULL */, int64_t M, int want_similarity,
+                             int64_t capacity, int64_t *indptr_out /* M + 1 */,
+                             int64_t *ids_out /* capacity, or NULL: count only */,
+                             double *val_out /* capacity, or NULL */);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

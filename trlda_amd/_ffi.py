@@ -194,6 +194,7 @@ _SIGNATURES = {
     "trlda_docindex_cluster": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int),
                                          C.POINTER(C.c_int)]),
     "trlda_docindex_silhouette": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, vp]),
+    "trlda_docindex_neighbors": (C.c_int, [vp, C.c_double, vp, vp, C.c_int64, C.c_int, C.c_int64, vp, vp, vp]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

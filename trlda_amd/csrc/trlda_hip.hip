@@ -60,6 +60,7 @@
 #include "topicdocs_kernels.h"
 #include "cluster_kernels.h"
 #include "silhouette_kernels.h"
+#include "neighbors_kernels.h"
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
 
@@ -6779,6 +6780,110 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
                                   : hipSuccess;
     hipError_t e5 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the radius join of an indexed corpus (csrc/neighbors_kernels.h) ----
+
+extern "C" {
+
+int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *ids_host, const double *gamma_host,
+                             int64_t M, int want_similarity, int64_t capacity, int64_t *indptr_out, int64_t *ids_out,
+                             double *val_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!x || !indptr_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / indptr");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (ids_host && gamma_host)
+        return fail(TRLDA_ERR_ARG, "the scored rows are either ids or a gamma, not both");
+    if ((ids_host || gamma_host) && M < 1)
+        return fail(TRLDA_ERR_ARG, "a list of ids or a gamma needs at least one document");
+    if (gamma_host && M > INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many gamma columns in one call");
+    if (capacity < 0)
+        return fail(TRLDA_ERR_ARG, "the capacity must not be negative");
+    if (val_out && !ids_out)
+        return fail(TRLDA_ERR_ARG, "values need ids");
+    const long long N = x->n;
+    const long long rows = ids_host || gamma_host ? (long long)M : N;
+    const long long blocks = (rows + trlda::kNeighborsRows - 1) / trlda::kNeighborsRows;
+    // the slab: the A/B switch rounded up to whole groups of 64 columns, else the default for this shape
+    long long slab = x->slab_rows > 0 ? ((long long)x->slab_rows + trlda::kNeighborsGroup - 1) /
+                                            trlda::kNeighborsGroup * trlda::kNeighborsGroup
+                                      : trlda::neighbors_default_slab(rows, N);
+    slab = std::min(slab, trlda::kNeighborsMaxSlab);
+    const long long nslab = (N + slab - 1) / slab;
+    if (blocks > INT_MAX || nslab > 65535)               // (grid dimensions x, y)
+        return fail(TRLDA_ERR_ARG, "too many rows or slabs: raise trlda_docindex_set_slab_rows");
+    if (!(radius >= 0.0) || !std::isfinite(radius))
+        return fail(TRLDA_ERR_VALUE, "the radius should be finite and not negative");
+    if (ids_host)
+        for (int64_t i = 0; i < M; ++i)
+            if (ids_host[i] < 0 || ids_host[i] >= N)
+                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
+    if (gamma_host)
+        if (int rc_val = docindex_check_gamma(gamma_host, (size_t)x->K * (size_t)M))
+            return rc_val;
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    const size_t cells = (size_t)rows * (size_t)nslab;
+    DevBuf<int> count;
+    DevBuf<long long> ids, off, indptr, hit_ids;
+    DevBuf<double> gstage, qrows, hit_val;
+    if ((rc = count.alloc(cells)) || (rc = off.alloc(cells)) || (rc = indptr.alloc((size_t)rows + 1)))
+        return rc;
+    if (ids_host && (rc = ids.alloc((size_t)M)))
+        return rc;
+    const size_t lds = trlda::neighbors_sweep_lds();
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::neighbors_count_kernel), lds)) ||
+        (rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::neighbors_fill_kernel), lds)))
+        return rc;
+    // (ids_host and gamma_host live until the synchronisation below)
+    if (ids_host)
+        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if (gamma_host && (rc = cluster_rows(x, gamma_host, (int)M, gstage, qrows)))
+        return rc;
+    const double *xrows = gamma_host ? qrows.get() : x->rows.get();
+    const long long *ids_dev = ids_host ? ids.get() : (const long long *)nullptr;
+    const int skip_self = gamma_host ? 0 : 1;
+    const dim3 grid((unsigned)blocks, (unsigned)nslab);
+    hipLaunchKernelGGL(trlda::neighbors_count_kernel, grid, dim3(trlda::kNeighborsThreads), lds, stream, x->Kp, rows, N,
+                       slab, x->measure, radius, skip_self, xrows, x->rows.get(), ids_dev, count.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::neighbors_scan_kernel, dim3(1), dim3(trlda::kNeighborsScanThreads), 0, stream, rows,
+                       nslab, count.get(), off.get(), indptr.get());
+    HIP_TRY(hipGetLastError());
+    {
+        hipError_t e1 = hipMemcpyAsync(indptr_out, indptr, ((size_t)rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                       stream);
+        hipError_t e2 = hipStreamSynchronize(stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+        HIP_TRY(hipGetLastError());
+    }
+    const int64_t total = indptr_out[rows];
+    // count only; or the caller's arrays are too small (it compares indptr_out[M] with its capacity)
+    if (!ids_out || total > capacity || total == 0)
+        return TRLDA_OK;
+    if ((rc = hit_ids.alloc((size_t)total)) || (val_out && (rc = hit_val.alloc((size_t)total))))
+        return rc;
+    hipLaunchKernelGGL(trlda::neighbors_fill_kernel, grid, dim3(trlda::kNeighborsThreads), lds, stream, x->Kp, rows, N,
+                       slab, x->measure, radius, skip_self, want_similarity ? 1 : 0, xrows, x->rows.get(), ids_dev,
+                       off.get(), (long long)total, hit_ids.get(), val_out ? hit_val.get() : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(ids_out, hit_ids, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = val_out ? hipMemcpyAsync(val_out, hit_val, (size_t)total * sizeof(double), hipMemcpyDeviceToHost,
+                                             stream)
+                            : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }

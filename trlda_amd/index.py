@@ -4,8 +4,10 @@ A device-resident table of the documents' topic proportions theta = gamma / sum(
 ranked search over it; the topic summaries of the indexed corpus -- per topic its most representative
 documents, and the covariance and correlations of theta (csrc/topicdocs_kernels.h, DESIGN.md 3.24);
 the indexed documents that best explain a query's words (csrc/querylik_kernels.h); and
-the document groups of the indexed corpus (csrc/cluster_kernels.h) and their
-silhouettes (csrc/silhouette_kernels.h).
+the document groups of the indexed corpus (csrc/cluster_kernels.h), their
+silhouettes (csrc/silhouette_kernels.h), and the radius join -- the documents within
+a distance of each document -- with the density-based groups built on it (csrc/neighbors_kernels.h,
+DESIGN.md 3.29).
 No counterpart in the reference package.
 """
 import ctypes as C
@@ -450,6 +452,119 @@ class DocumentIndex(object):
             raise ValueError("`candidates` should hold at least one number of clusters.")
         return min(scores, key=lambda c: (-scores[c], c)), scores
 
+    # -- the radius join (csrc/neighbors_kernels.h) ---------------------------------
+    def _neighbors(self, radius, rows, g, want_similarity, capacity, indptr, ids, val):
+        M = 0 if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+        _ffi.check(_ffi.lib().trlda_docindex_neighbors(self._live(), radius,
+                                                       None if rows is None else rows.ctypes.data,
+                                                       None if g is None else g.ctypes.data, M,
+                                                       1 if want_similarity else 0, capacity, indptr.ctypes.data,
+                                                       None if ids is None else ids.ctypes.data,
+                                                       None if val is None else val.ctypes.data))
+
+    def neighbors_within(self, radius, ids=None, gamma=None, return_similarity=False, count_only=False,
+                         max_pairs=1 << 26):
+        """The indexed documents within distance ``radius`` of each scored document, in the index's own
+        distance ``d``: ``sqrt(max(0, 1 - s))`` (hellinger) or ``max(0, 1 - s)`` (cosine); a pair is a
+        hit iff ``d <= radius``.  ``ids=None, gamma=None`` scores every indexed document; ``ids`` is an
+        integer array of row ids (any order, repeats allowed; out of range: RuntimeError); ``gamma``
+        (K x M) scores documents given by their variational parameters, as ``query_gamma`` takes them
+        (no E-step).  An indexed document is left out of its own list by id, so two documents with
+        equal rows find each other; for ``gamma`` nothing is left out, so a stored document's own
+        gamma finds that document too.
+
+        Returns ``(indptr, ids, dist)`` in CSR form: ``indptr`` int64 of length M + 1, ``ids`` int64 and
+        ``dist`` float64 of length ``indptr[-1]``; the hits of scored document q are
+        ``ids[indptr[q]:indptr[q + 1]]``, in ascending id.  With ``return_similarity=True`` the
+        similarity s stands in place of the distance; with ``count_only=True`` only ``indptr`` is
+        returned and one pass over the pairs is made instead of two.  More than ``max_pairs`` hits in
+        all is a RuntimeError that names the total (nothing of that size is allocated first).
+
+        ``s(i, j)`` and ``s(j, i)`` are the same bits, so the hit graph of the whole index is
+        symmetric.  The result does not depend on ``set_slab_rows``, on the documents scored beside a
+        document or on how the index was filled, and two calls agree bitwise.  Nothing is drawn.
+
+        ``radius=0`` finds a duplicate only where the two rows' own dot rounds to at least 1, which a
+        unit-length row in floating point need not give: look for duplicates with a small positive
+        radius (1e-6 is far above the rounding of a distance at any K)."""
+        handle = self._live()
+        radius = float(radius)
+        if not (radius >= 0.0 and math.isfinite(radius)):
+            raise ValueError("`radius` should be finite and not negative.")
+        if ids is not None and gamma is not None:
+            raise ValueError("Give `ids` or `gamma`, not both.")
+        max_pairs = operator.index(max_pairs)
+        if max_pairs < 1:
+            raise ValueError("`max_pairs` should be positive.")
+        N = int(_ffi.lib().trlda_docindex_size(handle))
+        if N < 1:
+            raise RuntimeError("The index is empty.")
+        rows = _silhouette_ids(ids, N)
+        g = None if gamma is None else self._gamma(gamma)
+        if g is not None and g.shape[1] < 1:
+            raise RuntimeError("`gamma` should hold at least one document.")
+        M = N if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+        indptr = np.empty(M + 1, dtype=np.int64)
+        if count_only:
+            self._neighbors(radius, rows, g, False, 0, indptr, None, None)
+            return indptr
+        capacity = min(max_pairs, max(16 * M, 1 << 20))
+        while True:
+            hit = np.empty(capacity, dtype=np.int64)
+            val = np.empty(capacity, dtype=np.float64)
+            self._neighbors(radius, rows, g, return_similarity, capacity, indptr, hit, val)
+            total = int(indptr[M])
+            if total <= capacity:
+                return indptr, hit[:total].copy(), val[:total].copy()
+            if total > max_pairs:
+                raise RuntimeError("%d pairs lie within the radius, more than `max_pairs` (%d)." % (total, max_pairs))
+            capacity = total                                         # (the second call: the exact size)
+
+    def dbscan(self, radius, min_samples=5, max_pairs=1 << 26, return_core=False):
+        """Density-based groups of the indexed documents (DBSCAN; Ester et al. 1996) under
+        ``neighbors_within(radius)``: no number of clusters is named, and outliers are.  A document is
+        a *core* iff its hits plus itself number at least ``min_samples``.  The clusters are the
+        connected components of the core documents under the hit graph, numbered from 0 by ascending
+        smallest core id.  A document that is no core but has a core among its hits (a border
+        document) takes the cluster of its nearest core hit, in the order (distance ascending, id
+        ascending).  Every other document is noise, labelled -1.
+
+        Returns the labels, int32 of length ``len(index)``; with ``return_core=True`` also the boolean
+        array of the core documents.  The cores come from one ``count_only`` pass; the hits are then
+        read in chunks of consecutive ids of at most ``max_pairs`` pairs each (a single document with
+        more hits than that is a RuntimeError), and the labels are the same bits whatever ``max_pairs``
+        is.  The rest is host arithmetic.  ``silhouette`` takes these labels once noise is given a
+        label of its own, for instance ``np.where(labels < 0, labels.max() + 1, labels)``."""
+        self._live()
+        min_samples = operator.index(min_samples)
+        if min_samples < 1:
+            raise ValueError("`min_samples` should be positive.")
+        max_pairs = operator.index(max_pairs)
+        if max_pairs < 1:
+            raise ValueError("`max_pairs` should be positive.")
+        counts = np.diff(self.neighbors_within(radius, count_only=True))
+        N = counts.shape[0]
+        core = counts + 1 >= min_samples
+        parent = np.arange(N, dtype=np.int64)
+        nearest = np.full(N, -1, dtype=np.int64)             # a border document's nearest core hit
+        before = np.concatenate(([0], np.cumsum(counts)))   # the pairs of the documents before each id
+        first = 0
+        while first < N:
+            # the longest run of consecutive ids from `first` that holds at most max_pairs pairs
+            last = int(np.searchsorted(before, before[first] + max_pairs, side="right")) - 1
+            last = max(last, first + 1)                      # (one document with more: the call raises)
+            if before[last] > before[first]:
+                scored = np.arange(first, last, dtype=np.int64)
+                indptr, hit, dist = self.neighbors_within(radius, ids=scored, max_pairs=max_pairs)
+                rows = np.repeat(scored, np.diff(indptr))
+                to_core = core[hit]
+                link = to_core & core[rows]
+                _union(parent, rows[link], hit[link])
+                border = to_core & ~core[rows]
+                _nearest(nearest, rows[border], hit[border], dist[border])
+            first = last
+        return _dbscan_labels(parent, core, nearest, return_core)
+
 
 def _silhouette_labels(labels, N):
     """(labels as contiguous int32, C) of ``silhouette``'s labels for an index of N documents, or the
@@ -481,6 +596,47 @@ def _silhouette_ids(ids, N):
     if int(rows.min()) < 0 or int(rows.max()) >= N:
         raise RuntimeError("`ids` should be ids of indexed documents, between 0 and %d." % (N - 1))
     return np.ascontiguousarray(rows, dtype=np.int64)
+
+
+def _roots(parent):
+    """Union-find: every entry of ``parent`` (in place) becomes the root of its tree."""
+    while True:
+        up = parent[parent]
+        if np.array_equal(up, parent):
+            return parent
+        parent[:] = up
+
+
+def _union(parent, a, b):
+    """Union-find over the edges (a[i], b[i]), all at once: the larger of two roots is hung under the
+    smaller until no edge joins two trees, so a tree's root is its smallest member."""
+    while len(a):
+        ra, rb = _roots(parent)[a], parent[b]
+        apart = ra != rb
+        a, b = a[apart], b[apart]
+        np.minimum.at(parent, np.maximum(ra, rb)[apart], np.minimum(ra, rb)[apart])
+
+
+def _nearest(nearest, rows, hit, dist):
+    """Per document of ``rows`` its first hit in the order (distance ascending, id ascending), into
+    ``nearest``; the three arrays hold one entry per (document, hit) pair."""
+    if not len(rows):
+        return
+    order = np.lexsort((hit, dist, rows))
+    rows, hit = rows[order], hit[order]
+    head = np.concatenate(([True], rows[1:] != rows[:-1]))
+    nearest[rows[head]] = hit[head]
+
+
+def _dbscan_labels(parent, core, nearest, return_core=False):
+    """The closing arithmetic of ``dbscan``: the cores' trees numbered by ascending root (a tree's
+    smallest member), a border document under its nearest core hit, noise -1."""
+    root = _roots(parent)
+    labels = np.full(len(core), -1, dtype=np.int32)
+    labels[core] = np.unique(root[core], return_inverse=True)[1].astype(np.int32)
+    border = np.flatnonzero(nearest >= 0)
+    labels[border] = labels[nearest[border]]
+    return (labels, core) if return_core else labels
 
 
 def _correlation(scatter):
