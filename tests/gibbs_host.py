@@ -101,9 +101,30 @@ def kpl_of(K):
     return kpl
 
 
-def sweep_draw(e_pad, cnt_pad, u, kpl):
+def _tally(stats, name):
+    if stats is not None:
+        stats[name] = stats.get(name, 0) + 1
+
+
+def sweep_draw(e_pad, cnt_pad, u, kpl, stats=None):
     """One histogram draw in the kernel's order (e_pad, cnt_pad: 64 * kpl, topics >= K zero).
-    Returns (topic, ok)."""
+    Returns (topic, ok).  `stats` (a dict) counts the branches taken: 'draws', 'last_in_lane' and
+    'last_overall' (the two fall-backs to the last topic with p > 0), 'zero_lane_below' (a lane
+    whose weights are all 0 below the chosen lane) and 'zero_weight_pick' (the chosen topic's weight
+    is not > 0: never, whatever the inputs)."""
+    z, ok = _sweep_draw(e_pad, cnt_pad, u, kpl, stats)
+    if ok and stats is not None:
+        p = e_pad * cnt_pad
+        _tally(stats, "draws")
+        if not p[z] > 0.0:
+            _tally(stats, "zero_weight_pick")
+        live = (p.reshape(WAVE, kpl)[:z // kpl] > 0.0).any(axis=1)
+        if live.any() and not live[int(np.argmax(live)):].all():
+            _tally(stats, "zero_lane_below")               # between a live lane and the chosen one
+    return z, ok
+
+
+def _sweep_draw(e_pad, cnt_pad, u, kpl, stats):
     p = e_pad * cnt_pad
     q = np.cumsum(p.reshape(WAVE, kpl), axis=1)           # lane-local sequential prefix
     x = q[:, -1].copy()
@@ -128,14 +149,17 @@ def sweep_draw(e_pad, cnt_pad, u, kpl):
             return L * kpl + int(inl[0]), True
         nz = np.nonzero(pr[L] > 0.0)[0]
         if nz.size:
+            _tally(stats, "last_in_lane")
             return L * kpl + int(nz[-1]), True
     nz = np.nonzero(p > 0.0)[0]
+    _tally(stats, "last_overall")
     return int(nz[-1]), True
 
 
-def gibbs(e, alpha, indptr, ids, cnts, theta0, num_samples, burn_in, key, docs=None):
+def gibbs(e, alpha, indptr, ids, cnts, theta0, num_samples, burn_in, key, docs=None, stats=None):
     """The whole call: returns (theta K x B, counts K x V int64 summed over the samples,
-    final topic counts K x B int64).  `docs`: only these documents (others left zero)."""
+    final topic counts K x B int64).  `docs`: only these documents (others left zero).  `stats`: a
+    dict that counts the branches of the sweeps' draws (sweep_draw)."""
     e = np.asarray(e, dtype=np.float64)
     alpha = np.asarray(alpha, dtype=np.float64)
     K, V = e.shape
@@ -195,7 +219,7 @@ def gibbs(e, alpha, indptr, ids, cnts, theta0, num_samples, burn_in, key, docs=N
                 e_pad[:K] = e[:, wid]
                 for _ in range(c):
                     cnt[z[ti]] -= 1.0
-                    zz, ok = sweep_draw(e_pad, cnt, us[ti], kpl)
+                    zz, ok = sweep_draw(e_pad, cnt, us[ti], kpl, stats)
                     if not ok:
                         raise RuntimeError("Something went wrong while sampling from histogram.")
                     cnt[zz] += 1.0

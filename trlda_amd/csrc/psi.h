@@ -218,8 +218,13 @@ __device__ __forceinline__ double rcp_pair(double a)
 // (profiles/r04_scoef_ab.txt).
 // ANY: the argument may be positive, infinite or NaN (exp(psi(x) - c) with a row sum's psi as c):
 // clamped at both ends by selects -- a NaN stays one, +-inf come out as inf / 0 through v_ldexp_f64
+// Returns scale * exp(a), the factor multiplied into the polynomial BEFORE the final v_ldexp_f64:
+// in the normal range that is the same bits as scale * ldexp(p, n) (the power of two is exact
+// either way), but a result below 2^-1022 is rounded onto the subnormal grid once -- the product
+// after the ldexp multiplied the half unit of that rounding by scale, 10 for exp(psi(x)) of a small
+// x: 5 units of 2^-1074, 1.5e-7 relative at 1e-316 (tests/test_gpu_trained_inputs.py, test_the_table).
 template <bool SC = false, bool ANY = false>
-__device__ __forceinline__ double exp_nonpos(double a)
+__device__ __forceinline__ double exp_nonpos(double a, double scale)
 {
     if constexpr (ANY) {
         a = a < -800.0 ? -800.0 : a;
@@ -269,7 +274,7 @@ __device__ __forceinline__ double exp_nonpos(double a)
     p = fma(r, p, 1.0);
     p = fma(r, p, 1.0);
 #endif
-    return ldexp(p, (int)n);
+    return ldexp(scale * p, (int)n);
 }
 
 // the same polynomial by Horner's rule with three-address steps, coefficients from scalar registers:
@@ -344,7 +349,7 @@ __device__ __forceinline__ double exp_psi_regular(double x, double c)
     if constexpr (ZERO_C) {
 #ifndef TRLDA_LIBRARY_EXP
         const double yh = z * psi_series_horner(z);
-        return s * exp_nonpos<SC>(-((fma(0.5, r, yh)) + w));     // psi(x) < log(x + 10): the argument is <= 0
+        return exp_nonpos<SC>(-((fma(0.5, r, yh)) + w), s);      // psi(x) < log(x + 10): the argument is <= 0
 #endif
     }
 #ifdef TRLDA_GENERAL_LIBRARY_EXP
@@ -352,7 +357,7 @@ __device__ __forceinline__ double exp_psi_regular(double x, double c)
     return s * exp(-((fma(0.5, r, y)) + w) - c);
 #else
     const double y = z * psi_series_horner(z);
-    return s * exp_nonpos<SC, true>(-((fma(0.5, r, y)) + w) - c);
+    return exp_nonpos<SC, true>(-((fma(0.5, r, y)) + w) - c, s);
 #endif
 }
 
