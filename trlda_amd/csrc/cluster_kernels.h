@@ -7,9 +7,8 @@
 // product, and the centroid that minimises the summed distance of its members is
 // (sum of members) / |sum of members|.
 //
-// Assignment.  s(n, c) = sum_k x_nk m_ck, formed by v_mfma_f64_16x16x4_f64 as docindex_query_kernel
-// forms its similarities: one chain of Kp / 4 instructions over k = 0, 4, 8, ..., whatever tile, slab
-// or workgroup the pair lies in; s depends on the two rows and K alone.  label(n) is the first c in
+// Assignment.  s(n, c) = sum_k x_nk m_ck, the staged tile product of tile_product.h: one chain of
+// Kp / 4 MFMAs per pair, so s depends on the two rows and K alone.  label(n) is the first c in
 // the total order (s descending, c ascending): every lane keeps the running best of its D elements in
 // registers and the 16 lanes that share a document row settle it once, at the end.  Nothing of size
 // N x C exists.
@@ -42,7 +41,7 @@ constexpr int kClusterMaxClusters = TRLDA_CLUSTER_MAX_CLUSTERS;
 // LDS of cluster_assign_kernel: the documents' chunk and the centroids' chunk
 constexpr size_t cluster_assign_lds()
 {
-    return (size_t)(64 * kClusterDocTiles + kClusterGroup) * kDocIndexStride * sizeof(double);
+    return tile_operands_lds(64 * kClusterDocTiles);
 }
 
 // blocks of the counting sort
@@ -52,12 +51,9 @@ inline long long cluster_sort_blocks(long long N) { return (N + kClusterSortRows
 inline long long cluster_max_chunks(long long N, int C) { return N / kClusterChunkRows + C; }
 
 // Grid (slab of slab_rows document rows), 4 waves.  The slab is taken 128 rows at a time: wave w owns
-// the 32 rows w * 32 ... of a pass and multiplies them with every centroid row, 64 at a time.  Both
-// operands are staged in LDS in k chunks of 32 taken in ascending k, as docindex_query_kernel stages
-// its own.  Rows past N and centroid rows past C are read as row N - 1 / C - 1 (the product is formed)
-// and kept out of the selection.
-//   A operand: lane l holds X[l & 15][k + (l >> 4)]; B operand: M[l & 15][k + (l >> 4)];
-//   D: register r of lane l is s(document (l >> 4) + 4 r, centroid l & 15).
+// the 32 rows w * 32 ... of a pass and multiplies them with every centroid row, 64 at a time: the
+// product and its layout are those of tile_product.h, X the document rows and Y the centroid rows.
+// Rows past N and centroid rows past C are read as row N - 1 / C - 1 and kept out of the selection.
 // A lane meets its centroids in ascending order, so its running best is the first in the total order
 // among them; the 16 lanes (l & 15) that share a document row compare theirs at the end of the pass.
 // label / sim: per document; changed[slab]: the slab's labels that differ from prev (0 without prev).
@@ -90,47 +86,18 @@ __global__ __launch_bounds__(kClusterThreads) void cluster_assign_kernel(
             }
 
         for (int g0 = 0; g0 < C; g0 += kClusterGroup) {
-            docindex_f64x4 acc[SW][4];
-#pragma unroll
-            for (int t = 0; t < SW; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+            docindex_f64x4 acc[SW][4] = {};
 
             for (int k0 = 0; k0 < Kp; k0 += kDocIndexChunk) {
                 const int cl = min(kDocIndexChunk, Kp - k0);    // a multiple of 4
                 __syncthreads();                                // the previous chunk has been read
-                for (int i = tid; i < QT * (kDocIndexChunk / 2); i += kClusterThreads) {
-                    const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                    if (c < cl) {
-                        const long long rr = min(slab0 + q0 + row, N - 1);
-                        *reinterpret_cast<double2 *>(x_lds + row * S + c) =
-                            *reinterpret_cast<const double2 *>(docs + (size_t)rr * Kp + k0 + c);
-                    }
-                }
-                for (int i = tid; i < kClusterGroup * (kDocIndexChunk / 2); i += kClusterThreads) {
-                    const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                    if (c < cl) {
-                        const int cr = min(g0 + row, C - 1);
-                        *reinterpret_cast<double2 *>(m_lds + row * S + c) =
-                            *reinterpret_cast<const double2 *>(crows + (size_t)cr * Kp + k0 + c);
-                    }
-                }
+                tile_stage<QT, kClusterThreads>(x_lds, docs, Kp, k0, cl, tid,
+                                                [&](int row) { return min(slab0 + q0 + row, N - 1); });
+                tile_stage<kClusterGroup, kClusterThreads>(m_lds, crows, Kp, k0, cl, tid,
+                                                           [&](int row) { return min(g0 + row, C - 1); });
                 __syncthreads();
-                for (int kk = 0; kk < cl; kk += 4) {
-                    double a[SW], b[4];
-#pragma unroll
-                    for (int t = 0; t < SW; ++t)
-                        a[t] = x_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        b[j] = m_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                    for (int t = 0; t < SW; ++t)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[j], acc[t][j], 0, 0, 0);
-                }
+                for (int kk = 0; kk < cl; kk += 4)
+                    tile_step<SW>(acc, x_lds, m_lds, kk, wid, m, kq);
             }
 
             // the lane's own centroids of this group, in ascending order

@@ -10,10 +10,8 @@
 // t_k^2 is rounded once before it is added (no contraction).  A row therefore depends on its gamma
 // column and K alone.  Rows are stored row-major with Kp = ceil(K / 4) * 4 doubles, the tail zero.
 //
-// Similarities.  s(q, d) = sum_k r_qk r_dk, formed by v_mfma_f64_16x16x4_f64: every element of every
-// 16 x 16 tile is the same chain of Kp / 4 instructions over k = 0, 4, 8, ..., each adding four
-// products to the running value, whatever tile, slab or workgroup the pair lies in.  The zero tail
-// adds +0 to a positive sum.  s depends on the two rows and K alone.
+// Similarities.  s(q, d) = sum_k r_qk r_dk, the staged tile product of tile_product.h: one chain of
+// Kp / 4 MFMAs per pair, so s depends on the two rows and K alone.
 //
 // Ranking.  The total order (s descending, id ascending).  docindex_query_kernel keeps, per query row
 // and slab of index rows, the best top_n pairs in LDS; docindex_merge_kernel ranks the slabs' lists.
@@ -23,28 +21,21 @@
 
 #include <climits>
 
-#include "estep_kernels.h"
+#include "tile_product.h"
 
 namespace trlda {
 
 constexpr int kDocIndexThreads = 256;      // 4 waves
 constexpr int kDocIndexMaxTop = 100;       // top_n <= min(N, 100): the cap of trlda_model_top_words
 constexpr int kDocIndexGroup = 64;         // index rows a workgroup multiplies at a time: 4 tiles of 16
-constexpr int kDocIndexChunk = 32;         // the k chunk staged in LDS
-// LDS row stride in doubles: 2 mod 4, so the 16 rows x 2 columns that half a wave reads at once fall
-// into 32 different 8-byte banks (row * 34 + c mod 32 = 2 row + c, c = 0, 1)
-constexpr int kDocIndexStride = kDocIndexChunk + 2;
 constexpr int kDocIndexSlabRows = 2048;    // default slab: index rows per workgroup
 constexpr int kDocIndexWideMaxTop = 32;    // up to here a workgroup takes 128 query rows, beyond 64
 constexpr int kDocIndexMeasures = 2;       // 0: hellinger, 1: cosine
 
-typedef double docindex_f64x4 __attribute__((ext_vector_type(4)));
-
 // LDS of docindex_query_kernel<SW>: the query chunk, the index chunk, the lists (fp64 s, int32 row)
 constexpr size_t docindex_query_lds(int sw, int top_n)
 {
-    return (size_t)(64 * sw + kDocIndexGroup) * kDocIndexStride * sizeof(double) +
-           (size_t)64 * sw * top_n * (sizeof(double) + sizeof(int));
+    return tile_operands_lds(64 * sw) + (size_t)64 * sw * top_n * (sizeof(double) + sizeof(int));
 }
 
 // gamma (K x B column-major) -> rows (B x Kp row-major).  One wave per document.
@@ -80,63 +71,12 @@ __global__ __launch_bounds__(kDocIndexThreads) void docindex_rows_kernel(int K, 
         r[k] = 0.0;
 }
 
-// is (v, i) before (w, j) in the order (s descending, id ascending)?
-template <typename I>
-__device__ __forceinline__ bool docindex_before(double v, I i, double w, I j)
-{
-    return v > w || (v == w && i < j);
-}
-
-// Puts (cv, cr) into the wave's own sorted list of n entries (n <= 128; the last entry falls out).
-// Every lane calls it with the same arguments; lane l looks after positions l and l + 64.  All reads
-// come before all writes: the fences keep the compiler from moving either across.
-__device__ __forceinline__ void docindex_insert(double *s, int *id, int n, double cv, int cr, int lane)
-{
-    const double ninf = -__builtin_huge_val();
-    const int p0 = lane, p1 = lane + kWave;
-    double e0 = ninf, e1 = ninf, f0 = ninf, f1 = ninf;      // the entries at p and at p - 1
-    int i0 = INT_MAX, i1 = INT_MAX, j0 = INT_MAX, j1 = INT_MAX;
-    if (p0 < n) {
-        e0 = s[p0];
-        i0 = id[p0];
-        if (p0 > 0) {
-            f0 = s[p0 - 1];
-            j0 = id[p0 - 1];
-        }
-    }
-    if (p1 < n) {
-        e1 = s[p1];
-        i1 = id[p1];
-        f1 = s[p1 - 1];
-        j1 = id[p1 - 1];
-    }
-    // (the list is sorted: the entries before the candidate are a prefix)
-    const int pos = __popcll(__ballot(p0 < n && docindex_before(e0, i0, cv, cr))) +
-                    __popcll(__ballot(p1 < n && docindex_before(e1, i1, cv, cr)));
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (p0 < n && p0 >= pos) {
-        s[p0] = p0 == pos ? cv : f0;
-        id[p0] = p0 == pos ? cr : j0;
-    }
-    if (p1 < n && p1 >= pos) {
-        s[p1] = p1 == pos ? cv : f1;
-        id[p1] = p1 == pos ? cr : j1;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Grid (tile of 64 SW query rows, slab of slab_rows index rows), 4 waves.  Wave w owns the 16 SW
-// query rows w * 16 SW ... of the tile -- their products and their lists, so no list is shared
-// between waves -- and multiplies them with every index row of the slab, 64 at a time.  Both
-// operands are staged in LDS in k chunks of 32; the chunks are taken in ascending k for every K, so
-// each s is one chain of MFMAs in one order.  Rows past N and query rows past B are read as row
-// N - 1 / B - 1 (the product is formed) and kept out of the selection.
-//   A operand: lane l holds Q[l & 15][k + (l >> 4)]; B operand: R[l & 15][k + (l >> 4)];
-//   D: register r of lane l is s(query (l >> 4) + 4 r, index row l & 15).
-// A list holds top_n (s, row in slab) pairs, sorted, filled with (-inf, INT_MAX) at the start: the
-// last entry is the threshold a candidate must be before, and most are not.
+// query rows w * 16 SW ... of the tile -- their products and their lists -- and multiplies them with
+// every index row of the slab, 64 at a time: the product, its layout and the selection are those of
+// tile_product.h, X the query rows and Y the index rows.  Rows past N and query rows past B are read
+// as row N - 1 / B - 1 and kept out of the selection.
+// A list holds top_n (s, row in slab) pairs.
 // out_s / out_id: (slabs x B x top_n), the pad written as (-inf, int64 max).
 template <int SW>
 __global__ __launch_bounds__(kDocIndexThreads) void docindex_query_kernel(
@@ -154,56 +94,23 @@ __global__ __launch_bounds__(kDocIndexThreads) void docindex_query_kernel(
     const int q0 = blockIdx.x * QT;
     const long long slab0 = (long long)blockIdx.y * slab_rows;
     const int nrows = (int)min((long long)slab_rows, N - slab0);
-    const double ninf = -__builtin_huge_val();
 
-    for (int i = tid; i < QT * top_n; i += kDocIndexThreads) {
-        ls[i] = ninf;
-        li[i] = INT_MAX;
-    }
+    select_init(ls, li, QT * top_n, tid, kDocIndexThreads);
     // (the first barrier of the loop below stands between this and the lists' first use)
 
     for (int g0 = 0; g0 < nrows; g0 += kDocIndexGroup) {
-        docindex_f64x4 acc[SW][4];
-#pragma unroll
-        for (int t = 0; t < SW; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+        docindex_f64x4 acc[SW][4] = {};
 
         for (int k0 = 0; k0 < Kp; k0 += kDocIndexChunk) {
             const int cl = min(kDocIndexChunk, Kp - k0);    // a multiple of 4
             __syncthreads();                                // the previous chunk has been read
-            for (int i = tid; i < QT * (kDocIndexChunk / 2); i += kDocIndexThreads) {
-                const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                if (c < cl) {
-                    const int qr = min(q0 + row, B - 1);
-                    *reinterpret_cast<double2 *>(q_lds + row * S + c) =
-                        *reinterpret_cast<const double2 *>(qrows + (size_t)qr * Kp + k0 + c);
-                }
-            }
-            for (int i = tid; i < kDocIndexGroup * (kDocIndexChunk / 2); i += kDocIndexThreads) {
-                const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                if (c < cl) {
-                    const long long rr = min(slab0 + g0 + row, N - 1);
-                    *reinterpret_cast<double2 *>(r_lds + row * S + c) =
-                        *reinterpret_cast<const double2 *>(table + (size_t)rr * Kp + k0 + c);
-                }
-            }
+            tile_stage<QT, kDocIndexThreads>(q_lds, qrows, Kp, k0, cl, tid,
+                                             [&](int row) { return min(q0 + row, B - 1); });
+            tile_stage<kDocIndexGroup, kDocIndexThreads>(r_lds, table, Kp, k0, cl, tid,
+                                                         [&](int row) { return min(slab0 + g0 + row, N - 1); });
             __syncthreads();
-            for (int kk = 0; kk < cl; kk += 4) {
-                double a[SW], b[4];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-                    a[t] = q_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    b[j] = r_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[j], acc[t][j], 0, 0, 0);
-            }
+            for (int kk = 0; kk < cl; kk += 4)
+                tile_step<SW>(acc, q_lds, r_lds, kk, wid, m, kq);
         }
 
         // the selection: the wave's own query rows against the 64 index rows of this pass
@@ -219,33 +126,18 @@ __global__ __launch_bounds__(kDocIndexThreads) void docindex_query_kernel(
                     const double tv = ls[ql * top_n + top_n - 1];
                     const int ti = li[ql * top_n + top_n - 1];
                     const bool pass = rl < nrows && q0 + ql < B && docindex_before(v, rl, tv, ti);
-                    unsigned long long mask = __ballot(pass);
-                    while (mask) {                                      // (uniform)
-                        const int L = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
-                        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
-                        const int cq = wid * WQ + t * 16 + (L >> 4) + 4 * r;
-                        docindex_insert(ls + cq * top_n, li + cq * top_n, top_n, __hiloint2double(hi, lo),
-                                        g0 + j * 16 + (L & 15), lane);
-                    }
+                    select_offer(pass, v, ls, li, top_n, lane,
+                                 [&](int L) { return wid * WQ + t * 16 + (L >> 4) + 4 * r; },
+                                 [&](int L) { return g0 + j * 16 + (L & 15); });
                 }
             }
         }
     }
 
-    // the wave's lists, each as one run of top_n values
-    for (int w = 0; w < WQ; ++w) {
-        const int ql = wid * WQ + w;
-        if (q0 + ql >= B)
-            break;
-        const size_t o = ((size_t)blockIdx.y * B + (q0 + ql)) * top_n;
-        for (int p = lane; p < top_n; p += kWave) {
-            const int id = li[ql * top_n + p];
-            out_s[o + p] = ls[ql * top_n + p];
-            out_id[o + p] = id == INT_MAX ? LLONG_MAX : slab0 + id;
-        }
-    }
+    // the wave's lists of query rows below B
+    const size_t o = ((size_t)blockIdx.y * B + q0 + wid * WQ) * top_n;
+    select_write<WQ>(ls + wid * WQ * top_n, li + wid * WQ * top_n, top_n, B - q0 - wid * WQ, out_s + o, out_id + o,
+                     slab0, (long long)LLONG_MAX, lane);
 }
 
 // One workgroup per query row ranks the slabs' lists: top_n passes, each taking the first candidate

@@ -2,10 +2,10 @@
 // documents within distance `radius` of it, as a CSR list (trlda_docindex_neighbors).
 // No reference counterpart.
 //
-//   s(i, j)     the dot of the scored row i and the stored row j, formed by v_mfma_f64_16x16x4_f64 as
-//               silhouette_pairs_kernel forms it: one chain of Kp / 4 instructions over k = 0, 4, 8, ...
-//               The chain depends on the two rows and K alone, so s(i, j) and s(j, i) are the same bits.
-//   d(i, j)     sqrt(fmax(1 - s, 0)) (hellinger) or fmax(1 - s, 0) (cosine)
+//   s(i, j)     the dot of the scored row i and the stored row j by the staged tile product of
+//               tile_product.h: one chain of Kp / 4 MFMAs that depends on the two rows and K alone, so
+//               s(i, j) and s(j, i) are the same bits.
+//   d(i, j)     docindex_distance(s): sqrt(fmax(1 - s, 0)) (hellinger) or fmax(1 - s, 0) (cosine)
 //   hit         d <= radius; the pair (i, i) is left out by id where the scored rows are stored rows
 //               (nothing is left out for rows made from a gamma); columns past N are left out by position
 //
@@ -32,8 +32,7 @@ constexpr long long kNeighborsMaxSlab = 1LL << 30;      // (a slab's hits of one
 // LDS of the two sweeps: the scored rows' chunk, the columns' chunk, and the scored rows' source rows
 constexpr size_t neighbors_sweep_lds()
 {
-    return (size_t)(kNeighborsRows + kNeighborsGroup) * kDocIndexStride * sizeof(double) +
-           (size_t)kNeighborsRows * sizeof(long long);
+    return tile_operands_lds(kNeighborsRows) + (size_t)kNeighborsRows * sizeof(long long);
 }
 
 // The default slab for M scored rows against N columns: about 1024 workgroups (four per CU) where N
@@ -48,12 +47,10 @@ inline long long neighbors_default_slab(long long M, long long N)
 
 // Grid (block of 128 scored rows, slab of `slab` columns), 4 waves: wave w owns the rows 32 w ...
 // 32 w + 31 of the block as two MFMA tiles and multiplies them with the slab's columns, 64 at a time in
-// ascending order.  Both operands are staged in LDS in k chunks of 32 taken in ascending k, as
-// silhouette_pairs_kernel stages its own; the scored rows are read from xrows through ids (NULL: scored
-// row q is row q of xrows), the columns from docs by position (a column past N reads row N - 1: the
-// product is formed and left out).  Rows past M are computed as row M - 1 and left out.
-//   A operand: lane l holds X[l & 15][k + (l >> 4)]; B operand: Y[l & 15][k + (l >> 4)];
-//   D: register r of lane l is s(row (l >> 4) + 4 r, column l & 15).
+// ascending order: the product and its layout are those of tile_product.h.  The scored rows (X) are
+// read from xrows through ids (NULL: scored row q is row q of xrows), the columns (Y) from docs by
+// position (a column past N reads row N - 1: the product is formed and left out).  Rows past M are
+// computed as row M - 1 and left out.
 // The 16 lanes 16 (l >> 4) ... 16 (l >> 4) + 15 hold one row's 16 columns of a tile in ascending order:
 // the row's hits of the tile are the 16-bit segment (l >> 4) of the wave's ballot, their number its
 // popcount, and the rank of lane l's hit the popcount of the segment's bits below l & 15.
@@ -105,46 +102,19 @@ __device__ __forceinline__ void neighbors_sweep(int Kp, long long M, long long N
         }
 
     for (long long g0 = c0; g0 < c1; g0 += G) {
-        docindex_f64x4 acc[SW][4];
-#pragma unroll
-        for (int t = 0; t < SW; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+        docindex_f64x4 acc[SW][4] = {};
 
         for (int k0 = 0; k0 < Kp; k0 += kDocIndexChunk) {
             const int cl = min(kDocIndexChunk, Kp - k0);    // a multiple of 4
             __syncthreads();                                // the previous chunk has been read
             if (!one_chunk || g0 == c0)
-                for (int i = tid; i < QT * (kDocIndexChunk / 2); i += kNeighborsThreads) {
-                    const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                    if (c < cl)
-                        *reinterpret_cast<double2 *>(x_lds + row * S + c) =
-                            *reinterpret_cast<const double2 *>(xrows + (size_t)src_lds[row] * Kp + k0 + c);
-                }
-            for (int i = tid; i < G * (kDocIndexChunk / 2); i += kNeighborsThreads) {
-                const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                if (c < cl) {
-                    const long long id = min(g0 + row, N - 1);
-                    *reinterpret_cast<double2 *>(y_lds + row * S + c) =
-                        *reinterpret_cast<const double2 *>(docs + (size_t)id * Kp + k0 + c);
-                }
-            }
+                tile_stage<QT, kNeighborsThreads>(x_lds, xrows, Kp, k0, cl, tid,
+                                                  [&](int row) { return src_lds[row]; });
+            tile_stage<G, kNeighborsThreads>(y_lds, docs, Kp, k0, cl, tid,
+                                             [&](int row) { return min(g0 + row, N - 1); });
             __syncthreads();
-            for (int kk = 0; kk < cl; kk += 4) {
-                double av[SW], bv[4];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-                    av[t] = x_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    bv[j] = y_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t], bv[j], acc[t][j], 0, 0, 0);
-            }
+            for (int kk = 0; kk < cl; kk += 4)
+                tile_step<SW>(acc, x_lds, y_lds, kk, wid, m, kq);
         }
 
         // the group's four tiles in ascending order (every lane of the wave takes every ballot)
@@ -156,9 +126,7 @@ __device__ __forceinline__ void neighbors_sweep(int Kp, long long M, long long N
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const double s = acc[t][j][r];
-                    double d = fmax(1.0 - s, 0.0);
-                    if (measure == 0)
-                        d = sqrt(d);
+                    const double d = docindex_distance(s, measure);
                     const bool hit = d <= radius && col < c1 && col != self[t][r] && live[t][r];
                     const unsigned seg = (unsigned)(__ballot(hit) >> (16 * kq)) & 0xFFFFu;
                     if (FILL) {

@@ -53,7 +53,7 @@ constexpr int kQueryLikWaveTiles = 2;      // tiles of 16 index rows a wave mult
 constexpr int kQueryLikWaveRows = 16 * kQueryLikWaveTiles;
 constexpr int kQueryLikGroup = kQueryLikWaves * kQueryLikWaveRows;   // index rows a workgroup takes at a time
 constexpr int kQueryLikChunk = kDocIndexChunk;       // the k chunk staged in LDS
-constexpr int kQueryLikStride = kDocIndexStride;     // (its bank argument: docindex_kernels.h)
+constexpr int kQueryLikStride = kDocIndexStride;     // (its bank argument: tile_product.h)
 
 // LDS of querylik_score_kernel: the index chunk (theta^), the word chunk, the tile's counts, the four
 // lists (fp64 score, int32 row in slab)
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kQueryLikThreads) void querylik_words_kernel(
 //   D: register r of lane l is P(row l & 15, word (l >> 4) + 4 r).
 // The lanes l, l + 16, l + 32, l + 48 hold the 16 words of one row; after the two butterfly steps each
 // of them has the row's tile sum, and lane l < 16 proposes the row to the list.
-// A list holds top_n (score, row in slab) pairs, sorted, filled with (-inf, INT_MAX) at the start.
+// A list holds top_n (score, row in slab) pairs: the selection of tile_product.h, one list per wave.
 // out_s / out_id: ((slab * 4 + wave) x B x top_n), the pad written as (-inf, int64 max).
 __global__ __launch_bounds__(kQueryLikThreads) void querylik_score_kernel(
     int Kp, long long N, int B, int measure, int top_n, int slab_rows, const double *__restrict__ table,
@@ -128,14 +128,8 @@ __global__ __launch_bounds__(kQueryLikThreads) void querylik_score_kernel(
     const long long slab0 = (long long)blockIdx.y * slab_rows;
     const int nrows = (int)min((long long)slab_rows, N - slab0);
     const int tile0 = tile_off[q], ntiles = tile_off[q + 1] - tile0;
-    const double ninf = -__builtin_huge_val();
-    double *my_s = ls + wid * top_n;
-    int *my_i = li + wid * top_n;
 
-    for (int i = tid; i < kQueryLikWaves * top_n; i += kQueryLikThreads) {
-        ls[i] = ninf;
-        li[i] = INT_MAX;
-    }
+    select_init(ls, li, kQueryLikWaves * top_n, tid, kQueryLikThreads);
     __syncthreads();
 
     for (int g0 = 0; g0 < nrows; g0 += G) {
@@ -211,26 +205,18 @@ __global__ __launch_bounds__(kQueryLikThreads) void querylik_score_kernel(
         for (int j = 0; j < WT; ++j) {
             const double v = score[j];
             const int rl = g0 + wid * WR + j * 16 + m;              // index row in the slab
-            const double tv = my_s[top_n - 1];
-            const int ti = my_i[top_n - 1];
-            unsigned long long mask = __ballot(kq == 0 && rl < nrows && docindex_before(v, rl, tv, ti));
-            while (mask) {                                          // (uniform)
-                const int L = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
-                const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
-                docindex_insert(my_s, my_i, top_n, __hiloint2double(hi, lo), g0 + wid * WR + j * 16 + L, lane);
-            }
+            const double tv = ls[wid * top_n + top_n - 1];
+            const int ti = li[wid * top_n + top_n - 1];
+            const bool pass = kq == 0 && rl < nrows && docindex_before(v, rl, tv, ti);
+            select_offer(pass, v, ls, li, top_n, lane, [&](int) { return wid; },
+                         [&](int L) { return g0 + wid * WR + j * 16 + L; });
         }
     }
 
     // the wave's list as one run of top_n values
     const size_t o = (((size_t)blockIdx.y * kQueryLikWaves + wid) * B + q) * top_n;
-    for (int p = lane; p < top_n; p += kWave) {
-        const int id = my_i[p];
-        out_s[o + p] = my_s[p];
-        out_id[o + p] = id == INT_MAX ? LLONG_MAX : slab0 + id;
-    }
+    select_write<1>(ls + wid * top_n, li + wid * top_n, top_n, 1, out_s + o, out_id + o, slab0, (long long)LLONG_MAX,
+                    lane);
 }
 
 }  // namespace trlda

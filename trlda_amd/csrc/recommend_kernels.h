@@ -8,9 +8,8 @@
 //                                                    through wave_sum_dpp
 //   q_dk   = t_dk / rs_k,     rs_k = sum_v lambda_kv formed from lambda itself (rowsum_partial_kernel,
 //                                                    rowsum_combine_wave_kernel)
-//   s(d, w) = sum_k q_dk lambda_kw                   by v_mfma_f64_16x16x4_f64: one chain of
-//                                                    ceil(K / 4) instructions over k = 0, 4, 8, ...,
-//                                                    each adding four products to the running value
+//   s(d, w) = sum_k q_dk lambda_kw                   the tile product of tile_product.h: one chain
+//                                                    of ceil(K / 4) MFMAs over k = 0, 4, 8, ...
 // The two divisions are the IEEE ones (no contraction outside the MFMA chain); topics past K add +0.
 // s(d, w) is p(w | d) under the point estimates of heldout_kernels.h.  It depends on gamma_d, column
 // w of lambda, rs and K alone -- not on the batch, the tile, the slab or the workgroup.
@@ -85,17 +84,14 @@ __global__ __launch_bounds__(kRecommendThreads) void recommend_seen_kernel(int B
 
 // Grid (tile of 64 SW documents, slab of slab_words words), 4 waves: docindex_query_kernel with
 // lambda itself as the table.  Wave w owns the 16 SW documents w * 16 SW ... of the tile -- their
-// products and their lists -- and multiplies them with every word of the slab, 64 at a time.  Both
-// operands are staged in LDS in k chunks of 32, taken in ascending k for every K (through registers,
-// a chunk ahead: below).  The q rows have
-// stride Kp; a word's column of lambda lies where the model keeps it, K contiguous doubles with
-// stride K (any alignment of 8 bytes: read one double at a time), and the tail of the last chunk is
-// filled with zeros while staging.  Words past V and documents past B are read as word V - 1 /
-// document B - 1 (the product is formed) and kept out of the selection.
-//   A operand: lane l holds Q[l & 15][k + (l >> 4)]; B operand: lambda[k + (l >> 4)][word l & 15];
-//   D: register r of lane l is s(document (l >> 4) + 4 r, word l & 15).
-// A list holds top_n (s, word in slab) pairs, sorted, filled with (-inf, INT_MAX) at the start: the
-// last entry is the threshold a candidate must be before, and most are not.  Only one that is has
+// products and their lists -- and multiplies them with every word of the slab, 64 at a time: the
+// multiply step, its layout and the selection are those of tile_product.h, X the q rows and Y the
+// words, Y[word][k] = lambda[k][word].  The staging is this kernel's own (through registers, a chunk
+// ahead: below): the q rows have stride Kp; a word's column of lambda lies where the model keeps it, K
+// contiguous doubles with stride K (any alignment of 8 bytes: read one double at a time), and the tail
+// of the last chunk is filled with zeros while staging.  Words past V and documents past B are read
+// as word V - 1 / document B - 1 and kept out of the selection.
+// A list holds top_n (s, word in slab) pairs.  Only a candidate that is before the threshold has
 // its seen bit read (seen != nullptr: B x nw uint32), and only an unseen one is inserted.
 // out_s / out_id: (slabs x B x top_n), the pad written as (-inf, INT_MAX).
 // (two waves per SIMD asked for: the compiler then keeps the accumulators in VGPRs and stays below 256)
@@ -116,12 +112,8 @@ __global__ __launch_bounds__(kRecommendThreads, SW == 1 ? 2 : 1) void recommend_
     const int q0 = blockIdx.x * QT;
     const int slab0 = blockIdx.y * slab_words;              // (below V: the host's grid)
     const int nwords = min(slab_words, V - slab0);
-    const double ninf = -__builtin_huge_val();
 
-    for (int i = tid; i < QT * top_n; i += kRecommendThreads) {
-        ls[i] = ninf;
-        li[i] = INT_MAX;
-    }
+    select_init(ls, li, QT * top_n, tid, kRecommendThreads);
     // (the first barrier of the loop below stands between this and the lists' first use)
 
     // The staging of a chunk goes through registers, a chunk ahead: the loads of chunk i + 1 (the
@@ -154,12 +146,7 @@ __global__ __launch_bounds__(kRecommendThreads, SW == 1 ? 2 : 1) void recommend_
     fetch(0, 0);
 
     for (int g0 = 0; g0 < nwords; g0 += kDocIndexGroup) {
-        docindex_f64x4 acc[SW][4];
-#pragma unroll
-        for (int t = 0; t < SW; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+        docindex_f64x4 acc[SW][4] = {};
 
         for (int k0 = 0; k0 < Kp; k0 += kDocIndexChunk) {
             const int cl = min(kDocIndexChunk, Kp - k0);
@@ -182,27 +169,13 @@ __global__ __launch_bounds__(kRecommendThreads, SW == 1 ? 2 : 1) void recommend_
                 if (ng < nwords)                            // (uniform)
                     fetch(ng, nk);
             }
-            auto multiply = [&](int kk) {
-                double a[SW], b[4];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-                    a[t] = q_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    b[j] = r_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[j], acc[t][j], 0, 0, 0);
-            };
             if (cl == kDocIndexChunk) {                     // (a whole chunk, unrolled: the LDS reads of
 #pragma unroll                                              //  a step are issued under the step before)
                 for (int kk = 0; kk < kDocIndexChunk; kk += 4)
-                    multiply(kk);
+                    tile_step<SW>(acc, q_lds, r_lds, kk, wid, m, kq);
             } else {
                 for (int kk = 0; kk < cl; kk += 4)
-                    multiply(kk);
+                    tile_step<SW>(acc, q_lds, r_lds, kk, wid, m, kq);
             }
         }
 
@@ -223,33 +196,18 @@ __global__ __launch_bounds__(kRecommendThreads, SW == 1 ? 2 : 1) void recommend_
                         const int w = slab0 + rl;
                         pass = !((seen[(size_t)(q0 + ql) * nw + (w >> 5)] >> (w & 31)) & 1u);
                     }
-                    unsigned long long mask = __ballot(pass);
-                    while (mask) {                                      // (uniform)
-                        const int L = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
-                        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
-                        const int cq = wid * WQ + t * 16 + (L >> 4) + 4 * r;
-                        docindex_insert(ls + cq * top_n, li + cq * top_n, top_n, __hiloint2double(hi, lo),
-                                        g0 + j * 16 + (L & 15), lane);
-                    }
+                    select_offer(pass, v, ls, li, top_n, lane,
+                                 [&](int L) { return wid * WQ + t * 16 + (L >> 4) + 4 * r; },
+                                 [&](int L) { return g0 + j * 16 + (L & 15); });
                 }
             }
         }
     }
 
-    // the wave's lists, each as one run of top_n values
-    for (int w = 0; w < WQ; ++w) {
-        const int ql = wid * WQ + w;
-        if (q0 + ql >= B)
-            break;
-        const size_t o = ((size_t)blockIdx.y * B + (q0 + ql)) * top_n;
-        for (int p = lane; p < top_n; p += kWave) {
-            const int id = li[ql * top_n + p];
-            out_s[o + p] = ls[ql * top_n + p];
-            out_id[o + p] = id == INT_MAX ? INT_MAX : slab0 + id;
-        }
-    }
+    // the wave's lists of documents below B
+    const size_t o = ((size_t)blockIdx.y * B + q0 + wid * WQ) * top_n;
+    select_write<WQ>(ls + wid * WQ * top_n, li + wid * WQ * top_n, top_n, B - q0 - wid * WQ, out_s + o, out_id + o,
+                     slab0, INT_MAX, lane);
 }
 
 // One workgroup per document ranks the slabs' lists as docindex_merge_kernel does: top_n passes, each

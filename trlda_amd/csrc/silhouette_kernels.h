@@ -2,9 +2,8 @@
 // index under a labelling, in the index's own distance (trlda_docindex_silhouette).
 // No reference counterpart.
 //
-//   d(i, j)     sqrt(max(0, 1 - s_ij)) (hellinger) or max(0, 1 - s_ij) (cosine), s_ij the dot of the two
-//               stored rows, formed by v_mfma_f64_16x16x4_f64 as cluster_assign_kernel forms s(n, c): one
-//               chain of Kp / 4 instructions over k = 0, 4, 8, ...; the pair (i, i) is left out by id
+//   d(i, j)     docindex_distance of s_ij, the dot of the two stored rows by the staged tile product of
+//               tile_product.h (one chain of Kp / 4 MFMAs per pair); the pair (i, i) is left out by id
 //   a(i)        sum_{j in own, j != i} d(i, j) / (n_own - 1)
 //   b(i)        the smallest of sum_{j in c} d(i, j) / n_c over the non-empty c != own; neighbour(i) the
 //               first such c in the total order (mean ascending, c ascending)
@@ -41,8 +40,7 @@ inline long long silhouette_positions(long long padded)
 // LDS of silhouette_pairs_kernel: the scored rows' chunk, the columns' chunk, and the ids of both
 constexpr size_t silhouette_pairs_lds()
 {
-    return (size_t)(kSilhouetteRows + kSilhouetteGroup) * kDocIndexStride * sizeof(double) +
-           (size_t)(kSilhouetteRows + kSilhouetteGroup) * sizeof(long long);
+    return tile_operands_lds(kSilhouetteRows) + (size_t)(kSilhouetteRows + kSilhouetteGroup) * sizeof(long long);
 }
 
 // The counting sort's second pass for the column sequence.  One workgroup; count[c * nb + b] from
@@ -95,13 +93,10 @@ __global__ __launch_bounds__(kClusterThreads) void silhouette_prefix_kernel(int 
 }
 
 // Grid (block of 128 scored rows), 4 waves: wave w owns the rows 32 w ... 32 w + 31 of the block as
-// two MFMA tiles and multiplies them with every column position, 64 at a time in ascending order.
-// Both operands are staged in LDS in k chunks of 32 taken in ascending k, as cluster_assign_kernel
-// stages its own; the scored rows are gathered through ids (NULL: row q is document q), the columns
-// through pos (a padding position reads row 0: the product is formed and left out).  Rows past M are
-// computed as row M - 1 and not written.
-//   A operand: lane l holds X[l & 15][k + (l >> 4)]; B operand: Y[l & 15][k + (l >> 4)];
-//   D: register r of lane l is s(row (l >> 4) + 4 r, column l & 15).
+// two MFMA tiles and multiplies them with every column position, 64 at a time in ascending order: the
+// product and its layout are those of tile_product.h.  The scored rows (X) are gathered through ids
+// (NULL: row q is document q), the columns (Y) through pos (a padding position reads row 0: the product
+// is formed and left out).  Rows past M are computed as row M - 1 and not written.
 // label[N], size[C]; pos[P] (P a multiple of 64), flush[P / 16]: see silhouette_prefix_kernel.
 // sil / a / b / nbr: one per scored row (a, b, nbr may be NULL).
 __global__ __launch_bounds__(kSilhouetteThreads) void silhouette_pairs_kernel(
@@ -144,12 +139,7 @@ __global__ __launch_bounds__(kSilhouetteThreads) void silhouette_pairs_kernel(
         }
 
     for (long long g0 = 0; g0 < P; g0 += G) {
-        docindex_f64x4 acc[SW][4];
-#pragma unroll
-        for (int t = 0; t < SW; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+        docindex_f64x4 acc[SW][4] = {};
 
         __syncthreads();                                    // the previous group's ids have been read
         if (tid < G)
@@ -158,35 +148,13 @@ __global__ __launch_bounds__(kSilhouetteThreads) void silhouette_pairs_kernel(
             const int cl = min(kDocIndexChunk, Kp - k0);    // a multiple of 4
             __syncthreads();                                // the previous chunk has been read
             if (!one_chunk || g0 == 0)
-                for (int i = tid; i < QT * (kDocIndexChunk / 2); i += kSilhouetteThreads) {
-                    const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                    if (c < cl)
-                        *reinterpret_cast<double2 *>(x_lds + row * S + c) =
-                            *reinterpret_cast<const double2 *>(docs + (size_t)rid_lds[row] * Kp + k0 + c);
-                }
-            for (int i = tid; i < G * (kDocIndexChunk / 2); i += kSilhouetteThreads) {
-                const int row = i / (kDocIndexChunk / 2), c = (i % (kDocIndexChunk / 2)) * 2;
-                if (c < cl) {
-                    const long long id = max(cid_lds[row], 0LL);
-                    *reinterpret_cast<double2 *>(y_lds + row * S + c) =
-                        *reinterpret_cast<const double2 *>(docs + (size_t)id * Kp + k0 + c);
-                }
-            }
+                tile_stage<QT, kSilhouetteThreads>(x_lds, docs, Kp, k0, cl, tid,
+                                                   [&](int row) { return rid_lds[row]; });
+            tile_stage<G, kSilhouetteThreads>(y_lds, docs, Kp, k0, cl, tid,
+                                              [&](int row) { return max(cid_lds[row], 0LL); });
             __syncthreads();
-            for (int kk = 0; kk < cl; kk += 4) {
-                double av[SW], bv[4];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-                    av[t] = x_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    bv[j] = y_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t], bv[j], acc[t][j], 0, 0, 0);
-            }
+            for (int kk = 0; kk < cl; kk += 4)
+                tile_step<SW>(acc, x_lds, y_lds, kk, wid, m, kq);
         }
 
         // the group's four tiles in ascending order: the distances join the lane's running sums, and
@@ -198,9 +166,7 @@ __global__ __launch_bounds__(kSilhouetteThreads) void silhouette_pairs_kernel(
             for (int t = 0; t < SW; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    double d = fmax(1.0 - acc[t][j][r], 0.0);
-                    if (measure == 0)
-                        d = sqrt(d);
+                    double d = docindex_distance(acc[t][j][r], measure);
                     if (cid < 0 || cid == rid[t][r])
                         d = 0.0;
                     sum[t][r] += d;

@@ -53,6 +53,7 @@
 #include "marginal_kernels.h"
 #include "l2r_kernels.h"
 #include "wordtopics_kernels.h"
+#include "tile_product.h"
 #include "docindex_kernels.h"
 #include "recommend_kernels.h"
 #include "relevance_kernels.h"

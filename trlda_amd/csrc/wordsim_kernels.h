@@ -30,8 +30,8 @@
 //                                                            relevance_column_kernel;
 //   z_w  = 1 / sqrt(n_w)                                     the word's scale: an IEEE square root,
 //                                                            then an IEEE division;
-//   d(q, w) = sum_k t_qk t_wk                                by v_mfma_f64_16x16x4_f64: one chain of
-//                                                            ceil(K / 4) instructions over k = 0, 4,
+//   d(q, w) = sum_k t_qk t_wk                                the tile product of tile_product.h: one
+//                                                            chain of ceil(K / 4) MFMAs over k = 0, 4,
 //                                                            8, ..., topics past K adding +0;
 //   s(q, w) = d(q, w) * (z_q * z_w)                          two multiplies, in the epilogue.
 // (sqrt(a / p) = sqrt(a) / sqrt(p) in exact arithmetic: the division leaves the inner loop.)
@@ -163,12 +163,10 @@ __global__ __launch_bounds__(kWordSimThreads) void wordsim_props_kernel(int K, i
 }
 
 // Grid (tile of 64 SW queries, slab of slab_words words), 4 waves: recommend_query_kernel's structure
-// -- wave w owns the 16 SW queries w * 16 SW ... of the tile, their products and their lists; both
-// operands are staged in LDS in k chunks of 32 taken in ascending k, through registers a chunk ahead;
-// words past V and queries past B are read as word V - 1 / query B - 1 (the product is formed) and
-// kept out of the selection.
-//   A operand: lane l holds Q[l & 15][k + (l >> 4)]; B operand: t[k + (l >> 4)][word l & 15];
-//   D: register r of lane l is d(query (l >> 4) + 4 r, word l & 15).
+// -- wave w owns the 16 SW queries w * 16 SW ... of the tile, their products and their lists; the
+// multiply step, its layout and the selection are those of tile_product.h, X the query rows and Y the
+// words' t rows; the staging is this kernel's own, through registers a chunk ahead; words past V and
+// queries past B are read as word V - 1 / query B - 1 and kept out of the selection.
 // What differs: a thread's 8 lambda values of a chunk share one k (256 threads, 32 columns), so it
 // holds that chunk's c_k in one register, and the element is transformed (wordsim_element) on its
 // way from the register to LDS; the 64 word scales of a pass are fetched with its first chunk and
@@ -199,12 +197,8 @@ __global__ __launch_bounds__(kWordSimThreads, 2) void wordsim_query_kernel(
     const int q0 = blockIdx.x * QT;
     const int slab0 = blockIdx.y * slab_words;              // (below V: the host's grid)
     const int nwords = min(slab_words, V - slab0);
-    const double ninf = -__builtin_huge_val();
 
-    for (int i = tid; i < QT * top_n; i += kWordSimThreads) {
-        ls[i] = ninf;
-        li[i] = INT_MAX;
-    }
+    select_init(ls, li, QT * top_n, tid, kWordSimThreads);
     for (int i = tid; i < QT; i += kWordSimThreads) {
         const int qr = min(q0 + i, B - 1);
         q_scale[i] = qscale ? qscale[qr] : 1.0;
@@ -251,12 +245,7 @@ __global__ __launch_bounds__(kWordSimThreads, 2) void wordsim_query_kernel(
     fetch(0, 0);
 
     for (int g0 = 0; g0 < nwords; g0 += kDocIndexGroup) {
-        docindex_f64x4 acc[SW][4];
-#pragma unroll
-        for (int t = 0; t < SW; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[t][j] = docindex_f64x4{0.0, 0.0, 0.0, 0.0};
+        docindex_f64x4 acc[SW][4] = {};
 
         for (int k0 = 0; k0 < Kp; k0 += kDocIndexChunk) {
             const int cl = min(kDocIndexChunk, Kp - k0);
@@ -281,27 +270,13 @@ __global__ __launch_bounds__(kWordSimThreads, 2) void wordsim_query_kernel(
                 if (ng < nwords)                            // (uniform)
                     fetch(ng, nk);
             }
-            auto multiply = [&](int kk) {
-                double a[SW], b[4];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-                    a[t] = q_lds[(wid * WQ + t * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    b[j] = r_lds[(j * 16 + m) * S + kk + kq];
-#pragma unroll
-                for (int t = 0; t < SW; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[j], acc[t][j], 0, 0, 0);
-            };
             if (cl == kDocIndexChunk) {                     // (a whole chunk, unrolled: the LDS reads of
 #pragma unroll                                              //  a step are issued under the step before)
                 for (int kk = 0; kk < kDocIndexChunk; kk += 4)
-                    multiply(kk);
+                    tile_step<SW>(acc, q_lds, r_lds, kk, wid, m, kq);
             } else {
                 for (int kk = 0; kk < cl; kk += 4)
-                    multiply(kk);
+                    tile_step<SW>(acc, q_lds, r_lds, kk, wid, m, kq);
             }
         }
 
@@ -322,33 +297,18 @@ __global__ __launch_bounds__(kWordSimThreads, 2) void wordsim_query_kernel(
                     const int ti = li[ql * top_n + top_n - 1];
                     const bool pass = rl < nwords && q0 + ql < B && slab0 + rl != q_id[ql] &&
                                       docindex_before(v, rl, tv, ti);
-                    unsigned long long mask = __ballot(pass);
-                    while (mask) {                                      // (uniform)
-                        const int L = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
-                        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
-                        const int cq = wid * WQ + t * 16 + (L >> 4) + 4 * r;
-                        docindex_insert(ls + cq * top_n, li + cq * top_n, top_n, __hiloint2double(hi, lo),
-                                        g0 + j * 16 + (L & 15), lane);
-                    }
+                    select_offer(pass, v, ls, li, top_n, lane,
+                                 [&](int L) { return wid * WQ + t * 16 + (L >> 4) + 4 * r; },
+                                 [&](int L) { return g0 + j * 16 + (L & 15); });
                 }
             }
         }
     }
 
-    // the wave's lists, each as one run of top_n values
-    for (int w = 0; w < WQ; ++w) {
-        const int ql = wid * WQ + w;
-        if (q0 + ql >= B)
-            break;
-        const size_t o = ((size_t)blockIdx.y * B + (q0 + ql)) * top_n;
-        for (int p = lane; p < top_n; p += kWave) {
-            const int id = li[ql * top_n + p];
-            out_s[o + p] = ls[ql * top_n + p];
-            out_id[o + p] = id == INT_MAX ? INT_MAX : slab0 + id;
-        }
-    }
+    // the wave's lists of queries below B
+    const size_t o = ((size_t)blockIdx.y * B + q0 + wid * WQ) * top_n;
+    select_write<WQ>(ls + wid * WQ * top_n, li + wid * WQ * top_n, top_n, B - q0 - wid * WQ, out_s + o, out_id + o,
+                     slab0, INT_MAX, lane);
 }
 
 }  // namespace trlda
