@@ -812,6 +812,43 @@ int trlda_model_recommend_dev(trlda_model *model, const trlda_batch *batch_or_nu
  * 16; 0: the default, 2048).  The results do not depend on it.  No reference counterpart. */
 int trlda_model_set_recommend_slab_words(trlda_model *model, int words);
 
+/* Where held-out words stand in the ranking of the whole vocabulary (csrc/ranks_kernels.h, DESIGN.md
+ * 3.30).  An E-step on observed_batch from gamma exactly as trlda_model_recommend runs it, then for
+ * every entry p = (h, c) of heldout_batch, in its stored order, of document d
+ *   ranks_out[p] = 1 + #{ w in [0, V) : w != h, w not seen by d, (s(d, w), w) before (s(d, h), h) },
+ * s and the order (s descending, word id ascending) those of trlda_model_recommend: the 1-based
+ * position of h in the list that call would return for d were top_n unbounded.  ranks_out[p] is 0
+ * where the entry is no candidate (c <= 0, or with exclude_seen != 0 a word the observed document
+ * has seen); a word listed twice gets its rank twice.  scores_out_or_null[p]: s(d, h), the bits
+ * trlda_model_recommend returns for that pair, 0.0 where the rank is 0.  candidates_out[d] = V - (distinct
+ * words d has seen), the length of d's ranking (V with exclude_seen == 0).  ranks_out (int32) and
+ * scores_out (fp64) hold nnz(heldout_batch) elements, candidates_out (int32) B, all host.  The rank is a
+ * count, taken behind the product trlda_model_recommend forms: no sort, no list, nothing of size B x V.
+ * It depends on gamma_d, lambda, the row sums, K and d's seen words alone -- not on the batch, the
+ * slab width or the threshold chunk --, and two calls agree bitwise (the only atomics are integer ORs
+ * and adds).  TRLDA_ERR_ARG, before anything is waited for, drawn, copied or launched: K above
+ * TRLDA_VI_MAX_TOPICS, a batch of another V or device, a NULL argument; TRLDA_ERR_SHAPE: the batches
+ * hold different numbers of documents.  lambda, alpha and the counters are left alone; afterwards
+ * trlda_model_get_sstats holds that E-step's statistics.  Synchronises.  No reference counterpart. */
+int trlda_model_heldout_ranks(trlda_model *model, const trlda_batch *observed_batch,
+                              const trlda_batch *heldout_batch, double *gamma, int exclude_seen, int max_iter,
+                              double threshold, int32_t *ranks_out, double *scores_out_or_null,
+                              int32_t *candidates_out);
+/* The same from B gamma columns the caller keeps on the device (K x B, read only, not validated; any
+ * K >= 1): no E-step runs, nothing is drawn, the model's statistics keep what they held.  Both batches
+ * must hold B documents (else TRLDA_ERR_SHAPE); with observed_batch NULL every word is a candidate.
+ * ranks_dev / scores_dev_or_null (nnz(heldout_batch)) and candidates_dev (B): device arrays.  Enqueued
+ * on the model's stream; does not synchronise.  On the same gamma bitwise the results of
+ * trlda_model_heldout_ranks.  No reference counterpart. */
+int trlda_model_heldout_ranks_dev(trlda_model *model, const trlda_batch *observed_batch_or_null,
+                                  const trlda_batch *heldout_batch, const double *gamma_dev, int B,
+                                  int32_t *ranks_dev, double *scores_dev_or_null, int32_t *candidates_dev);
+/* A/B switch for tests: how many of a document's thresholds (held-out entries) one counting sweep
+ * holds (1 ... 32; 0: the default, 32); a document with more takes further sweeps over the same
+ * words.  The results do not depend on it.  The slab of words is that of
+ * trlda_model_set_recommend_slab_words.  No reference counterpart. */
+int trlda_model_set_ranks_chunk(trlda_model *model, int pairs);
+
 /* Topic words by relevance, corpus terms by saliency, and the topic prevalence of a corpus
  * (csrc/relevance_kernels.h).  With R_k = sum_w lambda_kw and topic weights pi
  * (topic_weights == NULL: pi_k = R_k / sum_j R_j; else K host values, finite and > 0, normalised to

@@ -158,6 +158,9 @@ _SIGNATURES = {
     "trlda_model_recommend": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
     "trlda_model_recommend_dev": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "trlda_model_set_recommend_slab_words": (C.c_int, [vp, C.c_int]),
+    "trlda_model_heldout_ranks": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]),
+    "trlda_model_heldout_ranks_dev": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    "trlda_model_set_ranks_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_top_words": (C.c_int, [vp, C.c_int, i32p]),
     "trlda_model_word_stats": (C.c_int, [vp, vp, vp, vp, vp]),
     "trlda_model_relevant_words": (C.c_int, [vp, C.c_int, C.c_double, vp, vp, vp]),

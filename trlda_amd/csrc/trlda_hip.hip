@@ -56,6 +56,7 @@
 #include "tile_product.h"
 #include "docindex_kernels.h"
 #include "recommend_kernels.h"
+#include "ranks_kernels.h"
 #include "relevance_kernels.h"
 #include "topicdist_kernels.h"
 #include "topicdocs_kernels.h"
@@ -712,6 +713,14 @@ struct trlda_model {
         DevBuf<unsigned int> seen;
         int slab_words = 0;                     // 0: kRecommendSlabWords (trlda_model_set_recommend_slab_words)
     } recommend;
+    // the ranks of held-out words (ranks_kernels.h, trlda_model_heldout_ranks; the q rows and the seen
+    // bits are recommend's): the entries' thresholds, each document's chunks of them in order with
+    // the entries they came from, and the host form's output staging
+    struct {
+        DevBuf<double> thr, sorted_s, scores;
+        DevBuf<int32_t> sorted_h, sorted_p, ranks, candidates;
+        int chunk = 0;                          // 0: kRanksChunk (trlda_model_set_ranks_chunk)
+    } ranks;
     // relevance and saliency (relevance_kernels.h, trlda_model_relevant_words, _salient_words,
     // _word_stats): the given weights, c | log R | log pi, p | D | S | log p, the bad-lambda flag, the
     // levels' candidates and the ranked ids and scores
@@ -7066,6 +7075,206 @@ int trlda_model_recommend(trlda_model *m, const trlda_batch *b, double *gamma, i
     hipError_t e3 = hipMemcpyAsync(probs_out, g.probs, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipError_t e4 = hipStreamSynchronize(m->stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
+}
+
+}  // extern "C"
+
+// ---- the ranks of held-out words in the whole ranking (csrc/ranks_kernels.h) ----
+
+namespace {
+
+int ranks_chunk(const trlda_model *m) { return m->ranks.chunk > 0 ? m->ranks.chunk : trlda::kRanksChunk; }
+
+// what both forms check before anything is waited for, drawn, copied or launched
+int ranks_checks(const trlda_model *m, const trlda_batch *o, const trlda_batch *h)
+{
+    const int sw = recommend_slab_words(m);
+    if ((m->V + sw - 1) / sw > 65535)                    // (grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_model_set_recommend_slab_words");
+    for (const trlda_batch *b : {o, h}) {
+        if (!b)
+            continue;
+        if (b->V != m->V)
+            return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+        if (b->device != m->device)
+            return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    }
+    return TRLDA_OK;
+}
+
+// The ranks on the model's stream for the B gamma columns at gamma_dev and the entries of `held` (B
+// documents, begun), into ranks_dev / scores_dev (held->nnz each; scores_dev may be nullptr) and
+// cand_dev (B): the row sums and the q rows as recommend_device forms them (the same kernels: both
+// must give the same bits), the seen bits of `seen_of` (nullptr: every word is a candidate; else a
+// batch of B documents that has been begun), the entries' thresholds, their order, and one counting
+// sweep per chunk of thresholds of the longest held-out document.  The checks have been made; B > 0.
+int ranks_device(trlda_model *m, const trlda_batch *seen_of, const trlda_batch *held, const double *gamma_dev, int B,
+                 int32_t *ranks_dev, double *scores_dev, int32_t *cand_dev)
+{
+    auto &g = m->recommend;
+    auto &r = m->ranks;
+    const int K = m->K, V = m->V, Kp = (K + 3) / 4 * 4;
+    const int sw = recommend_slab_words(m);
+    const int slabs = (V + sw - 1) / sw;
+    const int nw = (V + 31) / 32;
+    const int T = ranks_chunk(m);
+    const int nnz = (int)held->nnz;                      // (indptr is int32)
+    const bool exclude = seen_of && seen_of->nnz > 0;
+    const double *rs = nullptr;
+    int rc = lambda_rowsums(m, &rs);
+    if (!rc) rc = g.qrows.grow((size_t)B * Kp);
+    if (!rc && exclude) rc = g.seen.grow((size_t)B * nw);
+    if (!rc) rc = r.thr.grow((size_t)nnz);
+    if (!rc) rc = r.sorted_s.grow((size_t)nnz);
+    if (!rc) rc = r.sorted_h.grow((size_t)nnz);
+    if (!rc) rc = r.sorted_p.grow((size_t)nnz);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kRanksThreads / trlda::kWave;
+    const dim3 per_doc((B + per_wg - 1) / per_wg), threads(trlda::kRanksThreads);
+    hipLaunchKernelGGL(trlda::recommend_rows_kernel, per_doc, threads, 0, m->stream, K, Kp, B, gamma_dev, rs, g.qrows);
+    HIP_TRY(hipGetLastError());
+    if (exclude) {
+        HIP_TRY(hipMemsetAsync(g.seen, 0, (size_t)B * nw * sizeof(unsigned int), m->stream));
+        hipLaunchKernelGGL(trlda::recommend_seen_kernel, per_doc, threads, 0, m->stream, B, V, nw, seen_of->indptr,
+                           seen_of->ids, seen_of->cnts, g.seen);
+        HIP_TRY(hipGetLastError());
+    }
+    const unsigned int *seen = exclude ? (const unsigned int *)g.seen : nullptr;
+    if (nnz > 0) {
+        hipLaunchKernelGGL(trlda::ranks_thresholds_kernel,
+                           dim3((nnz + trlda::kRanksEntries - 1) / trlda::kRanksEntries), threads, 0, m->stream, K, Kp,
+                           V, B, nnz, held->indptr, held->ids, held->cnts, m->lambda, g.qrows, seen, nw, r.thr,
+                           ranks_dev, scores_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(trlda::ranks_order_kernel, per_doc, threads, 0, m->stream, B, V, nw, T, held->indptr, held->ids,
+                       r.thr, seen, r.sorted_s, r.sorted_h, r.sorted_p, cand_dev);
+    HIP_TRY(hipGetLastError());
+    if (nnz == 0)
+        return TRLDA_OK;
+    constexpr int SW = 2;
+    const size_t lds = trlda::ranks_count_lds(SW);
+    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::ranks_count_kernel<SW>), lds);
+    if (rc)
+        return rc;
+    const int sweeps = (held->max_n + T - 1) / T;
+    for (int chunk = 0; chunk < sweeps; ++chunk) {
+        hipLaunchKernelGGL(trlda::ranks_count_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs), threads, lds,
+                           m->stream, K, Kp, V, B, T, chunk, sw, m->lambda, g.qrows, seen, nw, held->indptr, r.sorted_s,
+                           r.sorted_h, r.sorted_p, ranks_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_model_set_ranks_chunk(trlda_model *m, int pairs)
+{
+    if (!m || pairs < 0 || pairs > trlda::kRanksChunk)
+        return fail(TRLDA_ERR_ARG, "ranks chunk: 0 (default) or 1 ... 32 thresholds");
+    m->ranks.chunk = pairs;
+    return TRLDA_OK;
+}
+
+// The ranks from a gamma that is already on the device (no E-step): enqueued on the model's stream,
+// not synchronised
+int trlda_model_heldout_ranks_dev(trlda_model *m, const trlda_batch *o, const trlda_batch *h, const double *gamma_dev,
+                                  int B, int32_t *ranks_dev, double *scores_dev, int32_t *cand_dev)
+{
+    if (!m || !h)
+        return fail(TRLDA_ERR_ARG, "NULL model / held-out batch");
+    if (B < 0)
+        return fail(TRLDA_ERR_ARG, "a negative number of documents");
+    if (int rc_arg = ranks_checks(m, o, h))
+        return rc_arg;
+    if (h->B != B || (o && o->B != B))
+        return fail(TRLDA_ERR_SHAPE, "the batch holds another number of documents than gamma");
+    if (B > 0 && (!gamma_dev || !cand_dev || (h->nnz > 0 && !ranks_dev)))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / ranks / candidates");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(o))
+        return rc_built;
+    if (int rc_built = batch_wait(h))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc || B == 0)
+        return rc;
+    const bool exclude = o && o->nnz > 0;
+    if (exclude)
+        rc = batch_begin(m, o);
+    if (!rc) rc = batch_begin(m, h);
+    if (!rc) rc = ranks_device(m, exclude ? o : nullptr, h, gamma_dev, B, ranks_dev, scores_dev, cand_dev);
+    if (rc)
+        return rc;
+    if (exclude)
+        (void)batch_end(m, o);
+    (void)batch_end(m, h);
+    return TRLDA_OK;
+}
+
+// The E-step of trlda_model_estep_host on the observed batch, then the ranks with its gamma
+int trlda_model_heldout_ranks(trlda_model *m, const trlda_batch *o, const trlda_batch *h, double *gamma,
+                              int exclude_seen, int max_iter, double threshold, int32_t *ranks_out,
+                              double *scores_out, int32_t *cand_out)
+{
+    if (!m || !o || !h)
+        return fail(TRLDA_ERR_ARG, "NULL model / batch");
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (int rc_arg = ranks_checks(m, o, h))
+        return rc_arg;
+    if (h->B != o->B)
+        return fail(TRLDA_ERR_SHAPE, "the observed and held-out batches hold different numbers of documents");
+    if (o->B > 0 && (!gamma || !cand_out || (h->nnz > 0 && !ranks_out)))
+        return fail(TRLDA_ERR_ARG, "NULL gamma / ranks / candidates");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(o))
+        return rc_built;
+    if (int rc_built = batch_wait(h))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int K = m->K, B = o->B;
+    if (B <= 0)
+        return TRLDA_OK;
+    rc = ensure_update_workspace(m, B);
+    if (rc)
+        return rc;
+    auto &r = m->ranks;
+    const size_t nnz = (size_t)h->nnz;
+    rc = r.ranks.grow(nnz);
+    if (!rc && scores_out) rc = r.scores.grow(nnz);
+    if (!rc) rc = r.candidates.grow((size_t)B);
+    if (rc)
+        return rc;
+    double *scores_dev = scores_out ? r.scores.get() : nullptr;
+    const size_t gbytes = (size_t)K * B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, o, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc) rc = batch_begin(m, h);
+    if (!rc) rc = ranks_device(m, exclude_seen ? o : nullptr, h, m->gamma, B, r.ranks, scores_dev, r.candidates);
+    if (rc)
+        return rc;
+    (void)batch_end(m, o);
+    (void)batch_end(m, h);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(cand_out, r.candidates, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e3 = nnz ? hipMemcpyAsync(ranks_out, r.ranks, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream)
+                        : hipSuccess;
+    hipError_t e4 = nnz && scores_out ? hipMemcpyAsync(scores_out, r.scores, nnz * sizeof(double),
+                                                       hipMemcpyDeviceToHost, m->stream)
+                                      : hipSuccess;
+    hipError_t e5 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
     HIP_TRY(hipGetLastError());
     return check_split_exchange(m);
 }

@@ -169,6 +169,96 @@ def _recall_at(words, observed, heldout, num_words):
     return float(np.cumsum(ratio)[-1] / ratio.size), hits, relevant
 
 
+def _ranks_entries(indptr, ids, ranks, scores, num_words):
+    """The library's per-entry ranks (LDA.heldout_ranks) as per-document lists: of the entries with a
+    positive rank each distinct (document, word) once -- a word listed twice has the same rank twice
+    -- in ascending word id.  Returns ``(indptr int64, words int32, ranks int32, scores float64)``."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    B = len(indptr) - 1
+    V = np.int64(num_words)
+    doc = np.repeat(np.arange(B, dtype=np.int64), np.diff(indptr))
+    keep = np.flatnonzero(np.asarray(ranks) > 0)
+    key, first = np.unique(doc[keep] * V + np.asarray(ids, dtype=np.int64)[keep], return_index=True)
+    at = keep[first]
+    out = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // V, minlength=B), out=out[1:])
+    return (out, (key % V).astype(np.int32), np.asarray(ranks, dtype=np.int32)[at],
+            np.asarray(scores, dtype=np.float64)[at])
+
+
+def _ranking_tops(top_n):
+    """``top_n`` of LDA.ranking_metrics as a tuple of positive ints (one int: a tuple of one)."""
+    try:
+        tops = (operator.index(top_n),)
+    except TypeError:
+        try:
+            tops = tuple(operator.index(n) for n in top_n)
+        except TypeError:
+            raise TypeError("`top_n` should be an integer or a sequence of integers.")
+    if any(n < 1 for n in tops):
+        raise RuntimeError("`top_n` should hold positive integers.")
+    return tops
+
+
+def _ranking_metrics(indptr, ranks, candidates, top_n, return_documents=False):
+    """Full-ranking metrics from the ranks of the relevant words (LDA.ranking_metrics): host arithmetic
+    in float64, every sum through ``math.fsum``.  ``indptr`` (B + 1) and ``ranks`` (1-based) as
+    ``LDA.heldout_ranks`` returns them, ``candidates`` (B) the length n of each document's ranking,
+    ``top_n`` an int or a sequence of positive ints.  Document d with relevant ranks
+    r_1 < ... < r_R among n candidates:
+
+        mean_percentile_rank  mean over all relevant (d, w) of (r - 1) / (n - 1), 0 where n = 1
+        auc                   1 - sum_j (r_j - j) / (R (n - R)); mean over documents with R > 0, n > R
+        mrr                   mean of 1 / r_1
+        map                   mean of (1 / R) sum_j j / r_j
+        ndcg                  mean of sum_j 1 / log2(1 + r_j) / sum_{j = 1..R} 1 / log2(1 + j)
+        recall[N]             mean of #{r_j <= N} / R, for every N of top_n
+
+    the means over the documents with R > 0 (RuntimeError when there is none; ``auc`` is NaN when no
+    document has n > R).  With ``return_documents`` the entry ``documents`` holds the per-document
+    arrays (``relevant`` int64; ``percentile_rank``, ``auc``, ``mrr``, ``map``, ``ndcg`` and
+    ``recall[N]`` float64, NaN where a document is left out of the mean)."""
+    import math
+    tops = _ranking_tops(top_n)
+    indptr = np.asarray(indptr, dtype=np.int64)
+    ranks = np.asarray(ranks, dtype=np.int64)
+    candidates = np.asarray(candidates, dtype=np.int64)
+    B = len(indptr) - 1
+    if len(candidates) != B:
+        raise RuntimeError("`candidates` should hold one value per document.")
+    relevant = np.diff(indptr)
+    if not (relevant > 0).any():
+        raise RuntimeError("There are no held-out words that the observed parts have not seen.")
+    doc = {name: np.full(B, np.nan) for name in ("percentile_rank", "auc", "mrr", "map", "ndcg")}
+    doc_recall = {n: np.full(B, np.nan) for n in tops}
+    pairs = []
+    for d in np.flatnonzero(relevant > 0):
+        r = np.sort(ranks[indptr[d]:indptr[d + 1]]).astype(np.float64)
+        R, n = len(r), int(candidates[d])
+        j = np.arange(1, R + 1, dtype=np.float64)
+        pct = (r - 1.0) / (n - 1.0) if n > 1 else np.zeros(R)
+        pairs.extend(pct.tolist())
+        doc["percentile_rank"][d] = math.fsum(pct) / R
+        if n > R:
+            doc["auc"][d] = 1.0 - math.fsum(r - j) / (float(R) * float(n - R))
+        doc["mrr"][d] = 1.0 / r[0]
+        doc["map"][d] = math.fsum(j / r) / R
+        doc["ndcg"][d] = math.fsum(1.0 / np.log2(1.0 + r)) / math.fsum(1.0 / np.log2(1.0 + j))
+        for top in tops:
+            doc_recall[top][d] = np.count_nonzero(r <= top) / float(R)
+
+    def mean(a):
+        a = a[~np.isnan(a)]
+        return math.fsum(a) / len(a) if len(a) else float("nan")
+
+    out = {"mean_percentile_rank": math.fsum(pairs) / len(pairs), "auc": mean(doc["auc"]),
+           "mrr": mean(doc["mrr"]), "map": mean(doc["map"]), "ndcg": mean(doc["ndcg"]),
+           "recall": {n: mean(doc_recall[n]) for n in tops}}
+    if return_documents:
+        out["documents"] = dict(doc, recall=doc_recall, relevant=relevant.astype(np.int64))
+    return out
+
+
 class Distribution(object):
     """Abstract base (reference include/distribution.h, distributioninterface.cpp)."""
 
@@ -895,6 +985,173 @@ class LDA(Distribution):
         if return_documents:
             return recall, hits, relevant
         return recall
+
+    # -- where held-out words stand in the whole ranking (csrc/ranks_kernels.h) --------------------
+    def heldout_ranks(self, observed, heldout, latents=None, max_iter=100, threshold=0.001,
+                      return_scores=False, return_gamma=False):
+        """The position of every relevant held-out word in the ranking of the whole vocabulary.
+        ``observed`` and ``heldout`` hold the same documents' two parts as for ``recall_at`` (lists,
+        ``DocumentList`` or ``DeviceBatch``, equal in number, else RuntimeError).  VI on
+        ``observed`` exactly as ``recommend`` runs it (``latents`` as gamma0, else the draw of
+        ``update_variables``), then on the GPU, per document, the rank of each of its relevant
+        words -- the distinct words with a positive count in ``heldout_d`` that ``observed_d`` has
+        not seen, ``recall_at``'s rule -- in the ranking ``recommend(observed, exclude_seen=True)``
+        would return for it were ``top_n`` unbounded: 1 + the number of unseen words before it in
+        the order (p(w | d) descending, word id ascending).  The rank is a count behind the product
+        ``recommend`` forms: nothing is sorted and nothing of size B x V exists.
+
+        Returns ``(indptr, words, ranks, candidates)``: ``indptr`` int64 of length B + 1; ``words``
+        int32, per document its relevant words in ascending id; ``ranks`` int32, 1-based;
+        ``candidates`` int32 of length B, ``n_d = num_words - (distinct words d has seen)``, the
+        length of that ranking.  ``return_scores=True`` appends the float64 p(w | d) of each
+        relevant word (the bits ``recommend`` returns for it), ``return_gamma=True`` gamma (K x B).
+        A document's ranks do not depend on the other documents, and two calls agree bitwise.
+        lambda, alpha, eta and the update counters stay as they are."""
+        if len(observed) != len(heldout):
+            raise RuntimeError("Observed and held-out documents should be equal in number.")
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        obs, own_obs = self._batch(observed)
+        try:
+            held, own_held = self._batch(heldout)
+        except BaseException:
+            if own_obs:
+                obs.close()
+            raise
+        try:
+            self._settle()
+            B = len(obs)
+            L = _ffi.lib()
+            if latents is not None:
+                try:
+                    g = np.array(latents, dtype=np.float64, order="F", copy=True)
+                except (TypeError, ValueError):
+                    raise TypeError("`latents` should be of type `ndarray`.")
+                if g.ndim == 1:
+                    g = g.reshape(-1, 1, order="F")
+                if g.ndim != 2 or g.shape != (self._K, B):
+                    raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+                gamma = np.asfortranarray(g)
+            else:
+                gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                L.trlda_sample_gamma_init(self._K, B, gamma)          # lda.cpp:135
+            csr = held.csr
+            nnz = len(csr.ids)
+            ranks = np.zeros(nnz, dtype=np.int32)
+            scores = np.zeros(nnz, dtype=np.float64)
+            candidates = np.empty(B, dtype=np.int32)
+            _ffi.check(L.trlda_model_heldout_ranks(self._handle, obs.handle, held.handle, gamma.ctypes.data, 1,
+                                                   int(max_iter), float(threshold), ranks.ctypes.data,
+                                                   scores.ctypes.data if return_scores else None,
+                                                   candidates.ctypes.data))
+        finally:
+            if own_obs:
+                obs.close()
+            if own_held:
+                held.close()
+        indptr, words, ranks, scores = _ranks_entries(csr.indptr, csr.ids, ranks, scores, self._V)
+        out = (indptr, words, ranks, candidates)
+        if return_scores:
+            out += (scores,)
+        if return_gamma:
+            out += (gamma,)
+        return out
+
+    def heldout_ranks_gamma(self, gamma, heldout, docs=None, return_scores=False):
+        """The ranks of ``heldout_ranks`` for documents given by their ``gamma`` (K x B, every value
+        finite and positive, else RuntimeError; not an array, TypeError): no E-step runs and
+        nothing is drawn, so any number of topics is taken.  ``heldout`` (a list, ``DocumentList``
+        or ``DeviceBatch`` of B documents) holds the words to rank; ``docs`` (the same kinds, B
+        documents) gives the seen words.  Without ``docs`` every word is a candidate
+        (``candidates == num_words``) and every distinct held-out word with a positive count is
+        relevant.  Returns ``(indptr, words, ranks, candidates)`` as ``heldout_ranks`` does, with
+        ``return_scores=True`` the scores appended; on the gamma ``heldout_ranks`` returned the
+        same bits.  lambda, alpha, eta, the update counters, the model's statistics and the seeded
+        stream stay as they are."""
+        try:
+            g = np.array(gamma, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`gamma` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Gamma has wrong dimensionality.")
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise RuntimeError("Gamma should be finite and positive.")
+        g = np.asfortranarray(g)
+        B = g.shape[1]
+        if len(heldout) != B:
+            raise RuntimeError("`heldout` and `gamma` should hold the same number of documents.")
+        if docs is not None and len(docs) != B:
+            raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+        candidates = np.empty(B, dtype=np.int32)
+        if B == 0:
+            out = (np.zeros(1, dtype=np.int64), np.empty(0, dtype=np.int32), np.empty(0, dtype=np.int32), candidates)
+            return out + (np.empty(0, dtype=np.float64),) if return_scores else out
+        held, own_held = self._batch(heldout)
+        try:
+            batch, owned = self._batch(docs) if docs is not None else (None, False)
+        except BaseException:
+            if own_held:
+                held.close()
+            raise
+        L = _ffi.lib()
+        ptrs = []
+        try:
+            self._settle()
+            csr = held.csr
+            nnz = len(csr.ids)
+            ranks = np.zeros(nnz, dtype=np.int32)
+            scores = np.zeros(nnz, dtype=np.float64)
+            for nbytes in (g.nbytes, ranks.nbytes, scores.nbytes, candidates.nbytes):
+                ptr = _ffi.vp()
+                _ffi.check(L.trlda_dev_alloc(self._device, max(nbytes, 8), C.byref(ptr)))
+                ptrs.append(ptr)
+            _ffi.check(L.trlda_dev_upload(self._device, ptrs[0], g.ctypes.data, g.nbytes))
+            _ffi.check(L.trlda_model_heldout_ranks_dev(self._handle, None if batch is None else batch.handle,
+                                                       held.handle, ptrs[0], B, ptrs[1],
+                                                       ptrs[2] if return_scores else None, ptrs[3]))
+            _ffi.check(L.trlda_model_synchronize(self._handle))
+            if nnz:
+                _ffi.check(L.trlda_dev_download(self._device, ranks.ctypes.data, ptrs[1], ranks.nbytes))
+                if return_scores:
+                    _ffi.check(L.trlda_dev_download(self._device, scores.ctypes.data, ptrs[2], scores.nbytes))
+            _ffi.check(L.trlda_dev_download(self._device, candidates.ctypes.data, ptrs[3], candidates.nbytes))
+        finally:
+            for ptr in ptrs:
+                L.trlda_dev_free(self._device, ptr)
+            if owned:
+                batch.close()
+            if own_held:
+                held.close()
+        indptr, words, ranks, scores = _ranks_entries(csr.indptr, csr.ids, ranks, scores, self._V)
+        out = (indptr, words, ranks, candidates)
+        return out + (scores,) if return_scores else out
+
+    def ranking_metrics(self, observed, heldout, top_n=(10, 100), latents=None, max_iter=100, threshold=0.001,
+                        return_documents=False):
+        """The full-ranking figures of the implicit-feedback literature for the recommendations
+        against held-out words: ``heldout_ranks(observed, heldout, ...)`` on the GPU, then on the
+        host, in float64 with every sum through ``math.fsum``, for document d with relevant ranks
+        r_1 < ... < r_R among n candidates
+
+            mean_percentile_rank  mean over all relevant (d, w) of (r - 1) / (n - 1) (0 where n = 1):
+                                  0 is best, 0.5 chance (Hu, Koren & Volinsky 2008)
+            auc                   1 - sum_j (r_j - j) / (R (n - R)), over documents with R > 0, n > R
+            mrr                   1 / r_1
+            map                   (1 / R) sum_j j / r_j
+            ndcg                  sum_j 1 / log2(1 + r_j) / sum_{j = 1..R} 1 / log2(1 + j)
+            recall[N]             #{r_j <= N} / R for every N of ``top_n`` (positive ints, not capped)
+
+        each but the first the mean over the documents with R > 0 (``recall_at``'s rule, and its
+        RuntimeError when no document has a relevant word).  Relevance is binary: held-out counts
+        only decide positive or not.  Returns a dict of these entries, ``recall`` a dict N -> value;
+        with ``return_documents=True`` the entry ``documents`` holds the per-document arrays (NaN
+        where a document is left out of a mean).  lambda, alpha, eta and the update counters stay
+        as they are."""
+        tops = _ranking_tops(top_n)
+        indptr, _, ranks, candidates = self.heldout_ranks(observed, heldout, latents=latents, max_iter=max_iter,
+                                                          threshold=threshold)
+        return _ranking_metrics(indptr, ranks, candidates, tops, return_documents=return_documents)
 
     # -- nearest documents in topic space (csrc/docindex_kernels.h) ---------------------------------
     def _register_index(self, index):
