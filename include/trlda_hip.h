@@ -943,6 +943,54 @@ int trlda_prevalence_add_dev(trlda_prevalence *prevalence, const trlda_batch *ba
 int trlda_prevalence_read(trlda_prevalence *prevalence, double *prevalence_out, int64_t *num_docs);
 int trlda_prevalence_destroy(trlda_prevalence *prevalence);
 
+/* Per-topic quality diagnostics (csrc/diagnostics_kernels.h).  With R_k, pi and p_w as
+ * for trlda_model_word_stats, beta_kw = lambda_kw (1 / R_k) and log beta_kw = log lambda_kw - log R_k,
+ * K host values each:
+ *   eff_out         1 / sum_w beta_kw^2                           the effective number of words
+ *   entropy_out     H_k = -sum_w beta_kw log beta_kw
+ *   uniform_out     log V - H_k = KL(beta_k || uniform), formed on the host from H_k
+ *   corpus_out      sum_w beta_kw (log beta_kw - log p_w) = KL(beta_k || p)
+ *   exclusivity_out the mean over r < top_n, in rank order, of beta_kw / sum_j beta_jw, w = words[k * top_n + r]
+ * words (K x top_n int32, host, topic-major) are the lists the exclusivity is averaged over, e.g. those
+ * of trlda_model_top_words or trlda_model_relevant_words.  The sums over w run over chunks of 256
+ * consecutive words, ascending inside a chunk and then over the chunks, the sums over j in an order that
+ * depends on K alone; no atomics: every result repeats bitwise.  K = 1 gives exclusivity exactly 1.
+ * TRLDA_ERR_ARG, before anything is allocated or launched: a NULL argument, top_n outside
+ * [1, min(V, 100)], a weight that is not finite or <= 0, a word twice in a list; TRLDA_ERR_WORD_ID: an
+ * id outside [0, V).  A lambda with an element <= 0 or not finite fails with TRLDA_ERR_VALUE ("topic
+ * diagnostics needs a positive, finite lambda") and nothing is written to the outputs.  lambda, alpha,
+ * the counters, the statistics and the seeded stream are left alone; pending deferred statistics and
+ * stream lanes are settled first.  Synchronises.  No reference counterpart. */
+int trlda_model_word_diagnostics(trlda_model *model, int top_n, const double *topic_weights /* K or NULL */,
+                                 const int32_t *words /* K x top_n */, double *eff_out, double *entropy_out,
+                                 double *uniform_out, double *corpus_out, double *exclusivity_out);
+
+/* The document side's accumulator for `model`, in the mould of trlda_prevalence (N_d, the skipped
+ * documents and sum_j gamma_dj as there).  Per contributing document a_dk = (N_d gamma_dk) / sum_j
+ * gamma_dj and theta_dk = gamma_dk / sum_j gamma_dj; kept on the device between batches: T_k = sum_d
+ * a_dk (bitwise the sums behind trlda_prevalence_read on the same gamma), A_k = sum_d a_dk log a_dk,
+ * and the int64 counts of the documents whose largest gamma_dj is j = k (ties to the smaller j), with
+ * theta_dk > high, and with theta_dk > low.  One addition per document per sum in the order the
+ * documents are added: bitwise independent of how they are cut into batches.  0 <= low < high < 1,
+ * else TRLDA_ERR_ARG before anything is allocated.  It runs on the model's stream and must be
+ * destroyed before the model.  No reference counterpart. */
+typedef struct trlda_topicdiag trlda_topicdiag;
+int trlda_topicdiag_create(trlda_model *model, int weight_by_length, double high, double low,
+                           trlda_topicdiag **out);
+/* trlda_prevalence_add's E-step on the batch (gamma: K x B host, in: gamma0, out: gamma), then its
+ * documents are added; the same errors.  Synchronises. */
+int trlda_topicdiag_add(trlda_topicdiag *diag, const trlda_batch *batch, double *gamma, int max_iter,
+                        double threshold);
+/* Adds the batch's documents with a gamma the caller keeps on the device (K x B, read only, not
+ * validated; any K >= 1): no E-step runs, nothing is drawn.  Does not synchronise. */
+int trlda_topicdiag_add_dev(trlda_topicdiag *diag, const trlda_batch *batch, const double *gamma_dev);
+/* K host values each: tokens_out = T_k; entropy_out = log T_k - A_k / T_k, the entropy of p(d | k) =
+ * a_dk / T_k (closed in long double on the host); rank1_out, high_out, low_out = the counts;
+ * *num_docs = the documents that contributed.  None: TRLDA_ERR_VALUE.  Synchronises. */
+int trlda_topicdiag_read(trlda_topicdiag *diag, double *tokens_out, double *entropy_out, int64_t *rank1_out,
+                         int64_t *high_out, int64_t *low_out, int64_t *num_docs);
+int trlda_topicdiag_destroy(trlda_topicdiag *diag);
+
 /* Distances between topics (csrc/topicdist_kernels.h).  A topic is p_i = lambda_i /
  * S_i, S_i = sum_v lambda_iv; the second lambda, mu (K2 x V), gives q_j = mu_j / T_j.  dist_out (K x K2
  * column-major, host: [i + K * j]) =

@@ -174,6 +174,12 @@ _SIGNATURES = {
     "trlda_prevalence_add_dev": (C.c_int, [vp, vp, vp]),
     "trlda_prevalence_read": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
     "trlda_prevalence_destroy": (C.c_int, [vp]),
+    "trlda_model_word_diagnostics": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "trlda_topicdiag_create": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, C.POINTER(vp)]),
+    "trlda_topicdiag_add": (C.c_int, [vp, vp, vp, C.c_int, C.c_double]),
+    "trlda_topicdiag_add_dev": (C.c_int, [vp, vp, vp]),
+    "trlda_topicdiag_read": (C.c_int, [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64)]),
+    "trlda_topicdiag_destroy": (C.c_int, [vp]),
     "trlda_cooc_create": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
     "trlda_cooc_add": (C.c_int, [vp, vp]),
     "trlda_cooc_read": (C.c_int, [vp, i64p, i64p, C.POINTER(C.c_int64)]),

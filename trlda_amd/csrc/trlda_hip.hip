@@ -65,6 +65,7 @@
 #include "neighbors_kernels.h"
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
+#include "diagnostics_kernels.h"
 
 namespace {
 
@@ -739,6 +740,13 @@ struct trlda_model {
         DevBuf<int32_t> ids, cand_i, out_w;
         int slab_words = 0;                     // 0: kWordSimSlabWords (trlda_model_set_wordsim_slab_words)
     } wordsim;
+    // the word side of the topic diagnostics (diagnostics_kernels.h, trlda_model_word_diagnostics;
+    // log R, p and log p and the flag are relevance's): 1 / R_k, the chunks' rows of 3 K partials,
+    // Q | E | C | exclusivity (4 K), the listed words and their ratios
+    struct {
+        DevBuf<double> cinv, part, sums, ratio;
+        DevBuf<int32_t> words;
+    } diagnostics;
 };
 
 namespace {
@@ -7693,6 +7701,280 @@ int trlda_prevalence_read(trlda_prevalence *p, double *prevalence_out, int64_t *
 }
 
 int trlda_prevalence_destroy(trlda_prevalence *p)
+{
+    if (!p)
+        return TRLDA_OK;
+    if (p->model && use_device(p->model->device) == TRLDA_OK && p->model->stream)
+        (void)hipStreamSynchronize(p->model->stream);    // (its kernels may still read the buffers)
+    delete p;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- per-topic diagnostics (csrc/diagnostics_kernels.h) ----
+
+extern "C" {
+
+int trlda_model_word_diagnostics(trlda_model *m, int top_n, const double *topic_weights, const int32_t *words,
+                                 double *eff_out, double *entropy_out, double *uniform_out, double *corpus_out,
+                                 double *exclusivity_out)
+{
+    if (!m)
+        return fail(TRLDA_ERR_ARG, "model is NULL");
+    if (!words || !eff_out || !entropy_out || !uniform_out || !corpus_out || !exclusivity_out)
+        return fail(TRLDA_ERR_ARG, "NULL words / output");
+    if (int rc_arg = relevance_topn_check(m, top_n))
+        return rc_arg;
+    std::vector<double> pi;
+    if (int rc_arg = relevance_weights(m, topic_weights, pi))
+        return rc_arg;
+    const int K = m->K, V = m->V, n = top_n;
+    const size_t cells = (size_t)K * n;
+    {
+        std::vector<int32_t> row((size_t)n);
+        for (int k = 0; k < K; ++k) {
+            for (int r = 0; r < n; ++r) {
+                const int32_t w = words[(size_t)k * n + r];
+                if (w < 0 || w >= V)
+                    return fail(TRLDA_ERR_WORD_ID, "word id outside [0, num_words) in the word lists");
+                row[(size_t)r] = w;
+            }
+            std::sort(row.begin(), row.end());
+            if (std::adjacent_find(row.begin(), row.end()) != row.end())
+                return fail(TRLDA_ERR_ARG, "a word list holds a word twice");
+        }
+    }
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    auto &g = m->diagnostics;
+    const int chunks = (V + trlda::kDiagChunk - 1) / trlda::kDiagChunk;
+    rc = g.cinv.grow((size_t)K);
+    if (!rc) rc = g.part.grow((size_t)chunks * 3 * K);
+    if (!rc) rc = g.sums.grow(4 * (size_t)K);
+    if (!rc) rc = g.ratio.grow(cells);
+    if (!rc) rc = g.words.grow(cells);
+    if (!rc) rc = relevance_stats(m, pi);                // (the row sums, log R, log p and the flag)
+    if (rc)
+        return rc;
+    {
+        // (waited for here: `words` is the caller's and need not outlive an early return)
+        hipError_t e1 = hipMemcpyAsync(g.words, words, cells * sizeof(int32_t), hipMemcpyHostToDevice, m->stream);
+        hipError_t e2 = hipStreamSynchronize(m->stream);
+        HIP_TRY(e1); HIP_TRY(e2);
+    }
+    constexpr int T = trlda::kRelevanceThreads;
+    const double *rs = m->rowsums.rs;
+    hipLaunchKernelGGL(trlda::diagnostics_scale_kernel, dim3((K + T - 1) / T), dim3(T), 0, m->stream, K, rs,
+                       g.cinv.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::diagnostics_rows_kernel,
+                       dim3(chunks, (K + trlda::kDiagThreads - 1) / trlda::kDiagThreads),
+                       dim3(trlda::kDiagThreads), 0, m->stream, K, V, m->lambda, g.cinv.get(),
+                       m->relevance.coef + (size_t)K, m->relevance.stats + 3 * (size_t)V, g.part.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::diagnostics_combine_kernel, dim3((3 * K + T - 1) / T), dim3(T), 0, m->stream, 3 * K,
+                       chunks, g.part.get(), g.sums.get());
+    HIP_TRY(hipGetLastError());
+    constexpr int per_wg = T / trlda::kWave;
+    hipLaunchKernelGGL(trlda::diagnostics_exclusivity_kernel, dim3((unsigned)((cells + per_wg - 1) / per_wg)),
+                       dim3(T), 0, m->stream, K, n, m->lambda, g.cinv.get(), g.words.get(), g.ratio.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::diagnostics_mean_kernel, dim3((K + T - 1) / T), dim3(T), 0, m->stream, K, n,
+                       g.ratio.get(), g.sums + 3 * (size_t)K);
+    HIP_TRY(hipGetLastError());
+    rc = relevance_settle(m, "topic diagnostics");
+    if (rc)
+        return rc;
+    std::vector<double> sums(4 * (size_t)K);
+    hipError_t e1 = hipMemcpyAsync(sums.data(), g.sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    const long double logV = logl((long double)V);
+    for (int k = 0; k < K; ++k) {
+        const double H = -sums[(size_t)K + k];
+        eff_out[k] = 1.0 / sums[(size_t)k];
+        entropy_out[k] = H;
+        uniform_out[k] = (double)(logV - (long double)H);
+        corpus_out[k] = sums[2 * (size_t)K + k];
+        exclusivity_out[k] = sums[3 * (size_t)K + k];
+    }
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// The document side's accumulator: T | A (2 K fp64) and rank_1 | high | low and the number of
+// documents that contributed (3 K + 1 int64) on the device between batches, and the per-document
+// staging of a batch
+struct trlda_topicdiag {
+    trlda_model *model = nullptr;
+    int by_length = 1;
+    double high = 0.5, low = 0.02;
+    DevBuf<double> sums, nd, inv;
+    DevBuf<long long> counts;
+    DevBuf<int32_t> top;
+};
+
+namespace {
+
+int topicdiag_checks(const trlda_topicdiag *p, const trlda_batch *b)
+{
+    if (!p || !b)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
+    if (b->V != p->model->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != p->model->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    return TRLDA_OK;
+}
+
+// the two passes over a batch that has been begun (B > 0), on the model's stream
+int topicdiag_device(trlda_topicdiag *p, const trlda_batch *b, const double *gamma_dev)
+{
+    trlda_model *m = p->model;
+    const int K = m->K, B = b->B;
+    int rc = p->nd.grow((size_t)B);
+    if (!rc) rc = p->inv.grow((size_t)B);
+    if (!rc) rc = p->top.grow((size_t)B);
+    if (rc)
+        return rc;
+    constexpr int T = trlda::kRelevanceThreads, per_wg = T / trlda::kWave;
+    hipLaunchKernelGGL(trlda::topicdiag_docs_kernel, dim3((B + per_wg - 1) / per_wg), dim3(T), 0, m->stream, K, B,
+                       p->by_length, b->indptr, b->cnts, gamma_dev, p->nd.get(), p->inv.get(), p->top.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::topicdiag_add_kernel, dim3((K + T - 1) / T), dim3(T), 0, m->stream, K, B, p->high,
+                       p->low, gamma_dev, p->nd.get(), p->inv.get(), p->top.get(), p->sums.get(), p->counts.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_topicdiag_create(trlda_model *m, int weight_by_length, double high, double low, trlda_topicdiag **out)
+{
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!(low >= 0.0 && low < high && high < 1.0))
+        return fail(TRLDA_ERR_ARG, "the thresholds should satisfy 0 <= low < high < 1");
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    trlda_topicdiag *p = new trlda_topicdiag();
+    p->model = m;
+    p->by_length = weight_by_length ? 1 : 0;
+    p->high = high;
+    p->low = low;
+    const size_t K = (size_t)m->K;
+    rc = p->sums.alloc(2 * K);
+    if (!rc) rc = p->counts.alloc(3 * K + 1);
+    if (!rc) {
+        hipError_t e1 = hipMemsetAsync(p->sums, 0, 2 * K * sizeof(double), m->stream);
+        hipError_t e2 = hipMemsetAsync(p->counts, 0, (3 * K + 1) * sizeof(long long), m->stream);
+        if (e1 != hipSuccess || e2 != hipSuccess)
+            rc = fail(TRLDA_ERR_HIP, "clearing the diagnostics sums failed");
+    }
+    if (rc) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return TRLDA_OK;
+}
+
+int trlda_topicdiag_add_dev(trlda_topicdiag *p, const trlda_batch *b, const double *gamma_dev)
+{
+    if (int rc_arg = topicdiag_checks(p, b))
+        return rc_arg;
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    trlda_model *m = p->model;
+    int rc = check_model(m);
+    if (rc || b->B <= 0)
+        return rc;
+    if (!gamma_dev)
+        return fail(TRLDA_ERR_ARG, "gamma is NULL");
+    rc = batch_begin(m, b);
+    if (!rc) rc = topicdiag_device(p, b, gamma_dev);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    return TRLDA_OK;
+}
+
+// The E-step of trlda_model_estep_host on the batch, then the two passes with its gamma
+int trlda_topicdiag_add(trlda_topicdiag *p, const trlda_batch *b, double *gamma, int max_iter, double threshold)
+{
+    if (int rc_arg = topicdiag_checks(p, b))
+        return rc_arg;
+    trlda_model *m = p->model;
+    if (int rc_vi = check_vi(m))
+        return rc_vi;
+    if (b->B > 0 && !gamma)
+        return fail(TRLDA_ERR_ARG, "gamma is NULL");
+    // (the batches' indices are built on worker threads: trlda_batch_create)
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    int rc = check_model(m);
+    if (rc || b->B <= 0)
+        return rc;
+    rc = ensure_update_workspace(m, b->B);
+    if (rc)
+        return rc;
+    const size_t gbytes = (size_t)m->K * b->B * sizeof(double);
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
+    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc) rc = topicdiag_device(p, b, m->gamma);
+    if (rc)
+        return rc;
+    (void)batch_end(m, b);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
+}
+
+int trlda_topicdiag_read(trlda_topicdiag *p, double *tokens_out, double *entropy_out, int64_t *rank1_out,
+                         int64_t *high_out, int64_t *low_out, int64_t *num_docs)
+{
+    if (!p || !tokens_out || !entropy_out || !rank1_out || !high_out || !low_out || !num_docs)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = p->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const size_t K = (size_t)m->K;
+    std::vector<double> sums(2 * K);
+    std::vector<long long> counts(3 * K + 1);
+    hipError_t e1 = hipMemcpyAsync(sums.data(), p->sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipMemcpyAsync(counts.data(), p->counts, counts.size() * sizeof(long long),
+                                   hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    *num_docs = counts[3 * K];
+    if (counts[3 * K] <= 0)
+        return fail(TRLDA_ERR_VALUE, "topic diagnostics: no document with a positive count has been added");
+    for (size_t k = 0; k < K; ++k) {
+        const long double T = sums[k];
+        tokens_out[k] = sums[k];
+        entropy_out[k] = (double)(logl(T) - (long double)sums[K + k] / T);
+        rank1_out[k] = counts[k];
+        high_out[k] = counts[K + k];
+        low_out[k] = counts[2 * K + k];
+    }
+    return TRLDA_OK;
+}
+
+int trlda_topicdiag_destroy(trlda_topicdiag *p)
 {
     if (!p)
         return TRLDA_OK;

@@ -1564,6 +1564,49 @@ class LDA(Distribution):
                 L.trlda_prevalence_destroy(made)
         return pi
 
+    def _corpus_gamma0(self, docs, latents):
+        """``latents`` of a call that runs the E-step over ``docs`` (a batch or an iterator of
+        batches) as a K x B Fortran array, or None; checked before anything is drawn or uploaded."""
+        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
+        if latents is None:
+            return None
+        try:
+            g0 = np.array(latents, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`latents` should be of type `ndarray`.")
+        if g0.ndim == 1:
+            g0 = g0.reshape(-1, 1, order="F")
+        if g0.ndim != 2 or g0.shape[0] != self._K:
+            raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
+        # (one batch: its size is known before anything is uploaded or run)
+        if not hasattr(docs, "__next__") and g0.shape[1] != len(docs):
+            raise RuntimeError("Initial gamma has wrong dimensionality.")
+        return g0
+
+    def _corpus_estep(self, docs, g0, add):
+        """``add(batch, gamma0)`` for every batch of ``docs``, gamma0 the batch's columns of ``g0``
+        or a draw from the seeded stream as ``update_variables`` draws it."""
+        L = _ffi.lib()
+        at = 0
+        for part in (docs if hasattr(docs, "__next__") else (docs,)):
+            batch, owned = self._batch(part)
+            try:
+                B = len(batch)
+                if g0 is not None:
+                    if at + B > g0.shape[1]:
+                        raise RuntimeError("Initial gamma has wrong dimensionality.")
+                    gamma = np.asfortranarray(g0[:, at:at + B])
+                else:
+                    gamma = np.empty((self._K, B), dtype=np.float64, order="F")
+                    L.trlda_sample_gamma_init(self._K, B, gamma)  # lda.cpp:135
+                add(batch, gamma)
+                at += B
+            finally:
+                if owned:
+                    batch.close()
+        if g0 is not None and at != g0.shape[1]:
+            raise RuntimeError("Initial gamma has wrong dimensionality.")
+
     def topic_prevalence(self, docs, latents=None, max_iter=100, threshold=0.001, weight_by_length=True):
         """The weight of each topic in a corpus: a float64 array of K that sums to 1,
 
@@ -1582,43 +1625,12 @@ class LDA(Distribution):
         contributing document, or a batch of another model, raises RuntimeError.  The result plugs
         into ``topic_weights=``.  lambda, alpha, eta and the counters stay as they are (DESIGN.md
         3.23)."""
-        _ffi.check_vi_topics(self._K)                               # (before the draw and the upload)
-        g0 = None
-        if latents is not None:
-            try:
-                g0 = np.array(latents, dtype=np.float64, order="F", copy=True)
-            except (TypeError, ValueError):
-                raise TypeError("`latents` should be of type `ndarray`.")
-            if g0.ndim == 1:
-                g0 = g0.reshape(-1, 1, order="F")
-            if g0.ndim != 2 or g0.shape[0] != self._K:
-                raise RuntimeError("Initial gamma has wrong dimensionality.")  # lda.cpp:165
-            # (one batch: its size is known before anything is uploaded or run)
-            if not hasattr(docs, "__next__") and g0.shape[1] != len(docs):
-                raise RuntimeError("Initial gamma has wrong dimensionality.")
+        g0 = self._corpus_gamma0(docs, latents)
         L = _ffi.lib()
 
         def feed(acc):
-            at = 0
-            for part in (docs if hasattr(docs, "__next__") else (docs,)):
-                batch, owned = self._batch(part)
-                try:
-                    B = len(batch)
-                    if g0 is not None:
-                        if at + B > g0.shape[1]:
-                            raise RuntimeError("Initial gamma has wrong dimensionality.")
-                        gamma = np.asfortranarray(g0[:, at:at + B])
-                    else:
-                        gamma = np.empty((self._K, B), dtype=np.float64, order="F")
-                        L.trlda_sample_gamma_init(self._K, B, gamma)  # lda.cpp:135
-                    _ffi.check(L.trlda_prevalence_add(acc(), batch.handle, gamma.ctypes.data, int(max_iter),
-                                                      float(threshold)))
-                    at += B
-                finally:
-                    if owned:
-                        batch.close()
-            if g0 is not None and at != g0.shape[1]:
-                raise RuntimeError("Initial gamma has wrong dimensionality.")
+            self._corpus_estep(docs, g0, lambda batch, gamma: _ffi.check(L.trlda_prevalence_add(
+                acc(), batch.handle, gamma.ctypes.data, int(max_iter), float(threshold))))
 
         return self._prevalence(weight_by_length, feed)
 
@@ -1661,6 +1673,194 @@ class LDA(Distribution):
                     batch.close()
 
         return self._prevalence(weight_by_length, feed)
+
+    # -- per-topic diagnostics (csrc/diagnostics_kernels.h) -----------------------------------------
+    def topic_word_diagnostics(self, top_n=10, topic_weights=None, words=None):
+        """What lambda alone says about each topic's quality, the word-side columns of MALLET's
+        diagnostics file: a dict of float64 arrays of length K (``beta_kw = lambdas[k, w] /
+        lambdas[k].sum()``, ``p_w`` the marginal word probability of ``word_statistics``):
+
+          ``eff_num_words``  ``1 / sum_w beta_kw**2``: from 1 (one word) to V (uniform).
+          ``word_entropy``   ``H_k = -sum_w beta_kw log beta_kw``, nats.
+          ``uniform_dist``   ``log V - H_k``, the divergence KL(beta_k || uniform); near 0: a topic
+                             that says nothing.
+          ``corpus_dist``    KL(beta_k || p); near 0: a topic that repeats the corpus' word
+                             frequencies.
+          ``exclusivity``    the mean over the topic's listed words of ``beta_kw / sum_j beta_jw``:
+                             1 when no other topic holds them, 1 / K when every topic does.
+          ``top_words``      the K x top_n int32 lists used: ``top_words(top_n)``, or ``words`` (K x
+                             top_n ids in [0, num_words), distinct within a row, e.g. from
+                             ``relevant_words``; else RuntimeError).
+
+        ``topic_weights``, ``top_n`` and their errors are those of ``relevant_words``, as is the
+        RuntimeError for a lambda with an entry <= 0 or not finite.  Everything is reduced on the
+        GPU in an order that depends on K and V alone (5 K numbers come back; two calls agree
+        bitwise); lambda, alpha, eta, the counters and the seeded stream stay as they are
+        (DESIGN.md 3.31)."""
+        pi = self._topic_weights(topic_weights)
+        if words is None:
+            top_n = self._rank_top_n(top_n)
+        else:
+            try:
+                w = np.asarray(words)
+            except (TypeError, ValueError):
+                raise RuntimeError("`words` should be a num_topics x top_n array of word ids.")
+            if w.ndim != 2 or w.shape[0] != self._K or not np.issubdtype(w.dtype, np.integer):
+                raise RuntimeError("`words` should be a num_topics x top_n array of word ids.")
+            top_n = self._rank_top_n(w.shape[1])
+            if ((w < 0) | (w >= self._V)).any():
+                raise RuntimeError("Word id out of range in `words`.")
+            if (np.diff(np.sort(w, axis=1), axis=1) == 0).any():
+                raise RuntimeError("A row of `words` holds a word twice.")
+            words = np.ascontiguousarray(w, dtype=np.int32)
+        handle = self._open_handle()
+        if words is None:
+            words = self.top_words(top_n)
+        out = [np.empty(self._K, dtype=np.float64) for _ in range(5)]
+        _ffi.check(_ffi.lib().trlda_model_word_diagnostics(
+            handle, top_n, None if pi is None else pi.ctypes.data, words.ctypes.data,
+            *[x.ctypes.data for x in out]))
+        keys = ("eff_num_words", "word_entropy", "uniform_dist", "corpus_dist", "exclusivity")
+        res = dict(zip(keys, out))
+        res["top_words"] = words
+        return res
+
+    def _topic_document_diagnostics(self, weight_by_length, high, low, feed):
+        """``_prevalence`` for the diagnostics accumulator: runs ``feed(acc)`` and reads it."""
+        handle = self._open_handle()
+        L = _ffi.lib()
+        made = _ffi.vp()
+
+        def acc():
+            if not made:
+                _ffi.check(L.trlda_topicdiag_create(handle, 1 if weight_by_length else 0, high, low,
+                                                    C.byref(made)))
+            return made
+
+        K = self._K
+        try:
+            feed(acc)
+            tokens, entropy = np.empty(K, dtype=np.float64), np.empty(K, dtype=np.float64)
+            rank1, above, present = (np.empty(K, dtype=np.int64) for _ in range(3))
+            num_docs = C.c_int64(0)
+            _ffi.check(L.trlda_topicdiag_read(acc(), tokens.ctypes.data, entropy.ctypes.data, rank1.ctypes.data,
+                                              above.ctypes.data, present.ctypes.data, C.byref(num_docs)))
+        finally:
+            if made:
+                L.trlda_topicdiag_destroy(made)
+        ratio = np.full(K, np.nan)
+        some = present > 0
+        ratio[some] = above[some] / present[some]
+        return {"tokens": tokens, "document_entropy": entropy, "rank_1_docs": rank1, "docs_high": above,
+                "docs_low": present, "allocation_ratio": ratio, "num_docs": int(num_docs.value)}
+
+    @staticmethod
+    def _diagnostic_thresholds(high, low):
+        try:
+            high, low = float(high), float(low)
+        except (TypeError, ValueError):
+            raise RuntimeError("`high` and `low` should be numbers with 0 <= low < high < 1.")
+        if not 0.0 <= low < high < 1.0:
+            raise RuntimeError("`high` and `low` should satisfy 0 <= low < high < 1.")
+        return high, low
+
+    def topic_document_diagnostics(self, docs, latents=None, max_iter=100, threshold=0.001,
+                                   weight_by_length=True, high=0.5, low=0.02):
+        """What a corpus says about each topic's quality, the document-side columns of MALLET's
+        diagnostics file.  gamma comes from the E-step on each batch, ``docs``, ``latents``,
+        ``max_iter``, ``threshold``, ``weight_by_length`` and the skipped documents exactly as for
+        ``topic_prevalence``.  With ``theta_dk = gamma_dk / sum_j gamma_dj`` and ``a_dk = N_d
+        theta_dk``, a dict of arrays of length K:
+
+          ``tokens``            ``T_k = sum_d a_dk``, float64: the tokens the topic explains
+                                (``topic_prevalence`` is ``tokens / tokens.sum()``, bitwise).
+          ``document_entropy``  the entropy of ``p(d | k) = a_dk / T_k``, nats, float64: 0 for a
+                                topic that lives in one document, ``log(num_docs)`` for one spread
+                                evenly.
+          ``rank_1_docs``       int64: the documents whose largest gamma_dk is topic k (ties go to
+                                the smaller k); sums to ``num_docs``.
+          ``docs_high``, ``docs_low``  int64: the documents with ``theta_dk > high`` and ``> low``.
+          ``allocation_ratio``  ``docs_high / docs_low``, float64, NaN where ``docs_low`` is 0: small
+                                for a topic that is present in many documents and dominant in few.
+          ``num_docs``          the documents that contributed (an int).
+
+        ``0 <= low < high < 1``, else RuntimeError before anything is allocated; no contributing
+        document raises RuntimeError.  2 K sums and 3 K counters stay on the device between
+        batches, one addition per document each, so any cut of the corpus into batches gives the
+        same bits on the same gamma.  Like ``topic_prevalence`` the E-step overwrites the model's
+        gamma and statistics and draws only the gamma0 of batches without ``latents``; lambda,
+        alpha, eta and the counters stay as they are."""
+        high, low = self._diagnostic_thresholds(high, low)
+        g0 = self._corpus_gamma0(docs, latents)
+        L = _ffi.lib()
+
+        def feed(acc):
+            self._corpus_estep(docs, g0, lambda batch, gamma: _ffi.check(L.trlda_topicdiag_add(
+                acc(), batch.handle, gamma.ctypes.data, int(max_iter), float(threshold))))
+
+        return self._topic_document_diagnostics(weight_by_length, high, low, feed)
+
+    def topic_document_diagnostics_gamma(self, gamma, docs, weight_by_length=True, high=0.5, low=0.02):
+        """``topic_document_diagnostics`` for documents given by their ``gamma`` (K x B, finite and
+        positive, as for ``topic_prevalence_gamma``): no E-step runs, nothing is drawn and the
+        model's gamma and statistics are left alone.  ``docs`` is a batch of B documents or an
+        iterator of batches that hold B documents together, gamma's columns in their order.  On
+        the gamma ``update_variables`` returns, bitwise the result of
+        ``topic_document_diagnostics``."""
+        high, low = self._diagnostic_thresholds(high, low)
+        try:
+            g = np.array(gamma, dtype=np.float64, order="F", copy=True)
+        except (TypeError, ValueError):
+            raise TypeError("`gamma` should be of type `ndarray`.")
+        if g.ndim == 1:
+            g = g.reshape(-1, 1, order="F")
+        if g.ndim != 2 or g.shape[0] != self._K:
+            raise RuntimeError("Gamma has wrong dimensionality.")
+        if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+            raise RuntimeError("Gamma should be finite and positive.")
+        streamed = hasattr(docs, "__next__")
+        if not streamed and len(docs) != g.shape[1]:
+            raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+        L = _ffi.lib()
+
+        def feed(acc):
+            at = 0
+            for part in (docs if streamed else (docs,)):
+                batch, owned = self._batch(part)
+                ptr = _ffi.vp()
+                try:
+                    B = len(batch)
+                    if at + B > g.shape[1]:
+                        raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+                    if B:
+                        cols = np.asfortranarray(g[:, at:at + B])
+                        _ffi.check(L.trlda_dev_alloc(self._device, cols.nbytes, C.byref(ptr)))
+                        _ffi.check(L.trlda_dev_upload(self._device, ptr, cols.ctypes.data, cols.nbytes))
+                        _ffi.check(L.trlda_topicdiag_add_dev(acc(), batch.handle, ptr))
+                        _ffi.check(L.trlda_model_synchronize(self._handle))
+                    at += B
+                finally:
+                    if ptr:
+                        L.trlda_dev_free(self._device, ptr)
+                    if owned:
+                        batch.close()
+            if at != g.shape[1]:
+                raise RuntimeError("`docs` and `gamma` should hold the same number of documents.")
+
+        return self._topic_document_diagnostics(weight_by_length, high, low, feed)
+
+    def topic_diagnostics(self, docs=None, **kw):
+        """The per-topic diagnostics table: ``topic_word_diagnostics`` alone when ``docs`` is None,
+        else its dict merged with ``topic_document_diagnostics(docs, ...)``'s.  Keyword arguments
+        go to the side that takes them (``top_n``, ``topic_weights``, ``words``: the word side; the
+        others: the document side); an unknown one is a TypeError."""
+        word_kw = {k: kw.pop(k) for k in ("top_n", "topic_weights", "words") if k in kw}
+        if docs is None and kw:
+            raise TypeError("Unexpected keyword arguments without `docs`: %s." % ", ".join(sorted(kw)))
+        res = self.topic_word_diagnostics(**word_kw)
+        if docs is not None:
+            res.update(self.topic_document_diagnostics(docs, **kw))
+        return res
 
     # -- device reductions for the empirical-Bayes steps (csrc/eb_kernels.h) ----------------
     def _psi_gamma_diff_device(self, num_docs):
