@@ -778,6 +778,64 @@ int trlda_docindex_neighbors(trlda_docindex *index, double radius, const int64_t
                              int64_t *ids_out /* capacity, or NULL: count only */,
                              double *val_out /* capacity, or NULL */);
 
+/* A 2-D map of an indexed corpus: exact t-SNE (van der Maaten & Hinton 2008) on the stored rows
+ * (csrc/tsne_kernels.h).  No reference counterpart.  Every call below checks its
+ * arguments before anything is waited for, copied or launched (TRLDA_ERR_ARG; TRLDA_ERR_VALUE for
+ * values, counted on the host, with nothing changed), draws nothing, leaves the index, lambda, alpha, the
+ * counters and the model's statistics alone, settles pending deferred statistics and stream lanes first,
+ * runs on the model's stream, synchronises once at its end and keeps no device buffer of its own beyond
+ * the index's grow-only query workspaces.  No floating-point atomics; two calls agree bitwise.
+ *
+ * trlda_docindex_nearest: per indexed document its top_n nearest OTHER documents, 1 <= top_n <=
+ * min(N - 1, 99), in the total order of trlda_docindex_query (s descending, id ascending) with the
+ * document's own id removed: top_n + 1 entries are ranked with the table's own rows as the query rows
+ * (no gamma, no copy of the table), the entry with the own id is dropped, or the last one where the own
+ * id is not among them (more than top_n exact duplicates of smaller id).  ids_out (int64) and sim_out
+ * (fp64, the similarity s) are N x top_n row-major.  The rows are scored block_rows at a time (0:
+ * automatic); the result does not depend on it, on trlda_docindex_set_slab_rows or on how the index was
+ * filled. */
+int trlda_docindex_nearest(trlda_docindex *index, int top_n, int block_rows, int64_t *ids_out /* N x top_n */,
+                           double *sim_out /* N x top_n */);
+/* The conditional affinities of the k = min(N - 1, floor(3 perplexity)) nearest neighbours, 1 <=
+ * perplexity <= 33, from the device-resident form of trlda_docindex_nearest.  With D_j = fmax(1 - s_j, 0)
+ * (the squared Hellinger distance, or the cosine distance), d_j = D_j - D_first, w_j = exp(-beta d_j),
+ * S = sum w_j: p_j = w_j / S with beta such that H(beta) = log S + beta sum w_j d_j / S = log perplexity,
+ * found by doubling from 1 / mean(d) and bisection to hi - lo <= hi 2^-50 (at most 200 steps; beta = hi).
+ * Two limits: log k <= log perplexity gives beta = 0 and p = 1 / k; m >= perplexity exactly tied
+ * nearest (d_j = 0) gives beta = +inf and p = 1 / m on those m, 0 elsewhere.  ids_out (int64) and p_out
+ * (fp64) are N x k row-major in the order of trlda_docindex_nearest, beta_out (fp64) holds N values. */
+int trlda_docindex_affinities(trlda_docindex *index, double perplexity, int block_rows, int64_t *ids_out,
+                              double *p_out, double *beta_out);
+/* A/B switch: rows per workgroup of the repulsion kernel, 0 (default, 256) or a multiple of 64 up to 1024.
+ * Results do not depend on it. */
+int trlda_docindex_set_tsne_tile(trlda_docindex *index, int rows);
+/* y_out (N x 2 row-major) = (theta^ - mean) axes: theta^ recovered from the stored rows as
+ * trlda_docindex_topic_documents recovers it, mean_host K values, axes_host 2 x K (axis c at
+ * axes_host[c K ...]).  The PCA start of a map: the caller passes the two leading eigenvectors of the
+ * scatter of trlda_docindex_topic_moments, scaled as it likes. */
+int trlda_docindex_tsne_project(trlda_docindex *index, const double *mean_host /* K */,
+                                const double *axes_host /* 2 x K */, double *y_out /* N x 2 */);
+/* The t-SNE gradient and KL divergence of the map y (N x 2 row-major, host, finite) under the affinities
+ * P in CSR form (indptr N + 1 from 0, ids in [0, N), p finite and >= 0; N >= 2 is the index's size):
+ *   q_ij = 1 / (1 + |y_i - y_j|^2),  R_i = sum_{j != i} q_ij^2 (y_i - y_j),  Z = sum_i sum_{j != i} q_ij,
+ *   A_i = sum_{j in row i} P_ij q_ij (y_i - y_j),  grad_i = 4 (exaggeration A_i - R_i / Z),
+ *   kl = sum_{P_ij > 0} P_ij log(P_ij Z / q_ij)   (P without the exaggeration).
+ * All N^2 pairs are formed in fp64 with IEEE division; the order of every addition is fixed (the header
+ * comment of csrc/tsne_kernels.h), so the result is a function of (y, P, N, exaggeration) alone,
+ * whatever trlda_docindex_set_tsne_tile says.  grad_out is N x 2, kl_out one value. */
+int trlda_docindex_tsne_gradient(trlda_docindex *index, const int64_t *indptr, const int64_t *ids, const double *p,
+                                 const double *y, double exaggeration, double *grad_out, double *kl_out);
+/* num_iterations steps of gradient descent on y (in: the start, out: the map).  Iteration t uses
+ * early_exaggeration and momentum0 while t < exaggeration_iterations, then 1 and momentum1; elementwise
+ * same = (g > 0) == (v > 0), gain = same ? gain 0.8 : gain + 0.2, gain = max(gain, 0.01) (gains start at
+ * 1, v at 0), v = momentum v - learning_rate gain g, y += v; then the column means of y, formed in a
+ * fixed tree, are subtracted.  kl_out[t] is the KL divergence before update t.  The whole loop is
+ * enqueued on the model's stream and waited for once. */
+int trlda_docindex_tsne_run(trlda_docindex *index, const int64_t *indptr, const int64_t *ids, const double *p,
+                            double *y /* N x 2 */, int num_iterations, int exaggeration_iterations,
+                            double early_exaggeration, double learning_rate, double momentum0, double momentum1,
+                            double *kl_out /* num_iterations */);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

@@ -66,6 +66,7 @@
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
 #include "diagnostics_kernels.h"
+#include "tsne_kernels.h"
 
 namespace {
 
@@ -5890,6 +5891,7 @@ struct trlda_docindex {
     int64_t n = 0;                       // rows in use: the next id
     int slab_rows = 0;                   // 0: kDocIndexSlabRows
     int moment_chunk = 0;                // rows per chunk of trlda_docindex_topic_moments (0: automatic)
+    int tsne_tile = 0;                   // rows per workgroup of tsne_repulsion_kernel (0: kTsneDefaultTile)
     DevBuf<double> qrows, gstage, cand_s, out_s;
     DevBuf<long long> cand_i, out_i;
 };
@@ -6900,6 +6902,360 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
     hipError_t e2 = val_out ? hipMemcpyAsync(val_out, hit_val, (size_t)total * sizeof(double), hipMemcpyDeviceToHost,
                                              stream)
                             : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- a 2-D map of an indexed corpus (csrc/tsne_kernels.h) ----
+
+namespace {
+
+template <int SW>
+int docindex_launch_self(trlda_docindex *x, const double *qrows, int B, int top, int slab_rows, int slabs)
+{
+    const size_t lds = trlda::docindex_query_lds(SW, top);
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::docindex_query_kernel<SW>), lds);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::docindex_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
+                       dim3(trlda::kDocIndexThreads), lds, x->model->stream, x->Kp, (long long)x->n, B, top,
+                       slab_rows, x->rows, qrows, x->cand_s, x->cand_i);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// what the neighbour graph checks before anything is waited for, copied or launched
+int docindex_nearest_checks(const trlda_docindex *x, int top_n, int block_rows)
+{
+    if (x->n < 2)
+        return fail(TRLDA_ERR_ARG, "the neighbours of an index need at least two documents");
+    if (top_n < 1 || top_n > trlda::kTsneMaxNeighbors || (int64_t)top_n > x->n - 1)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(number of indexed documents - 1, 99)]");
+    if (block_rows < 0)
+        return fail(TRLDA_ERR_ARG, "rows per block: 0 (automatic) or positive");
+    const int sr = docindex_slab_rows(x);
+    if ((x->n + sr - 1) / sr > 65535)                    // (grid dimension y)
+        return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
+    return TRLDA_OK;
+}
+
+// The neighbour graph on the model's stream: per stored row its top_n nearest other rows into nn_i /
+// nn_s (N x top_n).  The table's own rows are the query rows, a block of them at a time: no gamma, no
+// copy.  The checks have been made.
+int docindex_nearest_device(trlda_docindex *x, int top_n, int block_rows, DevBuf<long long> &nn_i,
+                            DevBuf<double> &nn_s)
+{
+    const int top = top_n + 1, sr = docindex_slab_rows(x);
+    const int slabs = (int)((x->n + sr - 1) / sr);
+    // rows per block: whole tiles of 128 query rows, the slabs' lists of a block at most 2^24 entries
+    long long nb = block_rows > 0 ? block_rows
+                                  : std::max<long long>(128, ((1ll << 24) / ((long long)top * slabs)) / 128 * 128);
+    nb = std::min<long long>(nb, x->n);
+    const size_t cells = (size_t)nb * top;
+    int rc = x->cand_s.grow(cells * slabs);
+    if (!rc) rc = x->cand_i.grow(cells * slabs);
+    if (!rc) rc = x->out_s.grow(cells);
+    if (!rc) rc = x->out_i.grow(cells);
+    if (!rc) rc = nn_i.alloc((size_t)x->n * top_n);
+    if (!rc) rc = nn_s.alloc((size_t)x->n * top_n);
+    if (rc)
+        return rc;
+    for (int64_t b0 = 0; b0 < x->n; b0 += nb) {
+        const int B = (int)std::min<int64_t>(nb, x->n - b0);
+        const double *qrows = x->rows + (size_t)b0 * x->Kp;
+        rc = top <= trlda::kDocIndexWideMaxTop ? docindex_launch_self<2>(x, qrows, B, top, sr, slabs)
+                                               : docindex_launch_self<1>(x, qrows, B, top, sr, slabs);
+        if (rc)
+            return rc;
+        hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(B), dim3(trlda::kDocIndexThreads), 0,
+                           x->model->stream, B, top, slabs, x->cand_s, x->cand_i, x->out_i, x->out_s);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(trlda::tsne_selfdrop_kernel, dim3((B + trlda::kTsneThreads - 1) / trlda::kTsneThreads),
+                           dim3(trlda::kTsneThreads), 0, x->model->stream, B, top_n, (long long)b0, x->out_i.get(),
+                           x->out_s.get(), nn_i.get(), nn_s.get());
+        HIP_TRY(hipGetLastError());
+    }
+    return TRLDA_OK;
+}
+
+// a CSR of affinities for N rows and the map Y (N x 2), on the host: TRLDA_ERR_VALUE with nothing changed
+int tsne_check_inputs(int64_t N, const int64_t *indptr, const int64_t *ids, const double *p, const double *y)
+{
+    if (indptr[0] != 0)
+        return fail(TRLDA_ERR_VALUE, "affinities: indptr should start at 0");
+    for (int64_t i = 0; i < N; ++i)
+        if (indptr[i + 1] < indptr[i])
+            return fail(TRLDA_ERR_VALUE, "affinities: indptr should not decrease");
+    const int64_t nnz = indptr[N];
+    if (nnz > 0 && (!ids || !p))
+        return fail(TRLDA_ERR_VALUE, "affinities: NULL ids / values");
+    for (int64_t e = 0; e < nnz; ++e) {
+        if (ids[e] < 0 || ids[e] >= N)
+            return fail(TRLDA_ERR_VALUE, "affinities: an id lies outside [0, number of indexed documents)");
+        if (!(p[e] >= 0.0) || !std::isfinite(p[e]))
+            return fail(TRLDA_ERR_VALUE, "affinities: a value is negative or not finite");
+    }
+    for (int64_t t = 0; t < 2 * N; ++t)
+        if (!std::isfinite(y[t]))
+            return fail(TRLDA_ERR_VALUE, "the map should be finite");
+    return TRLDA_OK;
+}
+
+// The device side of one gradient: the CSR, the map and every intermediate
+struct tsne_work {
+    long long N = 0, W = 0;
+    int stripes = 0, tile = 0;
+    DevBuf<long long> indptr, ids;
+    DevBuf<double> P, Y, part, R, scal, grad, klrow;     // scal: Z, KL, the two column sums of Y
+};
+
+int tsne_upload(trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p, const double *y,
+                tsne_work &w)
+{
+    const long long N = x->n;
+    const size_t nnz = (size_t)indptr[N];
+    hipStream_t stream = x->model->stream;
+    w.N = N;
+    w.W = trlda::tsne_stripe_width(N);
+    w.stripes = (int)((N + w.W - 1) / w.W);
+    w.tile = x->tsne_tile > 0 ? x->tsne_tile : trlda::kTsneDefaultTile;
+    int rc = w.indptr.alloc((size_t)N + 1);
+    if (!rc) rc = w.ids.alloc(nnz);
+    if (!rc) rc = w.P.alloc(nnz);
+    if (!rc) rc = w.Y.alloc((size_t)2 * N);
+    if (!rc) rc = w.part.alloc((size_t)3 * w.stripes * N);
+    if (!rc) rc = w.R.alloc((size_t)3 * N);
+    if (!rc) rc = w.scal.alloc(4);
+    if (!rc) rc = w.grad.alloc((size_t)2 * N);
+    if (!rc) rc = w.klrow.alloc((size_t)N);
+    if (rc)
+        return rc;
+    // (the caller's arrays live until its synchronisation)
+    HIP_TRY(hipMemcpyAsync(w.indptr, indptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if (nnz) {
+        HIP_TRY(hipMemcpyAsync(w.ids, ids, nnz * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.P, p, nnz * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
+    HIP_TRY(hipMemcpyAsync(w.Y, y, (size_t)2 * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    return TRLDA_OK;
+}
+
+// grad (N x 2) and the rows' KL terms of the map w.Y, on the stream
+int tsne_gradient_device(hipStream_t stream, tsne_work &w, double exaggeration)
+{
+    const long long N = w.N;
+    const unsigned per_wave = (unsigned)((N + 3) / 4), per_thread = (unsigned)((N + trlda::kTsneThreads - 1) /
+                                                                              trlda::kTsneThreads);
+    hipLaunchKernelGGL(trlda::tsne_repulsion_kernel, dim3((unsigned)((N + w.tile - 1) / w.tile), w.stripes),
+                       dim3(w.tile), 0, stream, N, w.W, w.Y.get(), w.part.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::tsne_rowsum_kernel, dim3(per_thread), dim3(trlda::kTsneThreads), 0, stream, N,
+                       w.stripes, w.part.get(), w.R.get());
+    HIP_TRY(hipGetLastError());
+    const trlda::tsne_tree_job z = {w.R.get() + (size_t)2 * N, 1, w.scal.get()};
+    hipLaunchKernelGGL(trlda::tsne_tree_kernel, dim3(1), dim3(trlda::kTsneTreeThreads), 0, stream, N, z, z, z);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::tsne_attract_kernel, dim3(per_wave), dim3(trlda::kTsneThreads), 0, stream, N,
+                       w.indptr.get(), w.ids.get(), w.P.get(), w.Y.get(), w.R.get(), w.scal.get(), exaggeration,
+                       w.grad.get(), w.klrow.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int tsne_entry_checks(const trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p,
+                      const double *y)
+{
+    if (!x || !indptr || !y)
+        return fail(TRLDA_ERR_ARG, "NULL index / indptr / map");
+    if (x->n < 2)
+        return fail(TRLDA_ERR_ARG, "a map needs at least two indexed documents");
+    if (x->n > INT_MAX)                                  // (grid dimension x of the wave-per-document kernels)
+        return fail(TRLDA_ERR_ARG, "too many indexed documents for a map");
+    return tsne_check_inputs(x->n, indptr, ids, p, y);
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_set_tsne_tile(trlda_docindex *x, int rows)
+{
+    if (!x || rows < 0 || rows % 64 || rows > trlda::kTsneMaxTile)
+        return fail(TRLDA_ERR_ARG, "rows per workgroup: 0 (default) or a multiple of 64 up to 1024");
+    x->tsne_tile = rows;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_nearest(trlda_docindex *x, int top_n, int block_rows, int64_t *ids_out, double *sim_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!x || !ids_out || !sim_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / ids / similarities");
+    if (int rc_arg = docindex_nearest_checks(x, top_n, block_rows))
+        return rc_arg;
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    DevBuf<long long> nn_i;
+    DevBuf<double> nn_s;
+    if ((rc = docindex_nearest_device(x, top_n, block_rows, nn_i, nn_s)))
+        return rc;
+    const size_t cells = (size_t)x->n * top_n;
+    hipError_t e1 = hipMemcpyAsync(ids_out, nn_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(sim_out, nn_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_affinities(trlda_docindex *x, double perplexity, int block_rows, int64_t *ids_out, double *p_out,
+                              double *beta_out)
+{
+    if (!x || !ids_out || !p_out || !beta_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / ids / p / beta");
+    if (!(perplexity >= 1.0 && perplexity <= 33.0))
+        return fail(TRLDA_ERR_ARG, "the perplexity must lie in [1, 33]");
+    if (x->n < 2)
+        return fail(TRLDA_ERR_ARG, "the neighbours of an index need at least two documents");
+    const int k = (int)std::min<int64_t>(x->n - 1, (int64_t)std::floor(3.0 * perplexity));
+    if (int rc_arg = docindex_nearest_checks(x, k, block_rows))
+        return rc_arg;
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const long long N = x->n;
+    if ((N + 3) / 4 > INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many indexed documents");
+    DevBuf<long long> nn_i;
+    DevBuf<double> nn_s, pc, beta;
+    if ((rc = pc.alloc((size_t)N * k)) || (rc = beta.alloc((size_t)N)) ||
+        (rc = docindex_nearest_device(x, k, block_rows, nn_i, nn_s)))
+        return rc;
+    hipLaunchKernelGGL(trlda::tsne_calibrate_kernel, dim3((unsigned)((N + 3) / 4)), dim3(trlda::kTsneThreads), 0,
+                       m->stream, N, k, perplexity, nn_s.get(), pc.get(), beta.get());
+    HIP_TRY(hipGetLastError());
+    const size_t cells = (size_t)N * k;
+    hipError_t e1 = hipMemcpyAsync(ids_out, nn_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(p_out, pc, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipMemcpyAsync(beta_out, beta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_tsne_project(trlda_docindex *x, const double *mean_host, const double *axes_host, double *y_out)
+{
+    if (!x || !mean_host || !axes_host || !y_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / mean / axes / map");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    const long long N = x->n;
+    if ((N + 3) / 4 > INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many indexed documents");
+    for (int k = 0; k < 3 * x->K; ++k)
+        if (!std::isfinite(k < x->K ? mean_host[k] : axes_host[k - x->K]))
+            return fail(TRLDA_ERR_VALUE, "the mean and the axes should be finite");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    DevBuf<double> mean, axes, Y;
+    if ((rc = mean.alloc(x->K)) || (rc = axes.alloc((size_t)2 * x->K)) || (rc = Y.alloc((size_t)2 * N)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(mean, mean_host, (size_t)x->K * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(axes, axes_host, (size_t)2 * x->K * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(trlda::tsne_project_kernel, dim3((unsigned)((N + 3) / 4)), dim3(trlda::kTsneThreads), 0,
+                       m->stream, x->K, x->Kp, N, x->measure, x->rows.get(), mean.get(), axes.get(), Y.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(y_out, Y, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_tsne_gradient(trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p,
+                                 const double *y, double exaggeration, double *grad_out, double *kl_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!grad_out || !kl_out)
+        return fail(TRLDA_ERR_ARG, "NULL gradient / kl");
+    if (int rc_arg = tsne_entry_checks(x, indptr, ids, p, y))
+        return rc_arg;
+    if (!std::isfinite(exaggeration))
+        return fail(TRLDA_ERR_VALUE, "the exaggeration should be finite");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    tsne_work w;
+    if ((rc = tsne_upload(x, indptr, ids, p, y, w)) || (rc = tsne_gradient_device(stream, w, exaggeration)))
+        return rc;
+    const trlda::tsne_tree_job kl = {w.klrow.get(), 1, w.scal.get() + 1};
+    hipLaunchKernelGGL(trlda::tsne_tree_kernel, dim3(1), dim3(trlda::kTsneTreeThreads), 0, stream, w.N, kl, kl, kl);
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(grad_out, w.grad, (size_t)2 * w.N * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(kl_out, w.scal.get() + 1, sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_tsne_run(trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p, double *y,
+                            int num_iterations, int exaggeration_iterations, double early_exaggeration,
+                            double learning_rate, double momentum0, double momentum1, double *kl_out)
+{
+    if (num_iterations < 0 || (num_iterations > 0 && !kl_out))
+        return fail(TRLDA_ERR_ARG, "a negative number of iterations, or NULL kl");
+    if (int rc_arg = tsne_entry_checks(x, indptr, ids, p, y))
+        return rc_arg;
+    if (!std::isfinite(early_exaggeration) || !std::isfinite(learning_rate) || !std::isfinite(momentum0) ||
+        !std::isfinite(momentum1))
+        return fail(TRLDA_ERR_VALUE, "the exaggeration, learning rate and momenta should be finite");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc || num_iterations == 0)
+        return rc;
+    hipStream_t stream = m->stream;
+    tsne_work w;
+    DevBuf<double> vel, gain, kl;
+    const long long N = x->n, n2 = 2 * N;
+    if ((rc = tsne_upload(x, indptr, ids, p, y, w)) || (rc = vel.alloc((size_t)n2)) || (rc = gain.alloc((size_t)n2)) ||
+        (rc = kl.alloc((size_t)num_iterations)))
+        return rc;
+    std::vector<double> ones((size_t)n2, 1.0);           // (lives until the synchronisation below)
+    HIP_TRY(hipMemsetAsync(vel, 0, (size_t)n2 * sizeof(double), stream));
+    HIP_TRY(hipMemcpyAsync(gain, ones.data(), (size_t)n2 * sizeof(double), hipMemcpyHostToDevice, stream));
+    const unsigned per_el = (unsigned)((n2 + trlda::kTsneThreads - 1) / trlda::kTsneThreads);
+    for (int t = 0; t < num_iterations; ++t) {
+        const bool early = t < exaggeration_iterations;
+        if ((rc = tsne_gradient_device(stream, w, early ? early_exaggeration : 1.0)))
+            return rc;
+        hipLaunchKernelGGL(trlda::tsne_update_kernel, dim3(per_el), dim3(trlda::kTsneThreads), 0, stream, n2,
+                           early ? momentum0 : momentum1, learning_rate, w.grad.get(), vel.get(), gain.get(),
+                           w.Y.get());
+        HIP_TRY(hipGetLastError());
+        // the KL before this update, and the column sums of the new map: one launch, three workgroups
+        const trlda::tsne_tree_job j0 = {w.klrow.get(), 1, kl.get() + t}, j1 = {w.Y.get(), 2, w.scal.get() + 2},
+                                   j2 = {w.Y.get() + 1, 2, w.scal.get() + 3};
+        hipLaunchKernelGGL(trlda::tsne_tree_kernel, dim3(3), dim3(trlda::kTsneTreeThreads), 0, stream, N, j0, j1, j2);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(trlda::tsne_centre_kernel, dim3(per_el), dim3(trlda::kTsneThreads), 0, stream, n2, (double)N,
+                           w.scal.get() + 2, w.Y.get());
+        HIP_TRY(hipGetLastError());
+    }
+    hipError_t e1 = hipMemcpyAsync(y, w.Y, (size_t)n2 * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(kl_out, kl, (size_t)num_iterations * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e3 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());

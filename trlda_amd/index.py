@@ -21,6 +21,8 @@ from . import _ffi
 MEASURES = {"hellinger": 0, "cosine": 1}
 MAX_TOP_N = 100
 MAX_CLUSTERS = 4096                          # TRLDA_CLUSTER_MAX_CLUSTERS
+MAX_NEIGHBORS = 99                           # kTsneMaxNeighbors
+MAX_PERPLEXITY = 33                          # 3 * perplexity <= MAX_NEIGHBORS
 
 
 def _measure(name):
@@ -564,6 +566,246 @@ class DocumentIndex(object):
                 _nearest(nearest, rows[border], hit[border], dist[border])
             first = last
         return _dbscan_labels(parent, core, nearest, return_core)
+
+    # -- the map (csrc/tsne_kernels.h) ----------------------------------------------
+    def set_tsne_tile(self, rows):
+        """A/B switch: rows per workgroup of the map's repulsion kernel (0: default).  Results do not
+        depend on it."""
+        _ffi.check(_ffi.lib().trlda_docindex_set_tsne_tile(self._live(), operator.index(rows)))
+
+    def _size(self):
+        N = int(_ffi.lib().trlda_docindex_size(self._live()))
+        if N < 1:
+            raise RuntimeError("The index is empty.")
+        return N
+
+    def nearest_neighbors(self, top_n=10, return_similarity=False, block_rows=0):
+        """The k-nearest-neighbour graph of the index on itself: for every indexed document its
+        ``top_n`` nearest *other* documents in ``query``'s total order (s descending, id ascending),
+        its own id removed -- by id, so documents with equal rows find each other.  Returns ``(ids,
+        dist)``, int64 and float64 of shape (N, top_n); with ``return_similarity=True`` the
+        similarity s in place of the distance.  ``1 <= top_n <= min(N - 1, 99)``, else RuntimeError.
+        The table's own rows are the query rows, ``block_rows`` at a time (0: automatic): no gamma
+        makes a round trip and the table is not copied.  The result does not depend on
+        ``block_rows``, on ``set_slab_rows`` or on how the index was filled."""
+        handle = self._live()
+        N = self._size()
+        top_n = operator.index(top_n)
+        block_rows = operator.index(block_rows)
+        if not 1 <= top_n <= min(N - 1, MAX_NEIGHBORS):
+            raise RuntimeError("`top_n` should lie between 1 and min(len(index) - 1, %d)." % MAX_NEIGHBORS)
+        if block_rows < 0:
+            raise ValueError("`block_rows` should not be negative.")
+        ids = np.empty((N, top_n), dtype=np.int64)
+        sim = np.empty((N, top_n), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_nearest(handle, top_n, block_rows, ids.ctypes.data, sim.ctypes.data))
+        return self._result(ids, sim, return_similarity)
+
+    def affinities(self, perplexity=30.0, return_conditional=False, block_rows=0):
+        """The t-SNE affinities of the indexed documents: per document the conditional distribution
+        ``p_{j|i} = exp(-beta_i d_j) / sum`` over its ``k = min(N - 1, floor(3 * perplexity))`` nearest
+        neighbours, ``d_j = D_ij - D_i,first`` with ``D_ij = max(0, 1 - s_ij)`` (the squared Hellinger
+        distance, or the cosine distance), ``beta_i`` calibrated on the device so that the row's
+        entropy is ``log(perplexity)``; then ``P_ij = (p_{j|i} + p_{i|j}) / (2 N)`` on the union
+        pattern, on the host.  ``1 <= perplexity <= 33``, else ValueError.  A row with ``k <=
+        perplexity`` is uniform over its k neighbours (beta 0); a row whose m nearest are exactly tied
+        with ``m >= perplexity`` is uniform over those m (beta +inf).
+
+        Returns ``(indptr, ids, p)``: a CSR of N rows, int64, int64 and float64, ascending id within a
+        row, bitwise symmetric, summing to 1 up to rounding.  ``return_conditional=True`` returns
+        ``(ids N x k, p N x k, beta N)`` as the device left them, in ``nearest_neighbors``' order."""
+        handle = self._live()
+        N = self._size()
+        perplexity = _perplexity(perplexity)
+        block_rows = operator.index(block_rows)
+        if block_rows < 0:
+            raise ValueError("`block_rows` should not be negative.")
+        k = min(N - 1, int(math.floor(3.0 * perplexity)))
+        ids = np.empty((N, k), dtype=np.int64)
+        p = np.empty((N, k), dtype=np.float64)
+        beta = np.zeros(N, dtype=np.float64)
+        if N > 1:
+            _ffi.check(_ffi.lib().trlda_docindex_affinities(handle, perplexity, block_rows, ids.ctypes.data,
+                                                            p.ctypes.data, beta.ctypes.data))
+        return (ids, p, beta) if return_conditional else _symmetrise(ids, p)
+
+    def embedding_gradient(self, Y, affinities, exaggeration=1.0):
+        """The t-SNE gradient and KL divergence of the map ``Y`` (N x 2) under ``affinities`` (the CSR
+        ``(indptr, ids, p)`` of ``affinities()`` or any valid one for this N): with ``q_ij = 1 / (1 +
+        |y_i - y_j|^2)``, ``Z = sum_{i != j} q_ij``, ``grad_i = 4 (exaggeration * sum_j P_ij q_ij (y_i -
+        y_j) - sum_{j != i} q_ij^2 (y_i - y_j) / Z)`` and ``kl = sum_{P_ij > 0} P_ij log(P_ij Z / q_ij)``
+        (P without the exaggeration).  All N^2 pairs are formed, in float64 and a fixed order: two calls
+        agree bitwise, whatever ``set_tsne_tile`` says.  Returns ``(grad N x 2, kl)``."""
+        handle = self._live()
+        N = self._size()
+        y = _map(Y, N, "Y")
+        indptr, ids, p = _affinities(affinities, N)
+        exaggeration = float(exaggeration)
+        if not math.isfinite(exaggeration):
+            raise ValueError("`exaggeration` should be finite.")
+        grad = np.zeros((N, 2), dtype=np.float64)
+        kl = C.c_double(0.0)
+        if N > 1:
+            _ffi.check(_ffi.lib().trlda_docindex_tsne_gradient(handle, indptr.ctypes.data, ids.ctypes.data,
+                                                               p.ctypes.data, y.ctypes.data, exaggeration,
+                                                               grad.ctypes.data, C.byref(kl)))
+        return grad, kl.value
+
+    def _pca_start(self, N):
+        """The PCA start of a map: theta^ - mean projected on the two leading eigenvectors of the
+        scatter, scaled so that the first column's standard deviation is 1e-4."""
+        mean, scatter = self._moments()
+        axes = _pca_axes(scatter, N)
+        y = np.empty((N, 2), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_tsne_project(self._live(), mean.ctypes.data, axes.ctypes.data,
+                                                          y.ctypes.data))
+        return y
+
+    def embed(self, perplexity=30.0, num_iterations=750, init="pca", learning_rate="auto", early_exaggeration=12.0,
+              exaggeration_iterations=250, momentum=(0.5, 0.8), affinities=None, return_info=False):
+        """A 2-D map of the indexed documents by exact t-SNE (van der Maaten & Hinton 2008) in the
+        index's own measure: ``affinities(perplexity)`` (or the CSR given as ``affinities``), then
+        ``num_iterations`` steps of ``embedding_gradient`` with gains and momentum, all on the device
+        with one wait at the end.  Iteration t uses ``early_exaggeration`` and ``momentum[0]`` while
+        ``t < exaggeration_iterations``, then 1 and ``momentum[1]``; elementwise ``same = (g > 0) ==
+        (v > 0)``, ``gain = same ? 0.8 gain : gain + 0.2``, ``gain = max(gain, 0.01)``, ``v = momentum v -
+        learning_rate gain g``, ``y += v``; then the column means are subtracted.
+        ``learning_rate='auto'`` is ``max(N / early_exaggeration / 4, 50)``.
+
+        ``init='pca'`` starts from theta^ minus its mean projected on the two leading eigenvectors of
+        ``topic_covariance`` (each signed so that its largest-magnitude component is positive; the
+        eigenvectors come from ``numpy.linalg.eigh`` on the host, the projection runs on the device),
+        scaled so that the first column's standard deviation is 1e-4; an N x 2 array is taken as it is.
+        The repulsion is exact -- all N^2 pairs every iteration, no Barnes-Hut or FFT approximation -- and
+        every sum has a fixed order, so two calls agree bitwise.  Nothing is drawn.
+
+        Returns Y, float64 N x 2; with ``return_info=True`` also a dict: ``kl`` (float64,
+        ``num_iterations``: the KL divergence before each update), ``iterations``, ``learning_rate``.
+        One indexed document gives ``[[0, 0]]``."""
+        handle = self._live()
+        N = self._size()
+        num_iterations = operator.index(num_iterations)
+        exaggeration_iterations = operator.index(exaggeration_iterations)
+        if num_iterations < 0 or exaggeration_iterations < 0:
+            raise ValueError("`num_iterations` and `exaggeration_iterations` should not be negative.")
+        early_exaggeration = float(early_exaggeration)
+        if not (early_exaggeration > 0.0 and math.isfinite(early_exaggeration)):
+            raise ValueError("`early_exaggeration` should be finite and positive.")
+        try:
+            mom0, mom1 = (float(v) for v in momentum)
+        except (TypeError, ValueError):
+            raise ValueError("`momentum` should be a pair of numbers.")
+        if not (math.isfinite(mom0) and math.isfinite(mom1)):
+            raise ValueError("`momentum` should be finite.")
+        if isinstance(learning_rate, str):
+            if learning_rate != "auto":
+                raise ValueError("`learning_rate` should be 'auto' or a number.")
+            lr = max(N / early_exaggeration / 4.0, 50.0)
+        else:
+            lr = float(learning_rate)
+            if not (lr > 0.0 and math.isfinite(lr)):
+                raise ValueError("`learning_rate` should be finite and positive.")
+        if isinstance(init, str):
+            if init != "pca":
+                raise ValueError("`init` should be 'pca' or an N x 2 array.")
+            y = None
+        else:
+            y = _map(init, N, "init").copy()
+        if affinities is None:
+            perplexity = _perplexity(perplexity)
+        else:
+            affinities = _affinities(affinities, N)
+        # (every argument has been checked: the device comes in from here)
+        kl = np.zeros(num_iterations, dtype=np.float64)
+        if N == 1:
+            y = np.zeros((1, 2), dtype=np.float64)
+        else:
+            indptr, ids, p = self.affinities(perplexity) if affinities is None else affinities
+            if y is None:
+                y = self._pca_start(N)
+            _ffi.check(_ffi.lib().trlda_docindex_tsne_run(handle, indptr.ctypes.data, ids.ctypes.data, p.ctypes.data,
+                                                          y.ctypes.data, num_iterations, exaggeration_iterations,
+                                                          early_exaggeration, lr, mom0, mom1, kl.ctypes.data))
+        if not return_info:
+            return y
+        return y, {"kl": kl, "iterations": num_iterations, "learning_rate": lr}
+
+
+def _perplexity(perplexity):
+    perplexity = float(perplexity)
+    if not 1.0 <= perplexity <= MAX_PERPLEXITY:
+        raise ValueError("`perplexity` should lie between 1 and %d." % MAX_PERPLEXITY)
+    return perplexity
+
+
+def _map(Y, N, name):
+    """A map as contiguous float64 N x 2, or the documented error."""
+    try:
+        y = np.ascontiguousarray(Y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("`%s` should be of type `ndarray`." % name)
+    if y.shape != (N, 2):
+        raise ValueError("`%s` should be of shape (%d, 2)." % (name, N))
+    if not np.all(np.isfinite(y)):
+        raise ValueError("`%s` should be finite." % name)
+    return y
+
+
+def _affinities(affinities, N):
+    """``(indptr, ids, p)`` as contiguous int64, int64, float64 for a map of N documents, or ValueError."""
+    try:
+        indptr, ids, p = affinities
+    except (TypeError, ValueError):
+        raise ValueError("`affinities` should be the triple (indptr, ids, p).")
+    indptr, ids, p = np.asarray(indptr), np.asarray(ids), np.asarray(p)
+    if indptr.dtype.kind not in "iu" or ids.dtype.kind not in "iu" or p.dtype.kind not in "fiu":
+        raise ValueError("`affinities` should hold integer `indptr` and `ids` and real `p`.")
+    if indptr.ndim != 1 or indptr.shape[0] != N + 1:
+        raise ValueError("`affinities` were built for %d documents, not %d." % (max(indptr.size - 1, 0), N))
+    if ids.ndim != 1 or p.ndim != 1 or ids.shape != p.shape:
+        raise ValueError("`affinities`: `ids` and `p` should be one-dimensional and of one length.")
+    if int(indptr[0]) != 0 or int(indptr[-1]) != ids.shape[0] or np.any(np.diff(indptr) < 0):
+        raise ValueError("`affinities`: `indptr` should rise from 0 to len(ids).")
+    if ids.shape[0] and (int(ids.min()) < 0 or int(ids.max()) >= N):
+        raise ValueError("`affinities`: ids should lie between 0 and %d." % (N - 1))
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if not (np.all(np.isfinite(p)) and np.all(p >= 0.0)):
+        raise ValueError("`affinities`: p should be finite and not negative.")
+    return np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(ids, dtype=np.int64), p
+
+
+def _symmetrise(ids, p):
+    """The closing arithmetic of ``affinities``: ``P_ij = (p_{j|i} + p_{i|j}) / (2 N)`` on the union
+    pattern of the conditional rows (ids, p: N x k), as a CSR with ascending id within a row."""
+    N, k = ids.shape
+    rows = np.repeat(np.arange(N, dtype=np.int64), k)
+    cols = ids.reshape(-1)
+    r = np.concatenate((rows, cols))
+    c = np.concatenate((cols, rows))
+    v = np.concatenate((p.reshape(-1), p.reshape(-1)))
+    order = np.lexsort((c, r))
+    r, c, v = r[order], c[order], v[order]
+    if not len(r):
+        return np.zeros(N + 1, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+    head = np.flatnonzero(np.concatenate(([True], (r[1:] != r[:-1]) | (c[1:] != c[:-1]))))
+    # (a pair holds one or two terms: their sum is the same bits in either order)
+    P = np.add.reduceat(v, head) / (2.0 * N)
+    indptr = np.searchsorted(r[head], np.arange(N + 1, dtype=np.int64)).astype(np.int64)
+    return indptr, np.ascontiguousarray(c[head]), P
+
+
+def _pca_axes(scatter, N):
+    """The two leading eigenvectors of the scatter matrix (2 x K), each signed so that its
+    largest-magnitude component is positive, scaled so that the first projection's standard
+    deviation ``sqrt(l_1 / N)`` becomes 1e-4 (a scatter without spread: zeros)."""
+    K = scatter.shape[0]
+    w, V = np.linalg.eigh(scatter)
+    axes = np.zeros((2, K), dtype=np.float64)
+    for c in range(min(2, K)):
+        a = V[:, K - 1 - c]
+        axes[c] = a if a[np.argmax(np.abs(a))] > 0 else -a
+    top = float(w[K - 1])
+    return np.ascontiguousarray(axes * (1e-4 / math.sqrt(top / N) if top > 0.0 else 0.0))
 
 
 def _silhouette_labels(labels, N):
