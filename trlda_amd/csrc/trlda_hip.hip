@@ -956,6 +956,17 @@ int batch_end(trlda_model *m, const trlda_batch *b)
     return TRLDA_OK;
 }
 
+// was the batch made for this model's vocabulary, on its device?  (The entry points that report
+// these two next to each other in this order; the others keep their own.)
+int batch_matches_model(const trlda_model *m, const trlda_batch *b)
+{
+    if (b->V != m->V)
+        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
+    if (b->device != m->device)
+        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    return TRLDA_OK;
+}
+
 int ensure_batch_workspace(trlda_model *m, const trlda_batch *b)
 {
     // (row -1 of epg is zero: where the statistics stage of a merged launch points the entries
@@ -2780,6 +2791,22 @@ int estep_device(trlda_model *m, const trlda_batch *b, double *gamma_dev, double
     return estep_device(m, b, gamma_dev, out, max_iter, threshold, iters_dev, gamma_in_dev);
 }
 
+// The E-step of trlda_model_estep_host on the batch from the caller's gamma (host memory), into
+// m->gamma and m->sstats: the workspace, the upload, the launches.  Nothing is queued when the
+// workspace cannot grow.  The batch has been waited for and the model checked.
+int estep_from_host(trlda_model *m, const trlda_batch *b, const double *gamma, int max_iter, double threshold,
+                    int32_t *iters_dev)
+{
+    int rc = ensure_update_workspace(m, b->B);
+    if (rc)
+        return rc;
+    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
+    if (b->B > 0)
+        HIP_TRY(hipMemcpyAsync(m->gamma, gamma, (size_t)m->K * b->B * sizeof(double), hipMemcpyHostToDevice,
+                               m->stream));
+    return estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, iters_dev);
+}
+
 int blend_device(trlda_model *m, const double *lambda_prime, const double *sstats, double rho,
                  double eta, double scale)
 {
@@ -2929,6 +2956,27 @@ int check_split_exchange(trlda_model *m)
                                "launch for its documents or the documents for their topic factors "
                                "(trlda_model_set_merged_launch(model, 0)), or the direct slot exchange "
                                "for a peer's signal; the results of that call are void");
+}
+
+// The end of an entry point that brings results back: `queued` are the statuses of the copies it
+// has queued on the model's stream (all of them are queued before the first is looked at, so the
+// stream is waited for whatever they said: host buffers may go out of scope behind this).  The
+// first failed copy, then the wait, then a launch's error, then the exchange.
+int wait_for_results(trlda_model *m, std::initializer_list<hipError_t> queued)
+{
+    const hipError_t waited = hipStreamSynchronize(m->stream);
+    for (hipError_t copy_queued : queued)
+        HIP_TRY(copy_queued);
+    HIP_TRY(waited);
+    HIP_TRY(hipGetLastError());
+    return check_split_exchange(m);
+}
+
+// before an accumulator on the model's device is deleted: the stream's kernels may still read its buffers
+void wait_before_delete(const trlda_model *m)
+{
+    if (m && use_device(m->device) == TRLDA_OK && m->stream)
+        (void)hipStreamSynchronize(m->stream);
 }
 
 // wait for the model's stream; a call whose exchange gave up has no results
@@ -5023,9 +5071,6 @@ int trlda_model_estep_host(trlda_model *m, const trlda_batch *b, double *gamma, 
         return rc;
     if (!b || !sstats || (b->B > 0 && !gamma))
         return fail(TRLDA_ERR_ARG, "NULL batch / gamma / sstats");
-    rc = ensure_update_workspace(m, b->B);
-    if (rc)
-        return rc;
     const size_t gbytes = (size_t)m->K * b->B * sizeof(double);
     const size_t sbytes = (size_t)m->K * m->V * sizeof(double);
     int32_t *iters_dev = nullptr;
@@ -5035,10 +5080,7 @@ int trlda_model_estep_host(trlda_model *m, const trlda_batch *b, double *gamma, 
             return rc;
         iters_dev = m->iters;
     }
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    if (gbytes)
-        HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, iters_dev);
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, iters_dev);
     if (!rc) {
         if (gbytes)
             HIP_TRY(hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream));
@@ -5070,9 +5112,6 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
         return fail(TRLDA_ERR_ARG, "NULL batch / gamma / bound");
     if (b->B <= 0)
         return fail(TRLDA_ERR_ARG, "the lower bound needs at least one document");
-    rc = ensure_update_workspace(m, b->B);
-    if (rc)
-        return rc;
     // elbo_docs_kernel's K + 16 doubles: more than 48 KiB from K = 6129 on
     rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::elbo_docs_kernel<kDenseThreads>),
                             ((size_t)m->K + 4 * (kDenseThreads / trlda::kWave)) * sizeof(double));
@@ -5081,9 +5120,7 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     const int K = m->K, V = m->V, B = b->B;
     const size_t KV = (size_t)K * V;
     const size_t gbytes = (size_t)K * B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);   // :309
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);              // :309
     if (rc)
         return rc;
     const int G = (int)std::min<size_t>((KV + kDenseThreads - 1) / kDenseThreads, 1024);
@@ -5104,11 +5141,8 @@ int trlda_model_lower_bound(trlda_model *m, const trlda_batch *b, double *gamma,
     hipError_t e2 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
     hipError_t e3 = hipMemcpyAsync(alpha_h.data(), m->alpha, (size_t)K * sizeof(double),
                                    hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    HIP_TRY(hipGetLastError());
-    if (int rc_x = check_split_exchange(m))
-        return rc_x;
+    if (int rc_end = wait_for_results(m, {e1, e2, e3}))
+        return rc_end;
     HIP_TRY(hipMemcpy(lam_sum.data(), m->psi_sum + K, (size_t)K * sizeof(double),
                       hipMemcpyDeviceToHost));
     double pw_pb = 0.0, lg_lambda = 0.0, pz = 0.0, ptheta = 0.0;
@@ -5159,14 +5193,9 @@ int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_bat
         return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
     if (o->device != m->device || h->device != m->device)
         return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    rc = ensure_update_workspace(m, o->B);
-    if (rc)
-        return rc;
     const int K = m->K, B = o->B;
     const size_t gbytes = (size_t)K * B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, o, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    rc = estep_from_host(m, o, gamma, max_iter, threshold, nullptr);
     if (rc)
         return rc;
     rc = m->reduce_out.grow(2 * (size_t)B);
@@ -5192,11 +5221,8 @@ int trlda_model_predictive(trlda_model *m, const trlda_batch *o, const trlda_bat
     hipError_t e1 = hipMemcpyAsync(hbuf.data(), out, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost,
                                    m->stream);
     hipError_t e2 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    if (int rc_x = check_split_exchange(m))
-        return rc_x;
+    if (int rc_end = wait_for_results(m, {e1, e2}))
+        return rc_end;
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     std::memcpy(tokens_out, hbuf.data() + B, (size_t)B * sizeof(double));
     return TRLDA_OK;
@@ -5254,10 +5280,8 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
         return fail(TRLDA_ERR_ARG, "num_samples should be at least 1");
     if ((uint64_t)num_samples * (uint64_t)m->K >= ((uint64_t)1 << 32))
         return fail(TRLDA_ERR_ARG, "num_samples * num_topics should be below 2^32 (the draws' counter)");
-    if (b->V != m->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    if (int rc_arg = batch_matches_model(m, b))
+        return rc_arg;
     if (m->eb.active)
         return fail(TRLDA_ERR_ARG, "an empirical-Bayes step is on its way (its alpha is not on the device "
                                    "yet): trlda_model_online_eb_finish first");
@@ -5268,16 +5292,7 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
     if (B <= 0)
         return TRLDA_OK;
     const size_t gbytes = (size_t)K * B * sizeof(double);
-    if (vi) {
-        rc = ensure_update_workspace(m, B);
-        if (rc)
-            return rc;
-        m->gamma0_src = nullptr;                       // the caller's gamma, not one drawn ahead
-        HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-        rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
-    } else {
-        rc = batch_begin(m, b);
-    }
+    rc = vi ? estep_from_host(m, b, gamma, max_iter, threshold, nullptr) : batch_begin(m, b);
     if (rc)
         return rc;
     const double *rs = nullptr;
@@ -5300,11 +5315,8 @@ int trlda_model_document_loglik(trlda_model *m, const trlda_batch *b, double *ga
     hipError_t e1 = hipMemcpyAsync(hbuf.data(), out, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost,
                                    m->stream);
     hipError_t e2 = vi ? hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream) : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    if (int rc_x = check_split_exchange(m))
-        return rc_x;
+    if (int rc_end = wait_for_results(m, {e1, e2}))
+        return rc_end;
     std::memcpy(loglik_out, hbuf.data(), (size_t)B * sizeof(double));
     if (ess_out)
         std::memcpy(ess_out, hbuf.data() + B, (size_t)B * sizeof(double));
@@ -5538,11 +5550,7 @@ int word_topics_checks(const trlda_model *m, const trlda_batch *b, int top_n)
         return fail(TRLDA_ERR_ARG, "NULL batch");
     if (top_n < 1 || top_n > trlda::kWordTopicsMaxTop || top_n > m->K)
         return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_topics, 32)]");
-    if (b->V != m->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    return TRLDA_OK;
+    return batch_matches_model(m, b);
 }
 
 // The scoring stage on the model's stream: the row sums of lambda formed from lambda itself as in
@@ -5615,9 +5623,7 @@ int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma,
     const int K = m->K, B = b->B;
     if (B <= 0)
         return TRLDA_OK;
-    rc = ensure_update_workspace(m, B);
-    if (rc)
-        return rc;
+    // (the results' room before the E-step: no room, nothing queued)
     auto &g = m->wordtopics;
     const size_t cells = (size_t)b->nnz * (size_t)top_n;
     if (cells) {
@@ -5627,9 +5633,7 @@ int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma,
             return rc;
     }
     const size_t gbytes = (size_t)K * B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc && cells)
         rc = word_topics_device(m, b, top_n, m->gamma, g.topics, g.probs);
     if (rc)
@@ -5642,10 +5646,7 @@ int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma,
     hipError_t e3 = cells ? hipMemcpyAsync(probs_out, g.probs, cells * sizeof(double), hipMemcpyDeviceToHost,
                                            m->stream)
                           : hipSuccess;
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    return wait_for_results(m, {e1, e2, e3});
 }
 
 // ---- topic coherence: top words and document counts (csrc/coherence_kernels.h) ----
@@ -5804,10 +5805,8 @@ int trlda_cooc_add(trlda_cooc *c, const trlda_batch *b)
     int rc = check_model(m);
     if (rc)
         return rc;
-    if (b->V != m->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
+    if (int rc_arg = batch_matches_model(m, b))
+        return rc_arg;
     if (b->B > 0) {
         if ((rc = batch_begin(m, b)))
             return rc;
@@ -5871,8 +5870,7 @@ int trlda_cooc_destroy(trlda_cooc *c)
 {
     if (!c)
         return TRLDA_OK;
-    if (c->model && use_device(c->model->device) == TRLDA_OK && c->model->stream)
-        (void)hipStreamSynchronize(c->model->stream);    // (its kernels may still read the buffers)
+    wait_before_delete(c->model);
     delete c;
     return TRLDA_OK;
 }
@@ -5962,11 +5960,7 @@ int docindex_batch_checks(const trlda_model *m, const trlda_batch *b)
 {
     if (!b)
         return fail(TRLDA_ERR_ARG, "NULL batch");
-    if (b->V != m->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != m->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    return TRLDA_OK;
+    return batch_matches_model(m, b);
 }
 
 template <int SW>
@@ -6021,19 +6015,6 @@ int docindex_download(trlda_docindex *x, int B, int top_n, int64_t *ids_out, dou
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
-}
-
-// the E-step of trlda_model_estep_host on the batch from the caller's gamma, into m->gamma and
-// m->sstats; the batch has been waited for and the model checked
-int docindex_estep(trlda_model *m, const trlda_batch *b, const double *gamma, int max_iter, double threshold)
-{
-    int rc = ensure_update_workspace(m, b->B);
-    if (rc)
-        return rc;
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, (size_t)m->K * b->B * sizeof(double), hipMemcpyHostToDevice,
-                           m->stream));
-    return estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
 }
 
 }  // namespace
@@ -6135,7 +6116,7 @@ int trlda_docindex_add(trlda_docindex *x, const trlda_batch *b, double *gamma, i
     if (!gamma)
         return fail(TRLDA_ERR_ARG, "NULL gamma");
     rc = docindex_room(x, x->n + B, B);
-    if (!rc) rc = docindex_estep(m, b, gamma, max_iter, threshold);
+    if (!rc) rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = docindex_launch_rows(x, m->gamma, B, x->rows + (size_t)x->n * x->Kp);
     if (rc)
         return rc;
@@ -6145,6 +6126,7 @@ int trlda_docindex_add(trlda_docindex *x, const trlda_batch *b, double *gamma, i
     hipError_t e2 = hipStreamSynchronize(m->stream);
     HIP_TRY(e1); HIP_TRY(e2);
     HIP_TRY(hipGetLastError());
+    // (not wait_for_results: the rows count once the launches are known to have run, whatever the exchange says)
     x->n += B;
     return check_split_exchange(m);
 }
@@ -6197,7 +6179,7 @@ int trlda_docindex_query(trlda_docindex *x, const trlda_batch *b, double *gamma,
         return TRLDA_OK;
     if (!gamma || !ids_out || !sim_out)
         return fail(TRLDA_ERR_ARG, "NULL gamma / ids / similarities");
-    rc = docindex_estep(m, b, gamma, max_iter, threshold);
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = docindex_query_device(x, m->gamma, B, top_n);
     if (rc)
         return rc;
@@ -6229,8 +6211,7 @@ int trlda_docindex_destroy(trlda_docindex *x)
 {
     if (!x)
         return TRLDA_OK;
-    if (x->model && use_device(x->model->device) == TRLDA_OK && x->model->stream)
-        (void)hipStreamSynchronize(x->model->stream);    // (its kernels may still read the buffers)
+    wait_before_delete(x->model);
     delete x;
     return TRLDA_OK;
 }
@@ -7281,13 +7262,7 @@ int recommend_checks(const trlda_model *m, const trlda_batch *b, int top_n)
     const int sw = recommend_slab_words(m);
     if ((m->V + sw - 1) / sw > 65535)                    // (grid dimension y)
         return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_model_set_recommend_slab_words");
-    if (b) {
-        if (b->V != m->V)
-            return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-        if (b->device != m->device)
-            return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    }
-    return TRLDA_OK;
+    return b ? batch_matches_model(m, b) : TRLDA_OK;
 }
 
 template <int SW>
@@ -7417,30 +7392,20 @@ int trlda_model_recommend(trlda_model *m, const trlda_batch *b, double *gamma, i
     const int K = m->K, B = b->B;
     if (B <= 0)
         return TRLDA_OK;
-    rc = ensure_update_workspace(m, B);
-    if (rc)
-        return rc;
+    // (the results' room before the E-step: no room, nothing queued)
     auto &g = m->recommend;
     const size_t cells = (size_t)B * top_n;
     rc = g.words.grow(cells);
     if (!rc) rc = g.probs.grow(cells);
-    if (rc)
-        return rc;
-    const size_t gbytes = (size_t)K * B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    if (!rc) rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = recommend_device(m, exclude_seen ? b : nullptr, m->gamma, B, top_n, g.words, g.probs);
     if (rc)
         return rc;
     (void)batch_end(m, b);
-    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(words_out, g.words, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
     hipError_t e3 = hipMemcpyAsync(probs_out, g.probs, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    return wait_for_results(m, {e1, e2, e3});
 }
 
 }  // extern "C"
@@ -7457,15 +7422,10 @@ int ranks_checks(const trlda_model *m, const trlda_batch *o, const trlda_batch *
     const int sw = recommend_slab_words(m);
     if ((m->V + sw - 1) / sw > 65535)                    // (grid dimension y)
         return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_model_set_recommend_slab_words");
-    for (const trlda_batch *b : {o, h}) {
-        if (!b)
-            continue;
-        if (b->V != m->V)
-            return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-        if (b->device != m->device)
-            return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    }
-    return TRLDA_OK;
+    if (o)
+        if (int rc_arg = batch_matches_model(m, o))
+            return rc_arg;
+    return h ? batch_matches_model(m, h) : TRLDA_OK;
 }
 
 // The ranks on the model's stream for the B gamma columns at gamma_dev and the entries of `held` (B
@@ -7608,9 +7568,7 @@ int trlda_model_heldout_ranks(trlda_model *m, const trlda_batch *o, const trlda_
     const int K = m->K, B = o->B;
     if (B <= 0)
         return TRLDA_OK;
-    rc = ensure_update_workspace(m, B);
-    if (rc)
-        return rc;
+    // (the results' room before the E-step: no room, nothing queued)
     auto &r = m->ranks;
     const size_t nnz = (size_t)h->nnz;
     rc = r.ranks.grow(nnz);
@@ -7619,17 +7577,14 @@ int trlda_model_heldout_ranks(trlda_model *m, const trlda_batch *o, const trlda_
     if (rc)
         return rc;
     double *scores_dev = scores_out ? r.scores.get() : nullptr;
-    const size_t gbytes = (size_t)K * B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, o, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    rc = estep_from_host(m, o, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = batch_begin(m, h);
     if (!rc) rc = ranks_device(m, exclude_seen ? o : nullptr, h, m->gamma, B, r.ranks, scores_dev, r.candidates);
     if (rc)
         return rc;
     (void)batch_end(m, o);
     (void)batch_end(m, h);
-    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, (size_t)K * B * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(cand_out, r.candidates, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost,
                                    m->stream);
     hipError_t e3 = nnz ? hipMemcpyAsync(ranks_out, r.ranks, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream)
@@ -7637,10 +7592,7 @@ int trlda_model_heldout_ranks(trlda_model *m, const trlda_batch *o, const trlda_
     hipError_t e4 = nnz && scores_out ? hipMemcpyAsync(scores_out, r.scores, nnz * sizeof(double),
                                                        hipMemcpyDeviceToHost, m->stream)
                                       : hipSuccess;
-    hipError_t e5 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
-    HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    return wait_for_results(m, {e1, e2, e3, e4});
 }
 
 }  // extern "C"
@@ -7910,15 +7862,13 @@ struct trlda_prevalence {
 
 namespace {
 
-int prevalence_checks(const trlda_prevalence *p, const trlda_batch *b)
+// what the per-document accumulators (prevalence, topic diagnostics) check of a batch before anything
+// is waited for or launched; m: the accumulator's model, nullptr for no accumulator
+int accumulator_checks(const trlda_model *m, const trlda_batch *b)
 {
-    if (!p || !b)
+    if (!m || !b)
         return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
-    if (b->V != p->model->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != p->model->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    return TRLDA_OK;
+    return batch_matches_model(m, b);
 }
 
 // the two passes over a batch that has been begun (B > 0), on the model's stream
@@ -7976,7 +7926,7 @@ int trlda_prevalence_create(trlda_model *m, int weight_by_length, trlda_prevalen
 
 int trlda_prevalence_add_dev(trlda_prevalence *p, const trlda_batch *b, const double *gamma_dev)
 {
-    if (int rc_arg = prevalence_checks(p, b))
+    if (int rc_arg = accumulator_checks(p ? p->model : nullptr, b))
         return rc_arg;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
@@ -7998,7 +7948,7 @@ int trlda_prevalence_add_dev(trlda_prevalence *p, const trlda_batch *b, const do
 // The E-step of trlda_model_estep_host on the batch, then the two passes with its gamma
 int trlda_prevalence_add(trlda_prevalence *p, const trlda_batch *b, double *gamma, int max_iter, double threshold)
 {
-    if (int rc_arg = prevalence_checks(p, b))
+    if (int rc_arg = accumulator_checks(p ? p->model : nullptr, b))
         return rc_arg;
     trlda_model *m = p->model;
     if (int rc_vi = check_vi(m))
@@ -8011,22 +7961,14 @@ int trlda_prevalence_add(trlda_prevalence *p, const trlda_batch *b, double *gamm
     int rc = check_model(m);
     if (rc || b->B <= 0)
         return rc;
-    rc = ensure_update_workspace(m, b->B);
-    if (rc)
-        return rc;
-    const size_t gbytes = (size_t)m->K * b->B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = prevalence_device(p, b, m->gamma);
     if (rc)
         return rc;
     (void)batch_end(m, b);
-    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, (size_t)m->K * b->B * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    return wait_for_results(m, {e1});
 }
 
 int trlda_prevalence_read(trlda_prevalence *p, double *prevalence_out, int64_t *num_docs)
@@ -8060,8 +8002,7 @@ int trlda_prevalence_destroy(trlda_prevalence *p)
 {
     if (!p)
         return TRLDA_OK;
-    if (p->model && use_device(p->model->device) == TRLDA_OK && p->model->stream)
-        (void)hipStreamSynchronize(p->model->stream);    // (its kernels may still read the buffers)
+    wait_before_delete(p->model);
     delete p;
     return TRLDA_OK;
 }
@@ -8176,17 +8117,6 @@ struct trlda_topicdiag {
 
 namespace {
 
-int topicdiag_checks(const trlda_topicdiag *p, const trlda_batch *b)
-{
-    if (!p || !b)
-        return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
-    if (b->V != p->model->V)
-        return fail(TRLDA_ERR_ARG, "batch was created for a different vocabulary size");
-    if (b->device != p->model->device)
-        return fail(TRLDA_ERR_ARG, "batch was created on another device");
-    return TRLDA_OK;
-}
-
 // the two passes over a batch that has been begun (B > 0), on the model's stream
 int topicdiag_device(trlda_topicdiag *p, const trlda_batch *b, const double *gamma_dev)
 {
@@ -8245,7 +8175,7 @@ int trlda_topicdiag_create(trlda_model *m, int weight_by_length, double high, do
 
 int trlda_topicdiag_add_dev(trlda_topicdiag *p, const trlda_batch *b, const double *gamma_dev)
 {
-    if (int rc_arg = topicdiag_checks(p, b))
+    if (int rc_arg = accumulator_checks(p ? p->model : nullptr, b))
         return rc_arg;
     // (the batches' indices are built on worker threads: trlda_batch_create)
     if (int rc_built = batch_wait(b))
@@ -8267,7 +8197,7 @@ int trlda_topicdiag_add_dev(trlda_topicdiag *p, const trlda_batch *b, const doub
 // The E-step of trlda_model_estep_host on the batch, then the two passes with its gamma
 int trlda_topicdiag_add(trlda_topicdiag *p, const trlda_batch *b, double *gamma, int max_iter, double threshold)
 {
-    if (int rc_arg = topicdiag_checks(p, b))
+    if (int rc_arg = accumulator_checks(p ? p->model : nullptr, b))
         return rc_arg;
     trlda_model *m = p->model;
     if (int rc_vi = check_vi(m))
@@ -8280,22 +8210,14 @@ int trlda_topicdiag_add(trlda_topicdiag *p, const trlda_batch *b, double *gamma,
     int rc = check_model(m);
     if (rc || b->B <= 0)
         return rc;
-    rc = ensure_update_workspace(m, b->B);
-    if (rc)
-        return rc;
-    const size_t gbytes = (size_t)m->K * b->B * sizeof(double);
-    m->gamma0_src = nullptr;                           // the caller's gamma, not one drawn ahead
-    HIP_TRY(hipMemcpyAsync(m->gamma, gamma, gbytes, hipMemcpyHostToDevice, m->stream));
-    rc = estep_device(m, b, m->gamma, m->sstats, max_iter, threshold, nullptr);
+    rc = estep_from_host(m, b, gamma, max_iter, threshold, nullptr);
     if (!rc) rc = topicdiag_device(p, b, m->gamma);
     if (rc)
         return rc;
     (void)batch_end(m, b);
-    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, gbytes, hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    hipError_t e1 = hipMemcpyAsync(gamma, m->gamma, (size_t)m->K * b->B * sizeof(double), hipMemcpyDeviceToHost,
+                                   m->stream);
+    return wait_for_results(m, {e1});
 }
 
 int trlda_topicdiag_read(trlda_topicdiag *p, double *tokens_out, double *entropy_out, int64_t *rank1_out,
@@ -8334,8 +8256,7 @@ int trlda_topicdiag_destroy(trlda_topicdiag *p)
 {
     if (!p)
         return TRLDA_OK;
-    if (p->model && use_device(p->model->device) == TRLDA_OK && p->model->stream)
-        (void)hipStreamSynchronize(p->model->stream);    // (its kernels may still read the buffers)
+    wait_before_delete(p->model);
     delete p;
     return TRLDA_OK;
 }
