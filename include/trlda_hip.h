@@ -778,6 +778,29 @@ int trlda_docindex_neighbors(trlda_docindex *index, double radius, const int64_t
                              int64_t *ids_out /* capacity, or NULL: count only */,
                              double *val_out /* capacity, or NULL */);
 
+/* One round's sweep of Boruvka's algorithm on the complete graph over the N indexed documents
+ * (csrc/mst_kernels.h): per document its lightest edge to a document of another component.
+ *   s(i, j), d(i, j)  as in trlda_docindex_neighbors, bit for bit
+ *   w(i, j)           fmax(d, fmax(core_host[i], core_host[j])), the mutual-reachability distance of
+ *                     HDBSCAN*; d itself with core_host NULL.  w(i, j) and w(j, i) are the same bits.
+ *   candidate         j of i iff comp_host[j] != comp_host[i] and j != i
+ *   best_out[i]       the first candidate of i in the order (w ascending, j ascending) -- for a fixed i the
+ *                     edge order (w, min(i, j), max(i, j)), a strict total order on the edges, so that
+ *                     joining every component along its lightest outgoing edge closes no cycle -- and
+ *                     weight_out[i] its w; -1 and +inf for a document without a candidate.
+ * The two arrays are uploaded, one kernel runs on the model's stream, the results are downloaded and the
+ * call waits once.  A workgroup takes trlda_docindex_set_slab_rows rows of the table (0: whole passes of
+ * 128 rows, sized so that the grid stays near 1024 workgroups); the result does not depend on it or on how
+ * the index was filled; two calls agree bitwise.  No atomics; nothing of size N x N exists.  Any K >= 1: no E-step runs.
+ * TRLDA_ERR_ARG, before anything is waited for, copied or launched: a NULL index, comp_host, best_out or
+ * weight_out, an empty index, more than INT_MAX documents; TRLDA_ERR_VALUE, with nothing changed: a core
+ * distance that is not finite or is negative.  Nothing is drawn; the index, lambda, alpha, the counters and
+ * the model's statistics are left alone; pending deferred statistics and stream lanes are settled first;
+ * the temporaries are the call's own.  No reference counterpart. */
+int trlda_docindex_mst_sweep(trlda_docindex *index, const int32_t *comp_host /* N */,
+                             const double *core_host /* N or NULL */, int64_t *best_out /* N */,
+                             double *weight_out /* N */);
+
 /* A 2-D map of an indexed corpus: exact t-SNE (van der Maaten & Hinton 2008) on the stored rows
  * (csrc/tsne_kernels.h).  No reference counterpart.  Every call below checks its
  * arguments before anything is waited for, copied or launched (TRLDA_ERR_ARG; TRLDA_ERR_VALUE for

@@ -204,6 +204,7 @@ _SIGNATURES = {
                                          C.POINTER(C.c_int)]),
     "trlda_docindex_silhouette": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, vp]),
     "trlda_docindex_neighbors": (C.c_int, [vp, C.c_double, vp, vp, C.c_int64, C.c_int, C.c_int64, vp, vp, vp]),
+    "trlda_docindex_mst_sweep": (C.c_int, [vp, vp, vp, vp, vp]),
     "trlda_docindex_nearest": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "trlda_docindex_affinities": (C.c_int, [vp, C.c_double, C.c_int, vp, vp, vp]),
     "trlda_docindex_set_tsne_tile": (C.c_int, [vp, C.c_int]),

@@ -63,6 +63,7 @@
 #include "cluster_kernels.h"
 #include "silhouette_kernels.h"
 #include "neighbors_kernels.h"
+#include "mst_kernels.h"
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
 #include "diagnostics_kernels.h"
@@ -6883,6 +6884,61 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
     hipError_t e2 = val_out ? hipMemcpyAsync(val_out, hit_val, (size_t)total * sizeof(double), hipMemcpyDeviceToHost,
                                              stream)
                             : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- the minimum spanning tree of an indexed corpus (csrc/mst_kernels.h) ----
+
+extern "C" {
+
+int trlda_docindex_mst_sweep(trlda_docindex *x, const int32_t *comp_host, const double *core_host, int64_t *best_out,
+                             double *weight_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, components int32");
+    if (!x || !comp_host || !best_out || !weight_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / components / best / weight");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (x->n > INT_MAX)                                  // (the kernel's columns are ints)
+        return fail(TRLDA_ERR_ARG, "too many indexed documents for a spanning tree");
+    // the slab: the A/B switch, else the default for this size (the 2048 rows of a search would leave
+    // most of the device without a workgroup: here the rows are the whole table)
+    const int N = (int)x->n, sr = x->slab_rows > 0 ? x->slab_rows : (int)trlda::mst_default_slab(N);
+    const long long slabs = ((long long)N + sr - 1) / sr;
+    if (core_host)
+        for (int i = 0; i < N; ++i)
+            if (!(core_host[i] >= 0.0) || !std::isfinite(core_host[i]))
+                return fail(TRLDA_ERR_VALUE, "a core distance should be finite and not negative");
+    trlda_model *m = x->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<int> comp;
+    DevBuf<double> core, weight;
+    DevBuf<long long> best;
+    if ((rc = comp.alloc((size_t)N)) || (rc = weight.alloc((size_t)N)) || (rc = best.alloc((size_t)N)))
+        return rc;
+    if (core_host && (rc = core.alloc((size_t)N)))
+        return rc;
+    const size_t lds = trlda::mst_sweep_lds();
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::mst_sweep_kernel), lds)))
+        return rc;
+    // (comp_host and core_host live until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(comp, comp_host, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (core_host)
+        HIP_TRY(hipMemcpyAsync(core, core_host, (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(trlda::mst_sweep_kernel, dim3((unsigned)slabs), dim3(trlda::kMstThreads), lds, stream, x->Kp, N,
+                       sr, x->measure, x->rows.get(), comp.get(), core_host ? core.get() : (const double *)nullptr,
+                       best.get(), weight.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(best_out, best, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(weight_out, weight, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e3 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());

@@ -7,7 +7,8 @@ the indexed documents that best explain a query's words (csrc/querylik_kernels.h
 the document groups of the indexed corpus (csrc/cluster_kernels.h), their
 silhouettes (csrc/silhouette_kernels.h), and the radius join -- the documents within
 a distance of each document -- with the density-based groups built on it (csrc/neighbors_kernels.h,
-DESIGN.md 3.29).
+DESIGN.md 3.29), and the minimum spanning tree of the indexed corpus with the single-linkage hierarchy
+and HDBSCAN* on it (csrc/mst_kernels.h).
 No counterpart in the reference package.
 """
 import ctypes as C
@@ -567,6 +568,142 @@ class DocumentIndex(object):
             first = last
         return _dbscan_labels(parent, core, nearest, return_core)
 
+    # -- the spanning tree (csrc/mst_kernels.h) --------------------------------------
+    def _min_samples(self, min_samples, N):
+        min_samples = operator.index(min_samples)
+        if not 1 <= min_samples <= min(N, MAX_TOP_N):
+            raise RuntimeError("`min_samples` should lie between 1 and min(len(index), %d)." % MAX_TOP_N)
+        return min_samples
+
+    def _sweep(self, comp, core):
+        """One sweep on the device: per document its lightest edge to another component, ``(best_j,
+        best_w)``, int64 (-1: none) and float64."""
+        N = comp.shape[0]
+        best_j = np.empty(N, dtype=np.int64)
+        best_w = np.empty(N, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_mst_sweep(self._live(), comp.ctypes.data,
+                                                       None if core is None else core.ctypes.data,
+                                                       best_j.ctypes.data, best_w.ctypes.data))
+        return best_j, best_w
+
+    def spanning_tree(self, min_samples=1, return_core=False):
+        """The minimum spanning tree of the complete graph on the indexed documents.  With
+        ``min_samples=1`` the weight of the edge (i, j) is the index's own distance ``d(i, j)`` -- the
+        tree of single linkage; with ``min_samples >= 2`` it is the mutual-reachability distance of
+        HDBSCAN* (Campello, Moulavi & Sander 2013), ``max(d(i, j), core[i], core[j])``, where
+        ``core[i]`` is the distance to document i's (min_samples - 1)-th nearest other document
+        (``nearest_neighbors(min_samples - 1)``): the document itself counts as the first of its
+        neighbourhood, as in ``dbscan`` and scikit-learn.  ``1 <= min_samples <= min(len(index),
+        100)``, else RuntimeError.
+
+        Returns ``(u, v, w)``: int64, int64 and float64 of length N - 1 with ``u < v``, the edges sorted
+        by ``(w, u, v)`` (one document: three empty arrays); with ``return_core=True`` also the core
+        distances, float64 of length N (zeros for ``min_samples=1``).  Edges are compared in that
+        same order, a strict total one since ``d(i, j)`` and ``d(j, i)`` are the same bits, so the
+        tree is THE minimum spanning tree under it: equal weights, which mutual reachability makes
+        in bulk, leave no choice.
+
+        Boruvka's algorithm: every round one sweep on the device finds each document's lightest edge
+        to another component (nothing of size N x N exists), the host joins every component along its
+        lightest such edge; at most ceil(log2 N) rounds.  The result does not depend on
+        ``set_slab_rows`` or on how the index was filled, and two calls agree bitwise.  Nothing is
+        drawn."""
+        self._live()
+        N = self._size()
+        min_samples = self._min_samples(min_samples, N)
+        core = None
+        if min_samples > 1:
+            core = np.ascontiguousarray(self.nearest_neighbors(min_samples - 1)[1][:, -1])
+        parent = np.arange(N, dtype=np.int64)
+        comp = np.arange(N, dtype=np.int32)
+        parts, left = [], N
+        for _ in range(max(N - 1, 0).bit_length()):         # ceil(log2 N) rounds
+            if left == 1:
+                break
+            lo, hi, w = _boruvka_edges(comp, *self._sweep(comp, core))
+            parts.append((lo, hi, w))
+            _union(parent, lo, hi)
+            comp = _roots(parent).astype(np.int32)           # (a tree's root is its smallest member)
+            left = len(np.unique(comp))
+        tree = _sorted_edges(parts)
+        if left != 1 or len(tree[0]) != N - 1:
+            raise RuntimeError("internal error: the spanning tree did not close in ceil(log2 N) rounds.")
+        if return_core:
+            return tree + (np.zeros(N, dtype=np.float64) if core is None else core,)
+        return tree
+
+    def single_linkage(self, min_samples=1):
+        """The single-linkage hierarchy of the indexed documents from ``spanning_tree(min_samples)``, as
+        the (N - 1) x 4 float64 linkage matrix of SciPy: row t merges the clusters ``Z[t, 0] <
+        Z[t, 1]`` at height ``Z[t, 2]``, the tree's t-th edge weight, into cluster N + t of
+        ``Z[t, 3]`` documents; the merges are in the tree's edge order.
+        ``scipy.cluster.hierarchy.dendrogram`` and ``fcluster`` take it as it is, ``cut_linkage``
+        cuts it."""
+        N = self._size()
+        return _linkage(*self.spanning_tree(min_samples), N)
+
+    @staticmethod
+    def cut_linkage(Z, num_clusters=None, distance=None):
+        """The flat groups of a linkage matrix ``Z`` (N - 1 rows): with ``num_clusters`` after its first
+        N - num_clusters merges, with ``distance`` after every merge of height ``<= distance``;
+        exactly one of the two, else ValueError.  Returns int32 labels of length N, numbered from 0
+        by ascending smallest member id, as ``dbscan`` numbers its clusters."""
+        if (num_clusters is None) == (distance is None):
+            raise ValueError("Give exactly one of `num_clusters` and `distance`.")
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != 4:
+            raise ValueError("`Z` should be a linkage matrix of four columns.")
+        N = Z.shape[0] + 1
+        if num_clusters is not None:
+            num_clusters = operator.index(num_clusters)
+            if not 1 <= num_clusters <= N:
+                raise ValueError("`num_clusters` should lie between 1 and %d." % N)
+            merges = N - num_clusters
+        else:
+            distance = float(distance)
+            if math.isnan(distance):
+                raise ValueError("`distance` should be a number.")
+            merges = int(np.count_nonzero(Z[:, 2] <= distance))
+            if np.any(Z[merges:, 2] <= distance):
+                raise ValueError("`Z` should hold its merges in ascending height.")
+        return _cut(Z, merges)
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, selection="eom", allow_single_cluster=False,
+                return_info=False):
+        """Density-based groups of the indexed documents that need no radius (HDBSCAN*; Campello,
+        Moulavi & Sander 2013), from ``spanning_tree(min_samples)`` under mutual reachability:
+        the single-linkage hierarchy of that tree is condensed -- walking it from the top with
+        ``lambda = 1 / max(w, 2 ** -52)``, a split is *true* when both sides hold at least
+        ``min_cluster_size`` documents and starts two new clusters; otherwise the documents of a side
+        that is too small leave the cluster at that lambda and the cluster goes on -- each cluster
+        gets the stability ``sum over its documents of (lambda_leave - lambda_birth)``, and the
+        clusters are selected by ``'eom'`` (excess of mass: a cluster is kept when its stability is at
+        least the sum of the best below it) or ``'leaf'`` (the leaves of the condensed tree).  Equal
+        weights split one edge at a time in the tree's edge order.  The root is selected only with
+        ``allow_single_cluster=True``.
+
+        ``min_samples=None`` means ``min_cluster_size``, capped by ``spanning_tree``'s limit
+        ``min(len(index), 100)``.  ``min_cluster_size >= 2``, else ValueError.  A weight below one ulp
+        of 1 is the rounding of equal rows (see ``neighbors_within``), hence the floor of lambda.
+
+        Returns int32 labels, -1 for noise, the clusters numbered from 0 by ascending smallest member
+        id; every document that was in a selected cluster at its birth carries its label.  With
+        ``return_info=True`` also a dict: ``probabilities`` (float64, N: lambda of the document over the
+        largest lambda of its cluster, 0 for noise), ``stabilities`` (float64, one per returned
+        cluster) and ``tree``, the ``(u, v, w)`` used.  The tree comes from the device, the rest is
+        host arithmetic."""
+        self._live()
+        min_cluster_size, selection = _hdbscan_arguments(min_cluster_size, selection)
+        N = self._size()
+        if min_samples is None:
+            min_samples = min(min_cluster_size, N, MAX_TOP_N)
+        min_samples = self._min_samples(min_samples, N)
+        tree = self.spanning_tree(min_samples)
+        labels, prob, stab = _hdbscan_labels(*tree, N, min_cluster_size, selection, allow_single_cluster)
+        if not return_info:
+            return labels
+        return labels, {"probabilities": prob, "stabilities": stab, "tree": tree}
+
     # -- the map (csrc/tsne_kernels.h, DESIGN.md 3.32) ----------------------------------------------
     def set_tsne_tile(self, rows):
         """A/B switch: rows per workgroup of the map's repulsion kernel (0: default).  Results do not
@@ -879,6 +1016,182 @@ def _dbscan_labels(parent, core, nearest, return_core=False):
     border = np.flatnonzero(nearest >= 0)
     labels[border] = labels[nearest[border]]
     return (labels, core) if return_core else labels
+
+
+def _boruvka_edges(comp, best_j, best_w):
+    """One round of Boruvka's algorithm on the host: from every document's lightest edge to another
+    component (``best_j``, -1 without one, and its weight) each component's lightest in the order
+    (w, lo, hi), an edge chosen from both of its ends kept once.  Returns ``(lo, hi, w)``."""
+    N = comp.shape[0]
+    rows = np.flatnonzero(best_j >= 0)
+    if not len(rows):
+        return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+    j = best_j[rows]
+    lo, hi, w, c = np.minimum(rows, j), np.maximum(rows, j), best_w[rows], comp[rows]
+    order = np.lexsort((hi, lo, w, c))
+    c = c[order]
+    pick = order[np.concatenate(([True], c[1:] != c[:-1]))]
+    once = np.unique(lo[pick] * N + hi[pick], return_index=True)[1]
+    pick = pick[once]
+    return lo[pick], hi[pick], w[pick]
+
+
+def _sorted_edges(parts):
+    """The rounds' edges as one ``(u, v, w)`` sorted by (w, u, v)."""
+    if not parts:
+        return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+    u, v, w = (np.concatenate(p) for p in zip(*parts))
+    order = np.lexsort((v, u, w))
+    return u[order].astype(np.int64), v[order].astype(np.int64), w[order].astype(np.float64)
+
+
+def _linkage(u, v, w, N):
+    """The linkage matrix (N - 1 x 4, SciPy's convention) of the spanning tree ``(u, v, w)`` on N
+    documents: the edges in the order (w, u, v), edge t joining the clusters of its two ends into
+    cluster N + t.  One pass of union-find over the N - 1 edges; an edge list that is no spanning tree
+    is a ValueError."""
+    u, v, w = np.asarray(u, dtype=np.int64), np.asarray(v, dtype=np.int64), np.asarray(w, dtype=np.float64)
+    if not (u.shape == v.shape == w.shape == (N - 1,)):
+        raise ValueError("A spanning tree of %d documents has %d edges." % (N, N - 1))
+    if N > 1 and (min(u.min(), v.min()) < 0 or max(u.max(), v.max()) >= N):
+        raise ValueError("An edge names a document outside [0, %d)." % N)
+    lo, hi = np.minimum(u, v), np.maximum(u, v)
+    order = np.lexsort((hi, lo, w))
+    top = list(range(2 * N - 1))                             # union-find over the clusters, path halving
+    size = [1] * N + [0] * (N - 1)
+    Z = np.empty((N - 1, 4), dtype=np.float64)
+    for t, (a, b, h) in enumerate(zip(lo[order].tolist(), hi[order].tolist(), w[order].tolist())):
+        while top[a] != a:
+            top[a] = top[top[a]]
+            a = top[a]
+        while top[b] != b:
+            top[b] = top[top[b]]
+            b = top[b]
+        if a == b:
+            raise ValueError("The edges close a cycle: not a spanning tree.")
+        top[a] = top[b] = N + t
+        size[N + t] = size[a] + size[b]
+        Z[t] = (min(a, b), max(a, b), h, size[N + t])
+    return Z
+
+
+def _numbered(keys):
+    """(labels, kept): int32 labels of the keys -- the distinct keys >= 0 numbered from 0 by ascending
+    first position, which is the smallest member id, a negative key -1 -- and the keys in label order."""
+    keys = np.asarray(keys, dtype=np.int64)
+    labels = np.full(len(keys), -1, dtype=np.int32)
+    at = np.flatnonzero(keys >= 0)
+    if not len(at):
+        return labels, np.empty(0, dtype=np.int64)
+    uniq, first, inv = np.unique(keys[at], return_index=True, return_inverse=True)
+    by_first = np.argsort(first)
+    rank = np.empty(len(uniq), dtype=np.int32)
+    rank[by_first] = np.arange(len(uniq), dtype=np.int32)
+    labels[at] = rank[inv.reshape(-1)]
+    return labels, uniq[by_first]
+
+
+def _cut(Z, merges):
+    """The labels after the first ``merges`` merges of the linkage matrix Z."""
+    N = Z.shape[0] + 1
+    parent = np.arange(2 * N - 1, dtype=np.int64)
+    new = N + np.arange(merges, dtype=np.int64)
+    parent[Z[:merges, 0].astype(np.int64)] = new
+    parent[Z[:merges, 1].astype(np.int64)] = new
+    return _numbered(_roots(parent)[:N])[0]
+
+
+def _hdbscan_arguments(min_cluster_size, selection):
+    min_cluster_size = operator.index(min_cluster_size)
+    if min_cluster_size < 2:
+        raise ValueError("`min_cluster_size` should be at least 2.")
+    if selection not in ("eom", "leaf"):
+        raise ValueError("`selection` should be 'eom' or 'leaf'.")
+    return min_cluster_size, selection
+
+
+LAMBDA_FLOOR = 2.0 ** -52                    # weights below one ulp of 1 are the rounding of equal rows
+
+
+def _condense(Z, N, min_cluster_size):
+    """The condensed tree of the linkage matrix Z (N >= 2), walked from the root down, parents before
+    children.  Cluster 0 is the root, born at lambda 0.  At a node of height w, ``lambda = 1 /
+    max(w, 2 ** -52)``: two sides of at least ``min_cluster_size`` documents start two new clusters
+    born at lambda; otherwise a side that is too small leaves the cluster at lambda, all its
+    documents with it, and the other side carries the cluster on.  Returns ``(cluster, lam)`` per
+    document -- the cluster it left and the lambda it left at -- and per cluster ``(parent, birth,
+    size)``, children after parents."""
+    left, right = Z[:, 0].astype(np.int64).tolist(), Z[:, 1].astype(np.int64).tolist()
+    lam = (1.0 / np.maximum(Z[:, 2], LAMBDA_FLOOR)).tolist()
+    size = [1] * N + Z[:, 3].astype(np.int64).tolist()
+    own = [0] * (2 * N - 1)                                  # the cluster a node lies in
+    gone = [False] * (2 * N - 1)                             # has the node left it, and at which lambda
+    out = [0.0] * (2 * N - 1)
+    cparent, birth, csize = [-1], [0.0], [N]
+    for t in range(N - 2, -1, -1):
+        node = N + t
+        c, a, b = own[node], left[t], right[t]
+        if gone[node]:
+            for ch in (a, b):
+                own[ch], gone[ch], out[ch] = c, True, out[node]
+        elif size[a] >= min_cluster_size and size[b] >= min_cluster_size:
+            for ch in (a, b):
+                own[ch] = len(cparent)
+                cparent.append(c)
+                birth.append(lam[t])
+                csize.append(size[ch])
+        else:
+            for ch in (a, b):
+                own[ch] = c
+                if size[ch] < min_cluster_size:
+                    gone[ch], out[ch] = True, lam[t]
+    return (np.array(own[:N], dtype=np.int64), np.array(out[:N], dtype=np.float64),
+            np.array(cparent, dtype=np.int64), np.array(birth, dtype=np.float64), np.array(csize, dtype=np.int64))
+
+
+def _hdbscan_labels(u, v, w, N, min_cluster_size, selection="eom", allow_single_cluster=False):
+    """The closing arithmetic of ``hdbscan``: the spanning tree ``(u, v, w)`` under mutual reachability
+    in, ``(labels int32, probabilities, stabilities)`` out; no device is needed."""
+    min_cluster_size, selection = _hdbscan_arguments(min_cluster_size, selection)
+    if N == 1:
+        if allow_single_cluster:
+            return np.zeros(1, dtype=np.int32), np.ones(1), np.zeros(1)
+        return np.full(1, -1, dtype=np.int32), np.zeros(1), np.zeros(0)
+    cluster, lam, cparent, birth, csize = _condense(_linkage(u, v, w, N), N, min_cluster_size)
+    C = len(cparent)
+    kids = np.arange(1, C)
+    # sum over a cluster's documents of lambda_leave - lambda_birth: those that left it, and those that
+    # went on into its two children at the children's birth
+    stab = np.bincount(cluster, weights=lam - birth[cluster], minlength=C)
+    stab += np.bincount(cparent[kids], weights=csize[kids] * (birth[kids] - birth[cparent[kids]]), minlength=C)
+    split = np.zeros(C, dtype=bool)
+    split[cparent[kids]] = True
+    if selection == "leaf":
+        chosen = ~split
+    else:
+        chosen = np.ones(C, dtype=bool)
+        best, below = stab.tolist(), [0.0] * C               # the best of a subtree; the sum over the children
+        for c in range(C - 1, -1, -1):
+            if split[c] and below[c] > best[c]:
+                chosen[c], best[c] = False, below[c]
+            if c:
+                below[cparent[c]] += best[c]
+    if not allow_single_cluster:
+        chosen[0] = False
+    # a document carries the topmost chosen cluster above the one it left
+    rep = np.full(C, -1, dtype=np.int64)
+    for c in range(C):
+        above = rep[cparent[c]] if c else -1
+        rep[c] = above if above >= 0 else (c if chosen[c] else -1)
+    keys = rep[cluster]
+    labels, kept = _numbered(keys)
+    prob = np.zeros(N, dtype=np.float64)
+    at = np.flatnonzero(keys >= 0)
+    peak = np.zeros(C, dtype=np.float64)
+    np.maximum.at(peak, keys[at], lam[at])
+    ok = at[peak[keys[at]] > 0.0]
+    prob[ok] = lam[ok] / peak[keys[ok]]
+    return labels, prob, stab[kept]
 
 
 def _correlation(scatter):
