@@ -859,6 +859,56 @@ int trlda_docindex_tsne_run(trlda_docindex *index, const int64_t *indptr, const 
                             double early_exaggeration, double learning_rate, double momentum0, double momentum1,
                             double *kl_out /* num_iterations */);
 
+/* Topic prevalence against what the caller knows about the indexed documents (csrc/effects_kernels.h,
+ * DESIGN.md 3.34): the weighted mean and variance of theta^ per group of a labelling, and the parts of
+ * the least-squares regression of theta^ (N x K) on a design matrix.  theta^ is recovered from the stored
+ * rows as trlda_docindex_topic_documents recovers it.  Every + - x / is one rounded fp64 operation and
+ * nothing is atomic in floating point: two calls agree bitwise, whatever trlda_docindex_set_slab_rows
+ * says and however the index was filled.  weights_host (N, or NULL: every weight 1, and no multiply by
+ * it) holds finite values >= 0.  TRLDA_ERR_ARG, before anything is waited for, copied or launched: a NULL
+ * index, input or required output, an empty index, G outside [1, TRLDA_CLUSTER_MAX_CLUSTERS - 1], P
+ * outside [1, TRLDA_EFFECTS_MAX_COLUMNS (256)]; TRLDA_ERR_VALUE, likewise (checked on the host): a label
+ * outside [-1, G), a weight that is negative or not finite, a design or coefficient value that is not
+ * finite.  A failed call leaves its outputs untouched.  Nothing is drawn; the index, lambda, alpha, the
+ * counters and the model's statistics are left alone; pending deferred statistics and stream lanes are
+ * settled first; the temporaries, the uploaded design and weights among them, are the call's own.  Each
+ * call runs on the model's stream and synchronises once.
+ *
+ * The groups.  labels_host (int32, N) holds values in [-1, G); -1 leaves a document out.  The ids are
+ * sorted by label with the stable counting sort of trlda_docindex_cluster (the left-out documents take
+ * the slot past the last group); a group's members are taken in chunks of 256 in ascending id, the terms
+ * of a chunk are added one after the other from 0.0, the chunk sums in ascending order, then one
+ * division:
+ *   mean_out[k + K g]   S_gk / W_g,  S_gk = sum_{d in g} w_d theta^_dk,  W_g = sum w_d (wsum_out[g]; without
+ *                       weights the member count); NaN where W_g = 0
+ *   ss_out[k + K g]     sum_{d in g} (w_d q) q,  q = theta^_dk - mean_gk (unless NULL; no division)
+ *   count_out[g]        the members of g (int64), whatever their weights
+ * A group's column depends on its members' rows, their weights and K alone -- not on the other groups,
+ * their numbering or G.  No reference counterpart. */
+int trlda_docindex_group_moments(trlda_docindex *index, const int32_t *labels_host /* N */, int G,
+                                 const double *weights_host /* N or NULL */, double *mean_out /* K x G */,
+                                 double *wsum_out /* G */, int64_t *count_out /* G */,
+                                 double *ss_out /* K x G, may be NULL */);
+/* gram_out (P x P, bitwise symmetric) = Z^T W Z and cross_out (P x K row-major) = Z^T W Theta^ of the
+ * design z_host (N x P row-major, one row per indexed document in id order; an intercept is a column of
+ * ones the caller adds).  64 x 64 tiles on v_mfma_f64_16x16x4_f64: the left operand is w_d z_dp (one
+ * multiply), the right one z_dq or theta^_dk; N is cut into chunks of rows (a function of (P, K, N)
+ * alone, or what trlda_docindex_set_moment_chunk forces: results then agree within rounding), every
+ * element of a chunk is one chain of MFMAs over ascending rows, and the chunks' partial sums are added
+ * in ascending order.  No reference counterpart. */
+int trlda_docindex_regress_products(trlda_docindex *index, const double *z_host /* N x P row-major */, int P,
+                                    const double *weights_host /* N or NULL */, double *gram_out /* P x P */,
+                                    double *cross_out /* P x K */);
+/* rss_out[k] = sum_d w_d (theta^_dk - sum_p z_dp b_pk)^2 with the coefficients coef_host (K rows of P:
+ * b_pk at [k * P + p]), formed explicitly: fit is one chain of ceil(P / 4) MFMAs from +0 per (document,
+ * topic) over ascending p, r = theta^ - fit, the term (w r) r; the terms of each fixed block of 64
+ * documents are added in ascending document order from 0.0, the blocks in ascending order.  Nothing of
+ * size N x K is written.  The total sum of squares about the weighted means is this call on the
+ * one-column design of ones.  No reference counterpart. */
+int trlda_docindex_regress_residuals(trlda_docindex *index, const double *z_host /* N x P row-major */, int P,
+                                     const double *weights_host /* N or NULL */,
+                                     const double *coef_host /* K x P row-major */, double *rss_out /* K */);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

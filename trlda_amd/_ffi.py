@@ -212,6 +212,9 @@ _SIGNATURES = {
     "trlda_docindex_tsne_gradient": (C.c_int, [vp, vp, vp, vp, vp, C.c_double, vp, vp]),
     "trlda_docindex_tsne_run": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                           C.c_double, C.c_double, vp]),
+    "trlda_docindex_group_moments": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    "trlda_docindex_regress_products": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "trlda_docindex_regress_residuals": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

@@ -64,6 +64,7 @@
 #include "silhouette_kernels.h"
 #include "neighbors_kernels.h"
 #include "mst_kernels.h"
+#include "effects_kernels.h"
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
 #include "diagnostics_kernels.h"
@@ -6941,6 +6942,255 @@ int trlda_docindex_mst_sweep(trlda_docindex *x, const int32_t *comp_host, const 
     hipError_t e2 = hipMemcpyAsync(weight_out, weight, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e3 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- topic prevalence against document metadata (csrc/effects_kernels.h) ----
+
+namespace {
+
+// weights on the host: finite and not negative, or TRLDA_ERR_VALUE
+int effects_check_weights(const double *weights, long long N)
+{
+    if (weights)
+        for (long long d = 0; d < N; ++d)
+            if (!(weights[d] >= 0.0) || !std::isfinite(weights[d]))
+                return fail(TRLDA_ERR_VALUE, "a weight should be finite and not negative");
+    return TRLDA_OK;
+}
+
+// `rows` rows of P doubles as rows of Pp = ceil(P / 4) * 4 doubles, the tail zero: src itself where
+// P = Pp, else a copy in `pad`; finite, or TRLDA_ERR_VALUE
+int effects_padded_rows(const double *src, long long rows, int P, int Pp, std::vector<double> &pad,
+                        const double **out, const char *what)
+{
+    const size_t count = (size_t)rows * P;
+    for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(src[i]))
+            return fail(TRLDA_ERR_VALUE, std::string(what) + " should be finite");
+    *out = src;
+    if (P == Pp)
+        return TRLDA_OK;
+    pad.assign((size_t)rows * Pp, 0.0);
+    for (long long d = 0; d < rows; ++d)
+        std::copy(src + (size_t)d * P, src + (size_t)(d + 1) * P, pad.begin() + (size_t)d * Pp);
+    *out = pad.data();
+    return TRLDA_OK;
+}
+
+// The uploads of a regression call on the model's stream: the padded design (N rows of Pp doubles), and
+// the weights if any.  (The host arrays live until the call's synchronisation.)
+int effects_upload(trlda_docindex *x, const double *zpad, int Pp, const double *weights_host, DevBuf<double> &z,
+                   DevBuf<double> &w)
+{
+    const size_t count = (size_t)x->n * Pp;
+    int rc = z.alloc(count);
+    if (!rc && weights_host)
+        rc = w.alloc((size_t)x->n);
+    if (rc)
+        return rc;
+    hipStream_t stream = x->model->stream;
+    HIP_TRY(hipMemcpyAsync(z, zpad, count * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (weights_host)
+        HIP_TRY(hipMemcpyAsync(w, weights_host, (size_t)x->n * sizeof(double), hipMemcpyHostToDevice, stream));
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_group_moments(trlda_docindex *x, const int32_t *labels_host, int G, const double *weights_host,
+                                 double *mean_out, double *wsum_out, int64_t *count_out, double *ss_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, labels int32");
+    if (!x || !labels_host || !mean_out || !wsum_out || !count_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / labels / mean / weight sums / counts");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (G < 1 || G > trlda::kClusterMaxClusters - 1)
+        return fail(TRLDA_ERR_ARG, "the number of groups must lie in [1, " +
+                                       std::to_string(trlda::kClusterMaxClusters - 1) + "]");
+    const int K = x->K, C = G + 1;                       // (slot G: the documents left out)
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    const long long chunks = trlda::cluster_max_chunks(N, C);
+    const size_t cells = (size_t)K * G;
+    const size_t fblocks = (cells + trlda::kEffectsThreads - 1) / trlda::kEffectsThreads;
+    if (nb > INT_MAX || chunks > INT_MAX || fblocks > (size_t)INT_MAX)   // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many rows or groups for one call");
+    // the labels, counted on the host; -1 takes the slot past the last group
+    std::vector<int32_t> lab((size_t)N);
+    std::vector<int64_t> members((size_t)G, 0);
+    for (long long d = 0; d < N; ++d) {
+        const int32_t l = labels_host[d];
+        if (l < -1 || l >= G)
+            return fail(TRLDA_ERR_VALUE, "a label lies outside [-1, G)");
+        lab[(size_t)d] = l < 0 ? G : l;
+        if (l >= 0)
+            ++members[(size_t)l];
+    }
+    int rc = effects_check_weights(weights_host, N);
+    if (rc)
+        return rc;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<int> label, count;
+    DevBuf<long long> off, start, size, cstart, order;
+    DevBuf<double> scale, w, part, wpart, mean, wsum, ss;
+    if ((rc = label.alloc((size_t)N)) || (rc = count.alloc((size_t)C * nb)) || (rc = off.alloc((size_t)C * nb)) ||
+        (rc = start.alloc(C)) || (rc = size.alloc(C)) || (rc = cstart.alloc((size_t)C + 1)) ||
+        (rc = order.alloc((size_t)N)) || (rc = topicdocs_scale(x, scale)) || (rc = part.alloc((size_t)chunks * K)) ||
+        (rc = wpart.alloc((size_t)chunks)) || (rc = mean.alloc(cells)) || (rc = wsum.alloc(G)))
+        return rc;
+    if (weights_host && (rc = w.alloc((size_t)N)))
+        return rc;
+    if (ss_out && (rc = ss.alloc(cells)))
+        return rc;
+    // (lab and weights_host live until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(label, lab.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (weights_host)
+        HIP_TRY(hipMemcpyAsync(w, weights_host, (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
+    const double *wd = weights_host ? w.get() : (const double *)nullptr;
+    // the stable counting sort of cluster_kernels.h, launched as trlda_docindex_silhouette launches it
+    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
+                       (size_t)C * sizeof(int), stream, N, C, nb, label.get(), count.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::cluster_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, N, C, nb,
+                       count.get(), off.get(), start.get(), size.get(), cstart.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
+                       (size_t)C * sizeof(long long), stream, N, C, nb, label.get(), off.get(), order.get());
+    HIP_TRY(hipGetLastError());
+    const dim3 block(trlda::kEffectsThreads);
+    hipLaunchKernelGGL(trlda::effects_group_kernel<false>, dim3((unsigned)chunks), block, 0, stream, K, x->Kp, G,
+                       x->measure, x->rows.get(), scale.get(), wd, order.get(), start.get(), size.get(), cstart.get(),
+                       (const double *)nullptr, part.get(), wpart.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::effects_group_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, K, G, 1,
+                       cstart.get(), part.get(), wpart.get(), mean.get(), wsum.get());
+    HIP_TRY(hipGetLastError());
+    if (ss_out) {
+        hipLaunchKernelGGL(trlda::effects_group_kernel<true>, dim3((unsigned)chunks), block, 0, stream, K, x->Kp, G,
+                           x->measure, x->rows.get(), scale.get(), wd, order.get(), start.get(), size.get(),
+                           cstart.get(), mean.get(), part.get(), wpart.get());
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(trlda::effects_group_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, K, G, 0,
+                           cstart.get(), part.get(), wpart.get(), ss.get(), wsum.get());
+        HIP_TRY(hipGetLastError());
+    }
+    hipError_t e1 = hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(wsum_out, wsum, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = ss_out ? hipMemcpyAsync(ss_out, ss, cells * sizeof(double), hipMemcpyDeviceToHost, stream)
+                           : hipSuccess;
+    hipError_t e4 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    HIP_TRY(hipGetLastError());
+    std::copy(members.begin(), members.end(), count_out);
+    return TRLDA_OK;
+}
+
+int trlda_docindex_regress_products(trlda_docindex *x, const double *z_host, int P, const double *weights_host,
+                                    double *gram_out, double *cross_out)
+{
+    if (!x || !z_host || !gram_out || !cross_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / design / Gram / cross products");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (P < 1 || P > trlda::kEffectsMaxColumns)
+        return fail(TRLDA_ERR_ARG, "the number of design columns must lie in [1, " +
+                                       std::to_string(trlda::kEffectsMaxColumns) + "]");
+    const int K = x->K, Pp = (P + 3) / 4 * 4;
+    const long long N = x->n;
+    const long long cr = x->moment_chunk > 0 ? x->moment_chunk : trlda::effects_chunk_rows(P, K, N);
+    const long long chunks = (N + cr - 1) / cr, items = trlda::effects_product_items(P, K);
+    const size_t ng = (size_t)P * P, nc = (size_t)P * K;
+    const size_t fblocks = (ng + nc + trlda::kEffectsThreads - 1) / trlda::kEffectsThreads;
+    if (chunks > 65535 || items > INT_MAX || fblocks > (size_t)INT_MAX)   // (grid dimensions y, x)
+        return fail(TRLDA_ERR_ARG, "too many topics or chunks of rows: raise trlda_docindex_set_moment_chunk");
+    int rc = effects_check_weights(weights_host, N);
+    if (rc)
+        return rc;
+    std::vector<double> zcopy;
+    const double *zpad = nullptr;
+    if ((rc = effects_padded_rows(z_host, N, P, Pp, zcopy, &zpad, "the design matrix")))
+        return rc;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<double> z, w, scale, part_g, part_c, gram, cross;
+    if ((rc = effects_upload(x, zpad, Pp, weights_host, z, w)) || (rc = topicdocs_scale(x, scale)) ||
+        (rc = part_g.alloc((size_t)chunks * ng)) || (rc = part_c.alloc((size_t)chunks * nc)) ||
+        (rc = gram.alloc(ng)) || (rc = cross.alloc(nc)))
+        return rc;
+    const dim3 block(trlda::kEffectsThreads);
+    hipLaunchKernelGGL(trlda::effects_products_kernel, dim3((unsigned)items, (unsigned)chunks), block, 0, stream, P,
+                       Pp, K, x->Kp, N, cr, x->measure, z.get(), weights_host ? w.get() : (const double *)nullptr,
+                       x->rows.get(), scale.get(), part_g.get(), part_c.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::effects_products_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, P, K,
+                       (int)chunks, part_g.get(), part_c.get(), gram.get(), cross.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(gram_out, gram, ng * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(cross_out, cross, nc * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, int P, const double *weights_host,
+                                     const double *coef_host, double *rss_out)
+{
+    if (!x || !z_host || !coef_host || !rss_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / design / coefficients / residual sums");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (P < 1 || P > trlda::kEffectsMaxColumns)
+        return fail(TRLDA_ERR_ARG, "the number of design columns must lie in [1, " +
+                                       std::to_string(trlda::kEffectsMaxColumns) + "]");
+    const int K = x->K, Pp = (P + 3) / 4 * 4;
+    const long long N = x->n;
+    const long long blocks = (N + trlda::kEffectsBlockDocs - 1) / trlda::kEffectsBlockDocs;
+    if (blocks > INT_MAX)                                // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many rows for one call");
+    int rc = effects_check_weights(weights_host, N);
+    if (rc)
+        return rc;
+    std::vector<double> zcopy, ccopy;
+    const double *zpad = nullptr, *cpad = nullptr;
+    if ((rc = effects_padded_rows(z_host, N, P, Pp, zcopy, &zpad, "the design matrix")) ||
+        (rc = effects_padded_rows(coef_host, K, P, Pp, ccopy, &cpad, "the coefficients")))
+        return rc;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<double> z, w, coef, scale, part, rss;
+    if ((rc = effects_upload(x, zpad, Pp, weights_host, z, w)) || (rc = coef.alloc((size_t)K * Pp)) ||
+        (rc = topicdocs_scale(x, scale)) || (rc = part.alloc((size_t)blocks * K)) || (rc = rss.alloc(K)))
+        return rc;
+    const size_t lds = trlda::effects_residual_lds();
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::effects_residual_kernel), lds)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(coef, cpad, (size_t)K * Pp * sizeof(double), hipMemcpyHostToDevice, stream));
+    const dim3 block(trlda::kEffectsThreads);
+    hipLaunchKernelGGL(trlda::effects_residual_kernel, dim3((unsigned)blocks), block, lds, stream, Pp, K, x->Kp, N,
+                       x->measure, z.get(), weights_host ? w.get() : (const double *)nullptr, coef.get(),
+                       x->rows.get(), scale.get(), part.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::effects_residual_finish_kernel,
+                       dim3((K + trlda::kEffectsThreads - 1) / trlda::kEffectsThreads), block, 0, stream, K, blocks,
+                       part.get(), rss.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(rss_out, rss, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2);
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }

@@ -8,7 +8,9 @@ the document groups of the indexed corpus (csrc/cluster_kernels.h, DESIGN.md 3.2
 silhouettes (csrc/silhouette_kernels.h), and the radius join -- the documents within
 a distance of each document -- with the density-based groups built on it (csrc/neighbors_kernels.h,
 DESIGN.md 3.29), and the minimum spanning tree of the indexed corpus with the single-linkage hierarchy
-and HDBSCAN* on it (csrc/mst_kernels.h).
+and HDBSCAN* on it (csrc/mst_kernels.h); and topic prevalence against what the caller
+knows about the documents -- group means, topics over time, the regression on covariates
+(csrc/effects_kernels.h).
 No counterpart in the reference package.
 """
 import ctypes as C
@@ -24,6 +26,7 @@ MAX_TOP_N = 100
 MAX_CLUSTERS = 4096                          # TRLDA_CLUSTER_MAX_CLUSTERS
 MAX_NEIGHBORS = 99                           # kTsneMaxNeighbors
 MAX_PERPLEXITY = 33                          # 3 * perplexity <= MAX_NEIGHBORS
+MAX_DESIGN_COLUMNS = 256                     # TRLDA_EFFECTS_MAX_COLUMNS
 
 
 def _measure(name):
@@ -704,6 +707,102 @@ class DocumentIndex(object):
             return labels
         return labels, {"probabilities": prob, "stabilities": stab, "tree": tree}
 
+    # -- topic prevalence against document metadata (csrc/effects_kernels.h) ---------
+    def group_prevalence(self, labels, weights=None, num_groups=None, return_variance=False, ddof=1):
+        """The mean topic proportions of each group of a labelling -- that of ``cluster``, ``dbscan``,
+        ``hdbscan`` or any the caller brings (a source, an author, a class).  Returns ``(mean,
+        counts)``: ``mean`` float64 K x G in Fortran order like ``cluster``'s centroids, ready for
+        ``query_gamma``, ``recommend_gamma`` or ``words_near``, column g being ``S_g / W_g`` with
+        ``S_gk = sum_{d in g} w_d theta_dk`` and ``W_g = sum w_d``; ``counts`` int64, the members of
+        each group whatever their weights.  A group with ``W_g = 0`` gets a NaN column.
+
+        ``labels``: N integers; -1 leaves a document out; values below -1 or at or above
+        ``num_groups`` (default ``max(labels) + 1``) are a ValueError; ``1 <= num_groups <= 4095``,
+        else RuntimeError.  ``weights``: N finite values >= 0, not all zero (document lengths give
+        token-weighted shares), or None.  With ``return_variance=True`` also ``variance`` (K x G):
+        ``(SS_gk / W_g) n_g / (n_g - ddof)`` with ``SS_gk = sum w_d (theta_dk - mean_gk)^2`` and
+        ``n_g`` the members of weight > 0 -- without weights ``SS / (n_g - ddof)`` -- and NaN where
+        ``n_g - ddof <= 0``.
+
+        A group's members are added by ascending id in chunks of 256, so its column depends on its
+        members' rows, their weights and K alone: not on the other groups, their numbering,
+        ``num_groups``, ``set_slab_rows`` or how the index was filled.  Nothing of size N x K leaves
+        the device."""
+        N = len(self)
+        lab, G = _group_labels(labels, N, num_groups)
+        w = _effects_weights(weights, N)
+        handle = self._live()
+        mean = np.empty((self._K, G), dtype=np.float64, order="F")
+        wsum = np.empty(G, dtype=np.float64)
+        counts = np.empty(G, dtype=np.int64)
+        ss = np.empty((self._K, G), dtype=np.float64, order="F") if return_variance else None
+        _ffi.check(_ffi.lib().trlda_docindex_group_moments(handle, lab.ctypes.data, G,
+                                                           None if w is None else w.ctypes.data, mean.ctypes.data,
+                                                           wsum.ctypes.data, counts.ctypes.data,
+                                                           ss.ctypes.data if return_variance else None))
+        if not return_variance:
+            return mean, counts
+        return mean, counts, _group_variance(ss, wsum, _positive_counts(lab, w, G), ddof, w is not None)
+
+    def topic_trends(self, times, bins=10, weights=None, return_variance=False):
+        """Topics over time: ``group_prevalence`` of the documents binned by ``times`` (N values).
+        ``bins``: an integer gives that many equal-width bins over the finite times, the last one
+        closed, as ``np.histogram`` does; an ascending array is taken as the bins' edges.  Times that
+        are not finite or lie outside the edges are left out.  Returns ``(edges, mean, counts)``
+        (``mean`` K x bins), with ``return_variance=True`` also the variance."""
+        edges, lab = _time_labels(times, bins)
+        rest = self.group_prevalence(lab, weights=weights, num_groups=len(edges) - 1,
+                                     return_variance=return_variance)
+        return (edges,) + tuple(rest)
+
+    def _residuals(self, handle, Z, w, coef):
+        """rss (K) of the design Z (N x P, C order) under the coefficients ``coef`` (P x K)."""
+        rss = np.empty(self._K, dtype=np.float64)
+        rows = np.ascontiguousarray(coef.T)
+        _ffi.check(_ffi.lib().trlda_docindex_regress_residuals(handle, Z.ctypes.data, Z.shape[1],
+                                                               None if w is None else w.ctypes.data,
+                                                               rows.ctypes.data, rss.ctypes.data))
+        return rss
+
+    def topic_effects(self, X, weights=None, intercept=True):
+        """The least-squares regression of the topic proportions theta (N x K) on covariates ``X``
+        (N x P float64, finite, one row per indexed document in id order; a vector is one column):
+        the effect of what is known about the documents on topic prevalence.  With ``intercept`` the
+        design is ``Z = [1 | X]``; it has ``1 <= P' <= 256`` columns.  ``weights``: N finite values
+        >= 0, not all zero, or None.
+
+        Returns a dict: ``coef`` (P' x K), ``stderr`` and ``tvalues`` (P' x K), ``rss`` (K),
+        ``sigma2 = rss / dof`` (K), ``dof = nobs - P'``, ``nobs`` (the rows of weight > 0), ``gram``
+        (``Z^T W Z``, P' x P') and ``cov_unscaled`` (its inverse), and with an intercept ``tss`` (the
+        weighted sum of squares about the weighted mean, K) and ``r2 = 1 - rss / tss``.  With
+        ``dof <= 0`` ``sigma2``, ``stderr`` and ``tvalues`` are NaN.  A rank-deficient design is a
+        ValueError.
+
+        The Gram matrix and ``Z^T W theta`` are formed on the device and solved on the host after
+        equilibration; the residuals are then formed explicitly on the device from the returned
+        coefficients, not from the products.  Nothing of size N x K leaves the device or is written
+        on it."""
+        N = len(self)
+        intercept = bool(intercept)
+        Z = _design(X, N, intercept)
+        w = _effects_weights(weights, N)
+        nobs = N if w is None else int(np.count_nonzero(w > 0.0))
+        P = Z.shape[1]
+        if nobs < P:
+            raise ValueError(RANK_DEFICIENT)
+        handle = self._live()
+        gram = np.empty((P, P), dtype=np.float64)
+        cross = np.empty((P, self._K), dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_regress_products(handle, Z.ctypes.data, P,
+                                                              None if w is None else w.ctypes.data,
+                                                              gram.ctypes.data, cross.ctypes.data))
+        coef, _ = _effects_solve(gram, cross)
+        rss = self._residuals(handle, Z, w, coef)
+        tss = None
+        if intercept:
+            tss = self._residuals(handle, np.ones((N, 1), dtype=np.float64), w, (cross[0] / gram[0, 0])[None, :])
+        return _effects_closing(gram, cross, rss, tss, nobs, intercept)
+
     # -- the map (csrc/tsne_kernels.h, DESIGN.md 3.32) ----------------------------------------------
     def set_tsne_tile(self, rows):
         """A/B switch: rows per workgroup of the map's repulsion kernel (0: default).  Results do not
@@ -1192,6 +1291,179 @@ def _hdbscan_labels(u, v, w, N, min_cluster_size, selection="eom", allow_single_
     ok = at[peak[keys[at]] > 0.0]
     prob[ok] = lam[ok] / peak[keys[ok]]
     return labels, prob, stab[kept]
+
+
+def _group_labels(labels, N, num_groups=None):
+    """(labels as contiguous int32, G) of ``group_prevalence``'s labels for an index of N documents, or
+    the documented error; no device is needed."""
+    lab = np.asarray(labels)
+    if lab.dtype.kind not in "iu":
+        raise TypeError("`labels` should be an array of integers.")
+    if N < 1:
+        raise RuntimeError("The index is empty.")
+    if lab.ndim != 1 or lab.shape[0] != N:
+        raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
+    low, high = int(lab.min()), int(lab.max())
+    G = max(high + 1, 1) if num_groups is None else operator.index(num_groups)
+    if not 1 <= G <= MAX_CLUSTERS - 1:
+        raise RuntimeError("`num_groups` should lie between 1 and %d." % (MAX_CLUSTERS - 1))
+    if low < -1 or high >= G:
+        raise ValueError("`labels` should lie between -1 (left out) and `num_groups` - 1.")
+    return np.ascontiguousarray(lab, dtype=np.int32), G
+
+
+def _effects_weights(weights, N):
+    """``weights`` as contiguous float64 (None: no weights), or the documented error."""
+    if weights is None:
+        return None
+    try:
+        w = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("`weights` should be of type `ndarray`.")
+    if w.ndim != 1 or w.shape[0] != N:
+        raise RuntimeError("`weights` should hold one weight per indexed document (%d)." % N)
+    if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+        raise ValueError("`weights` should be finite and not negative.")
+    if not np.any(w > 0.0):
+        raise ValueError("`weights` should not all be zero.")
+    return np.ascontiguousarray(w)
+
+
+def _positive_counts(lab, w, G):
+    """n_g (float64, G): the members of each group of weight > 0 (all of them without weights)."""
+    keep = lab >= 0 if w is None else (lab >= 0) & (w > 0.0)
+    return np.bincount(lab[keep], minlength=G).astype(np.float64)
+
+
+def _group_variance(ss, wsum, npos, ddof, weighted):
+    """The closing arithmetic of ``group_prevalence``'s variance on the device's sums (K x G):
+    ``(SS / W) n / (n - ddof)``, without weights ``SS / (n - ddof)``; NaN where ``n - ddof <= 0``."""
+    rest = npos - ddof
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = (ss / wsum[None, :]) * npos[None, :] / rest[None, :] if weighted else ss / rest[None, :]
+    var = np.asfortranarray(var)
+    var[:, ~(rest > 0)] = np.nan
+    return var
+
+
+def _time_labels(times, bins=10):
+    """(edges float64, labels int32) of ``topic_trends``: the bin of each time as ``np.histogram``
+    counts it -- half-open bins, the last one closed -- and -1 for a time that is not finite or lies
+    outside the edges.  An integer ``bins`` gives equal-width edges over the finite times."""
+    try:
+        t = np.array(times, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("`times` should be of type `ndarray`.")
+    if t.ndim != 1:
+        raise RuntimeError("`times` should be a one-dimensional array.")
+    finite = np.isfinite(t)
+    if np.ndim(bins) == 0:
+        count = operator.index(bins)
+        if count < 1:
+            raise ValueError("`bins` should be at least 1.")
+        if not finite.any():
+            raise ValueError("`times` holds no finite value to place the bins by.")
+        edges = np.histogram_bin_edges(t[finite], count)
+    else:
+        try:
+            edges = np.array(bins, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError("`bins` should be an integer or an array of edges.")
+        if edges.ndim != 1 or edges.shape[0] < 2:
+            raise RuntimeError("`bins` should hold at least two edges.")
+        if not np.all(np.isfinite(edges)) or np.any(np.diff(edges) < 0):
+            raise ValueError("The edges in `bins` should be finite and ascending.")
+    lab = np.searchsorted(edges, t, side="right") - 1
+    lab[t == edges[-1]] = len(edges) - 2
+    with np.errstate(invalid="ignore"):
+        lab[~finite | (t < edges[0]) | (t > edges[-1])] = -1
+    return edges, lab.astype(np.int32)
+
+
+RANK_DEFICIENT = "the design matrix is rank deficient"
+
+
+def _design(X, N, intercept):
+    """The design Z (N x P', float64, C order) of ``topic_effects``, or the documented error."""
+    if X is None:
+        raise TypeError("`X` should be of type `ndarray`.")
+    try:
+        x = np.array(X, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("`X` should be of type `ndarray`.")
+    if N < 1:
+        raise RuntimeError("The index is empty.")
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    if x.ndim != 2 or x.shape[0] != N:
+        raise RuntimeError("`X` should hold one row per indexed document (%d)." % N)
+    P = x.shape[1] + (1 if intercept else 0)
+    if not 1 <= P <= MAX_DESIGN_COLUMNS:
+        raise RuntimeError("The design should have between 1 and %d columns, the intercept included."
+                           % MAX_DESIGN_COLUMNS)
+    if not np.all(np.isfinite(x)):
+        raise ValueError("`X` should be finite.")
+    Z = np.empty((N, P), dtype=np.float64)
+    if intercept:
+        Z[:, 0] = 1.0
+    Z[:, P - x.shape[1]:] = x
+    return Z
+
+
+def _effects_solve(gram, cross):
+    """(coef P' x K, cov_unscaled P' x P') of the normal equations ``G b = C``: equilibrated by
+    ``D = diag(G)^-1/2``, ``D G D`` solved in float64, ``coef = D solve``.  ValueError where the
+    equilibrated Gram matrix is not positive definite or its smallest eigenvalue is at or below
+    ``P' 2^-52`` times the largest."""
+    G = np.asarray(gram, dtype=np.float64)
+    Cx = np.asarray(cross, dtype=np.float64)
+    P = G.shape[0]
+    diag = np.diag(G)
+    if not (np.all(np.isfinite(G)) and np.all(diag > 0.0)):
+        raise ValueError(RANK_DEFICIENT)
+    d = 1.0 / np.sqrt(diag)
+    A = G * d[:, None] * d[None, :]
+    try:
+        np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        raise ValueError(RANK_DEFICIENT)
+    ev = np.linalg.eigvalsh(A)
+    if not ev[0] > P * 2.0 ** -52 * ev[-1]:
+        raise ValueError(RANK_DEFICIENT)
+    coef = d[:, None] * np.linalg.solve(A, d[:, None] * Cx)
+    inv = np.linalg.solve(A, np.eye(P))
+    inv = 0.5 * (inv + inv.T)
+    return coef, d[:, None] * inv * d[None, :]
+
+
+def _effects_closing(gram, cross, rss, tss, nobs, intercept):
+    """The closing arithmetic of ``topic_effects`` on the device's sums: ``gram`` (P' x P'), ``cross``
+    (P' x K), ``rss`` (K) and, with an intercept, ``tss`` (K); ``nobs`` the rows of weight > 0."""
+    gram = np.asarray(gram, dtype=np.float64)
+    cross = np.asarray(cross, dtype=np.float64)
+    rss = np.asarray(rss, dtype=np.float64)
+    P, K = cross.shape
+    nobs = int(nobs)
+    if nobs < P:
+        raise ValueError(RANK_DEFICIENT)
+    coef, cov = _effects_solve(gram, cross)
+    dof = nobs - P
+    if dof > 0:
+        sigma2 = rss / float(dof)
+        stderr = np.sqrt(sigma2[None, :] * np.diag(cov)[:, None])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tvalues = coef / stderr
+    else:
+        sigma2 = np.full(K, np.nan)
+        stderr = np.full((P, K), np.nan)
+        tvalues = np.full((P, K), np.nan)
+    out = {"coef": coef, "stderr": stderr, "tvalues": tvalues, "rss": rss, "sigma2": sigma2, "dof": dof,
+           "nobs": nobs, "gram": gram, "cov_unscaled": cov}
+    if intercept:
+        tss = np.asarray(tss, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["tss"], out["r2"] = tss, 1.0 - rss / tss
+    return out
 
 
 def _correlation(scatter):
