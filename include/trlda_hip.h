@@ -909,6 +909,59 @@ int trlda_docindex_regress_residuals(trlda_docindex *index, const double *z_host
                                      const double *weights_host /* N or NULL */,
                                      const double *coef_host /* K x P row-major */, double *rss_out /* K */);
 
+/* Indexed documents classified from their topic proportions (csrc/classify_kernels.h):
+ * the device's part of the multinomial logistic regression of a label y_d in [0, C) on theta^_d, and its
+ * predictions.  theta^ is recovered from the stored rows as trlda_docindex_topic_documents recovers it.
+ * With the coefficients W (C x K row-major; no separate intercept, since sum_k theta^_dk = 1):
+ *   z_dc = sum_k theta^_dk W_ck      one chain of ceil(K / 4) MFMAs from +0 over ascending k
+ *   m = max_c z_dc,  e_c = exp(z_dc - m),  S = the e_c added one after the other from 0.0 in ascending c
+ *   l_d = (log S + m) - z_{d,y_d},   p_dc = e_c / S,   r_dc = w_d (p_dc - [c = y_d])
+ * Every + - x / is one rounded fp64 operation and nothing is atomic: two calls agree bitwise, however the
+ * index was filled.  2 <= C <= TRLDA_CLASSIFY_MAX_CLASSES (128).  TRLDA_ERR_ARG, before anything is waited
+ * for, copied or launched: a NULL index, input or required output, an empty index, C outside its range,
+ * ids together with a gamma, an evaluation without labels or after the index has grown; TRLDA_ERR_VALUE,
+ * likewise (checked on the host): a label outside [-1, C), a weight that is negative or not finite, a
+ * coefficient that is not finite, an id outside the index, a gamma that is not finite and positive.  A
+ * failed call leaves its outputs untouched.  Nothing is drawn; the index's rows, lambda, alpha, the
+ * counters and the model's statistics are left alone.  Each call runs on the model's stream and
+ * synchronises once.
+ *
+ * The labels of a fit go to the device once: labels_host (int32, N; -1 leaves a document out) and
+ * weights_host (N finite values >= 0, or NULL: every weight 1 and no multiply by it) are uploaded and
+ * kept on the index handle with the scratch of the evaluations until trlda_docindex_classify_clear, the
+ * next trlda_docindex_classify_set or trlda_docindex_destroy.  weight_sum_out[0] = the weights of the
+ * labelled documents added in ascending id from 0.0 on the host; count_out[c] the members of class c
+ * (int64), whatever their weights.  No reference counterpart. */
+int trlda_docindex_classify_set(trlda_docindex *index, const int32_t *labels_host /* N */, int C,
+                                const double *weights_host /* N or NULL */, double *weight_sum_out /* 1 */,
+                                int64_t *count_out /* C */);
+/* Frees what trlda_docindex_classify_set keeps (nothing, if nothing is kept).  No reference counterpart. */
+int trlda_docindex_classify_clear(trlda_docindex *index);
+/* loss_out[0] = sum_d w_d l_d and grad_out (C x K row-major) = sum_d r_dc theta^_dk over the labelled
+ * documents, unnormalised and without a penalty, for the labels that are set.  A workgroup owns a fixed
+ * block of 64 documents: its terms w_d l_d are added in ascending document order from 0.0, the blocks in
+ * ascending order.  The rows r (N x ceil(C / 4) * 4, the tail zero; a left-out document's row is exact
+ * zeros) are written for a slab of rows at a time and contracted with theta^ by the cross items of
+ * trlda_docindex_regress_products' kernel: chunks of rows (a function of (C, K, N) alone), every element
+ * of a chunk one chain of MFMAs over ascending rows, the chunks' partial sums added in ascending order
+ * once all slabs are done.  Neither sum depends on the slab or on the documents left out.  Up: C x K
+ * doubles; down: 1 + C x K.  No reference counterpart. */
+int trlda_docindex_classify_eval(trlda_docindex *index, const double *coef_host /* C x K row-major */,
+                                 double *loss_out /* 1 */, double *grad_out /* C x K row-major */);
+/* labels_out[i] (int32) = the first class of largest z for scored document i, and unless NULL
+ * proba_out[i * C + c] = p_ic.  Scored are the M documents of ids_host (int64 row ids, any order, repeats
+ * allowed), or the M columns of gamma_host (K x M, turned into rows as trlda_docindex_add_gamma turns
+ * them: an indexed document and its gamma give the same bits), or with both NULL every indexed document
+ * (M is ignored).  Needs no labels.  No reference counterpart. */
+int trlda_docindex_classify_predict(trlda_docindex *index, const double *coef_host /* C x K row-major */, int C,
+                                    const double *gamma_host /* K x M or NULL */, int64_t M,
+                                    const int64_t *ids_host /* M or NULL */, int32_t *labels_out /* M or N */,
+                                    double *proba_out /* (M or N) x C, may be NULL */);
+/* A/B switch: rows of r per slab of trlda_docindex_classify_eval, rounded down to whole chunks and at
+ * least one (0: what 256 MiB hold).  Results do not depend on it.  TRLDA_ERR_ARG while labels are set.
+ * No reference counterpart. */
+int trlda_docindex_set_classify_slab(trlda_docindex *index, int rows);
+
 /* The words a document most likely holds next (csrc/recommend_kernels.h).  An E-step
  * on the batch from gamma (K x B host, in: gamma0, out: gamma; max_iter, threshold as for
  * trlda_model_estep_host), then per document d and word w of the vocabulary

@@ -215,6 +215,11 @@ _SIGNATURES = {
     "trlda_docindex_group_moments": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "trlda_docindex_regress_products": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "trlda_docindex_regress_residuals": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "trlda_docindex_classify_set": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "trlda_docindex_classify_clear": (C.c_int, [vp]),
+    "trlda_docindex_classify_eval": (C.c_int, [vp, vp, vp, vp]),
+    "trlda_docindex_classify_predict": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp]),
+    "trlda_docindex_set_classify_slab": (C.c_int, [vp, C.c_int]),
     "trlda_model_topic_distances": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "trlda_model_set_topicdist_chunk": (C.c_int, [vp, C.c_int]),
     "trlda_model_allreduce_sstats": (C.c_int, [vp, vp, vp]),

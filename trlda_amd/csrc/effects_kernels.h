@@ -179,10 +179,13 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_group_finish_kernel(i
 //   first operand:  lane l holds B[column l & 15][row kk + (l >> 4)] (tile tj), second: A likewise
 //   (tile ti); D: register r of lane l is (tj column (l >> 4) + 4 r, ti column l & 15).
 // part_g[(chunk * P + j) * P + i], i in tile ti, j in tile tj; part_c[(chunk * P + i) * K + j].
+// A launch takes the items from item0 on and the chunks from chunk0 on (item0 = effects_gram_pairs(P):
+// the cross items alone, part_g is not touched), and z holds the design from row z_row0 on: what
+// classify_kernels.h works a slab of its rows off with.  The three are 0 for the regression.
 __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
     int P, int Pp, int K, int Kp, long long N, long long cr, int measure, const double *__restrict__ z,
     const double *__restrict__ w, const double *__restrict__ table, const double *__restrict__ scale,
-    double *__restrict__ part_g, double *__restrict__ part_c)
+    double *__restrict__ part_g, double *__restrict__ part_c, int item0, long long chunk0, long long z_row0)
 {
 #pragma clang fp contract(off)
     constexpr int S = kEffectsStride, T = kEffectsTile, W = kEffectsStage;
@@ -191,11 +194,13 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
     const int m = lane & 15, kq = lane >> 4;
     const int wi = (wid & 1) * 32, wj = (wid >> 1) * 32;
     const int PT = (P + T - 1) / T, pairs = PT * (PT + 1) / 2;
-    const bool cross = (int)blockIdx.x >= pairs;
-    int tj = 0, ti = blockIdx.x;
+    const int item = (int)blockIdx.x + item0;
+    const long long chunk = (long long)blockIdx.y + chunk0;
+    const bool cross = item >= pairs;
+    int tj = 0, ti = item;
     if (cross) {
-        ti = ((int)blockIdx.x - pairs) % PT;
-        tj = ((int)blockIdx.x - pairs) / PT;
+        ti = (item - pairs) % PT;
+        tj = (item - pairs) / PT;
     } else {
         // the pair (ti <= tj): column tj holds the tj + 1 pairs from tj (tj + 1) / 2 on
         while (ti > tj) {
@@ -204,7 +209,7 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
         }
     }
     const int i0 = ti * T, j0 = tj * T, J = cross ? K : P;
-    const long long dbeg = (long long)blockIdx.y * cr, dend = min(N, dbeg + cr);
+    const long long dbeg = chunk * cr, dend = min(N, dbeg + cr);
     const int st = tid & (T - 1), sw = tid / T;                     // staging: column, first row
     const bool a_in = i0 + st < P, b_in = j0 + st < J;
     const double *ap = z + (a_in ? i0 + st : 0);
@@ -227,12 +232,12 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
             double x = 0.0, y = 0.0;
             if (d < dend) {
                 if (a_in) {
-                    x = ap[(size_t)d * Pp];
+                    x = ap[(size_t)(d - z_row0) * Pp];
                     if (w)
                         x = w[d] * x;
                 }
                 if (b_in) {
-                    y = bp[(size_t)d * bstride];
+                    y = bp[(size_t)(cross ? d : d - z_row0) * bstride];
                     if (cross)
                         y = topicdocs_theta(y, measure, scale, d);
                 }
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
         }
     }
 
-    double *og = part_g + (size_t)blockIdx.y * P * P, *oc = part_c + (size_t)blockIdx.y * P * K;
+    double *og = part_g + (size_t)chunk * P * P, *oc = part_c + (size_t)chunk * P * K;
 #pragma unroll
     for (int ta = 0; ta < 2; ++ta)
 #pragma unroll
@@ -277,16 +282,18 @@ __global__ __launch_bounds__(kEffectsThreads) void effects_products_kernel(
 
 // One thread per element of the Gram (P x P) and of the cross products (P x K, row-major): the chunks'
 // partial sums in ascending order.  Element (p, q) of the Gram with p > q lies in a tile that was not
-// formed (or in the lower half of a diagonal one): it is read from (q, p).
+// formed (or in the lower half of a diagonal one): it is read from (q, p).  The launch's first thread
+// takes element e0 (e0 = P * P: the cross products alone, the Gram is not touched).
 __global__ __launch_bounds__(kEffectsThreads) void effects_products_finish_kernel(int P, int K, int chunks,
                                                                                   const double *__restrict__ part_g,
                                                                                   const double *__restrict__ part_c,
                                                                                   double *__restrict__ gram,
-                                                                                  double *__restrict__ cross)
+                                                                                  double *__restrict__ cross,
+                                                                                  size_t e0)
 {
 #pragma clang fp contract(off)
     const size_t ng = (size_t)P * P, nc = (size_t)P * K;
-    const size_t e = (size_t)blockIdx.x * kEffectsThreads + threadIdx.x;
+    const size_t e = e0 + (size_t)blockIdx.x * kEffectsThreads + threadIdx.x;
     if (e >= ng + nc)
         return;
     double a = 0.0;

@@ -65,6 +65,7 @@
 #include "neighbors_kernels.h"
 #include "mst_kernels.h"
 #include "effects_kernels.h"
+#include "classify_kernels.h"
 #include "querylik_kernels.h"
 #include "wordsim_kernels.h"
 #include "diagnostics_kernels.h"
@@ -5883,8 +5884,21 @@ int trlda_cooc_destroy(trlda_cooc *c)
 
 // The index: the table of rows (row-major, Kp doubles each) on the model's device, and the grow-only
 // workspaces of a query -- the queries' rows, a staged gamma, the slabs' lists, the results
+// What a classifier's fit keeps on the device between its evaluations (trlda_docindex_classify_set):
+// the labels and weights, the rows' sums of a cosine index, the slab of R and the partial sums
+struct ClassifyFit {
+    int C = 0, Cp = 0;
+    int64_t n = 0;                       // the rows the index held when the labels were set
+    bool weighted = false;
+    long long cr = 0, chunks = 0, slab = 0, blocks = 0;
+    DevBuf<int> labels;
+    DevBuf<double> w, scale, R, part_c, part_loss, coef, grad, loss;
+};
+
 struct trlda_docindex {
     trlda_model *model = nullptr;
+    int classify_slab = 0;               // rows of R per slab of trlda_docindex_classify_eval (0: default)
+    std::unique_ptr<ClassifyFit> fit;
     int measure = 0;
     int K = 0, Kp = 0;
     DevBuf<double> rows;                 // (its capacity: Kp doubles per row the table holds)
@@ -7131,10 +7145,10 @@ int trlda_docindex_regress_products(trlda_docindex *x, const double *z_host, int
     const dim3 block(trlda::kEffectsThreads);
     hipLaunchKernelGGL(trlda::effects_products_kernel, dim3((unsigned)items, (unsigned)chunks), block, 0, stream, P,
                        Pp, K, x->Kp, N, cr, x->measure, z.get(), weights_host ? w.get() : (const double *)nullptr,
-                       x->rows.get(), scale.get(), part_g.get(), part_c.get());
+                       x->rows.get(), scale.get(), part_g.get(), part_c.get(), 0, 0LL, 0LL);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(trlda::effects_products_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, P, K,
-                       (int)chunks, part_g.get(), part_c.get(), gram.get(), cross.get());
+                       (int)chunks, part_g.get(), part_c.get(), gram.get(), cross.get(), (size_t)0);
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(gram_out, gram, ng * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(cross_out, cross, nc * sizeof(double), hipMemcpyDeviceToHost, stream);
@@ -7191,6 +7205,264 @@ int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, in
     hipError_t e1 = hipMemcpyAsync(rss_out, rss, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipStreamSynchronize(stream);
     HIP_TRY(e1); HIP_TRY(e2);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- indexed documents classified from their topic proportions (csrc/classify_kernels.h) ----
+
+namespace {
+
+int classify_check_classes(int C)
+{
+    if (C < 2 || C > trlda::kClassifyMaxClasses)
+        return fail(TRLDA_ERR_ARG, "the number of classes must lie in [2, " +
+                                       std::to_string(trlda::kClassifyMaxClasses) + "]");
+    return TRLDA_OK;
+}
+
+// the rows' sums of `rows` (n x Kp) into `scale` on the model's stream; a hellinger index needs none
+int classify_scale(trlda_docindex *x, const double *rows, long long n, DevBuf<double> &scale)
+{
+    if (x->measure == 0)
+        return TRLDA_OK;
+    int rc = scale.alloc((size_t)n);
+    if (rc)
+        return rc;
+    constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)),
+                       dim3(trlda::kTopicDocsThreads), 0, x->model->stream, x->K, x->Kp, n, rows, scale.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_docindex_set_classify_slab(trlda_docindex *x, int rows)
+{
+    if (!x || rows < 0)
+        return fail(TRLDA_ERR_ARG, "classify slab: 0 (default) or a positive number of rows");
+    if (x->fit)
+        return fail(TRLDA_ERR_ARG, "the slab is set before the labels: trlda_docindex_classify_clear first");
+    x->classify_slab = rows;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_classify_clear(trlda_docindex *x)
+{
+    if (!x)
+        return fail(TRLDA_ERR_ARG, "NULL index");
+    if (x->fit) {
+        wait_before_delete(x->model);
+        x->fit.reset();
+    }
+    return TRLDA_OK;
+}
+
+int trlda_docindex_classify_set(trlda_docindex *x, const int32_t *labels_host, int C, const double *weights_host,
+                                double *weight_sum_out, int64_t *count_out)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "labels are int32");
+    if (!x || !labels_host || !weight_sum_out || !count_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / labels / weight sum / counts");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = classify_check_classes(C))
+        return rc_arg;
+    const int K = x->K, Cp = (C + 3) / 4 * 4;
+    const long long N = x->n;
+    const long long cr = trlda::classify_chunk_rows(C, K, N), chunks = (N + cr - 1) / cr;
+    const long long slab = trlda::classify_slab_rows(x->classify_slab, cr, Cp);
+    const long long blocks = (N + trlda::kClassifyBlockDocs - 1) / trlda::kClassifyBlockDocs;
+    // (grid dimensions x, y of a slab's launches)
+    if (std::min(slab, N) / trlda::kClassifyBlockDocs + 1 > INT_MAX || std::min(slab / cr, chunks) > 65535)
+        return fail(TRLDA_ERR_ARG, "too many rows per slab: lower trlda_docindex_set_classify_slab");
+    std::vector<int64_t> members((size_t)C, 0);
+    double omega = 0.0;                                  // the weights of the labelled documents, ascending id
+    for (long long d = 0; d < N; ++d) {
+        const int32_t l = labels_host[d];
+        if (l < -1 || l >= C)
+            return fail(TRLDA_ERR_VALUE, "a label lies outside [-1, C)");
+        if (l >= 0)
+            ++members[(size_t)l];
+    }
+    int rc = effects_check_weights(weights_host, N);
+    if (rc)
+        return rc;
+    for (long long d = 0; d < N; ++d)
+        if (labels_host[d] >= 0)
+            omega += weights_host ? weights_host[d] : 1.0;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    if (x->fit) {
+        wait_before_delete(m);
+        x->fit.reset();
+    }
+    hipStream_t stream = m->stream;
+    std::unique_ptr<ClassifyFit> f(new ClassifyFit());
+    f->C = C;
+    f->Cp = Cp;
+    f->n = N;
+    f->weighted = weights_host != nullptr;
+    f->cr = cr;
+    f->chunks = chunks;
+    f->slab = slab;
+    f->blocks = blocks;
+    const size_t ck = (size_t)C * K;
+    if ((rc = f->labels.alloc((size_t)N)) || (weights_host && (rc = f->w.alloc((size_t)N))) ||
+        (rc = classify_scale(x, x->rows.get(), N, f->scale)) ||
+        (rc = f->R.alloc((size_t)std::min(slab, chunks * cr) * Cp)) || (rc = f->part_c.alloc((size_t)chunks * ck)) ||
+        (rc = f->part_loss.alloc((size_t)blocks)) || (rc = f->coef.alloc((size_t)C * x->Kp)) ||
+        (rc = f->grad.alloc(ck)) || (rc = f->loss.alloc(1)))
+        return rc;
+    // (labels_host and weights_host live until the synchronisation below)
+    hipError_t e1 = hipMemcpyAsync(f->labels, labels_host, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, stream);
+    hipError_t e2 = weights_host ? hipMemcpyAsync(f->w, weights_host, (size_t)N * sizeof(double),
+                                                  hipMemcpyHostToDevice, stream)
+                                 : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    x->fit = std::move(f);
+    *weight_sum_out = omega;
+    std::copy(members.begin(), members.end(), count_out);
+    return TRLDA_OK;
+}
+
+int trlda_docindex_classify_eval(trlda_docindex *x, const double *coef_host, double *loss_out, double *grad_out)
+{
+    if (!x || !coef_host || !loss_out || !grad_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / coefficients / loss / gradient");
+    ClassifyFit *f = x->fit.get();
+    if (!f)
+        return fail(TRLDA_ERR_ARG, "no labels are set: trlda_docindex_classify_set first");
+    if (f->n != x->n)
+        return fail(TRLDA_ERR_ARG, "the index has grown since the labels were set");
+    const int K = x->K, Kp = x->Kp, C = f->C, Cp = f->Cp;
+    const long long N = f->n;
+    std::vector<double> ccopy;
+    const double *cpad = nullptr;
+    int rc = effects_padded_rows(coef_host, C, K, Kp, ccopy, &cpad, "the coefficients");
+    if (rc)
+        return rc;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    hipStream_t stream = m->stream;
+    const size_t lds = trlda::classify_forward_lds(C);
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::classify_forward_kernel<true>), lds)))
+        return rc;
+    // (ccopy lives until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(f->coef, cpad, (size_t)C * Kp * sizeof(double), hipMemcpyHostToDevice, stream));
+    const int pairs = (int)trlda::effects_gram_pairs(C);
+    const unsigned items = (unsigned)(trlda::effects_tiles(C) * trlda::effects_tiles(K));
+    const double *wd = f->weighted ? f->w.get() : (const double *)nullptr;
+    for (long long s0 = 0; s0 < N; s0 += f->slab) {
+        const long long s1 = std::min(N, s0 + f->slab);
+        const long long blocks = (s1 - s0 + trlda::kClassifyBlockDocs - 1) / trlda::kClassifyBlockDocs;
+        const long long chunks = (s1 - s0 + f->cr - 1) / f->cr;
+        hipLaunchKernelGGL(trlda::classify_forward_kernel<true>, dim3((unsigned)blocks), dim3(trlda::kClassifyThreads),
+                           lds, stream, C, Cp, Kp, N, s0, x->measure, x->rows.get(), f->scale.get(),
+                           (const long long *)nullptr, f->coef.get(), f->labels.get(), wd, f->R.get(),
+                           f->part_loss.get(), (int *)nullptr, (double *)nullptr);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(trlda::effects_products_kernel, dim3(items, (unsigned)chunks), dim3(trlda::kEffectsThreads),
+                           0, stream, C, Cp, K, Kp, N, f->cr, x->measure, f->R.get(), (const double *)nullptr,
+                           x->rows.get(), f->scale.get(), (double *)nullptr, f->part_c.get(), pairs, s0 / f->cr, s0);
+        HIP_TRY(hipGetLastError());
+    }
+    const size_t ck = (size_t)C * K;
+    hipLaunchKernelGGL(trlda::classify_loss_finish_kernel, dim3(1), dim3(trlda::kClassifyThreads), 0, stream,
+                       f->blocks, f->part_loss.get(), f->loss.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::effects_products_finish_kernel,
+                       dim3((unsigned)((ck + trlda::kEffectsThreads - 1) / trlda::kEffectsThreads)),
+                       dim3(trlda::kEffectsThreads), 0, stream, C, K, (int)f->chunks, (const double *)nullptr,
+                       f->part_c.get(), (double *)nullptr, f->grad.get(), (size_t)C * C);
+    HIP_TRY(hipGetLastError());
+    double loss = 0.0;
+    hipError_t e1 = hipMemcpyAsync(&loss, f->loss, sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = hipMemcpyAsync(grad_out, f->grad, ck * sizeof(double), hipMemcpyDeviceToHost, stream);
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    HIP_TRY(hipGetLastError());
+    *loss_out = loss;
+    return TRLDA_OK;
+}
+
+int trlda_docindex_classify_predict(trlda_docindex *x, const double *coef_host, int C, const double *gamma_host,
+                                    int64_t M, const int64_t *ids_host, int32_t *labels_out, double *proba_out)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
+    if (!x || !coef_host || !labels_out)
+        return fail(TRLDA_ERR_ARG, "NULL index / coefficients / labels");
+    if (x->n < 1)
+        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = classify_check_classes(C))
+        return rc_arg;
+    if (ids_host && gamma_host)
+        return fail(TRLDA_ERR_ARG, "the scored rows are either ids or a gamma, not both");
+    if ((ids_host || gamma_host) && M < 1)
+        return fail(TRLDA_ERR_ARG, "a list of ids or a gamma needs at least one document");
+    if (gamma_host && M > INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many gamma columns in one call");
+    const int K = x->K, Kp = x->Kp;
+    const long long N = x->n;
+    const long long rows = ids_host || gamma_host ? (long long)M : N;
+    const long long blocks = (rows + trlda::kClassifyBlockDocs - 1) / trlda::kClassifyBlockDocs;
+    if (blocks > INT_MAX)                                // (grid dimension x)
+        return fail(TRLDA_ERR_ARG, "too many rows for one call");
+    if (ids_host)
+        for (int64_t i = 0; i < M; ++i)
+            if (ids_host[i] < 0 || ids_host[i] >= N)
+                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
+    if (gamma_host)
+        if (int rc_val = docindex_check_gamma(gamma_host, (size_t)K * (size_t)M))
+            return rc_val;
+    std::vector<double> ccopy;
+    const double *cpad = nullptr;
+    int rc = effects_padded_rows(coef_host, C, K, Kp, ccopy, &cpad, "the coefficients");
+    if (rc)
+        return rc;
+    trlda_model *m = x->model;
+    if ((rc = check_model(m)))
+        return rc;
+    hipStream_t stream = m->stream;
+    DevBuf<double> coef, gstage, qrows, scale, proba;
+    DevBuf<long long> ids;
+    DevBuf<int> label;
+    if ((rc = coef.alloc((size_t)C * Kp)) || (rc = label.alloc((size_t)rows)) ||
+        (proba_out && (rc = proba.alloc((size_t)rows * C))) || (ids_host && (rc = ids.alloc((size_t)M))))
+        return rc;
+    const size_t lds = trlda::classify_forward_lds(C);
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::classify_forward_kernel<false>), lds)))
+        return rc;
+    // (ccopy, ids_host and gamma_host live until the synchronisation below)
+    HIP_TRY(hipMemcpyAsync(coef, cpad, (size_t)C * Kp * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (ids_host)
+        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if (gamma_host && (rc = cluster_rows(x, gamma_host, (int)M, gstage, qrows)))
+        return rc;
+    const double *table = gamma_host ? qrows.get() : x->rows.get();
+    if ((rc = classify_scale(x, table, gamma_host ? rows : N, scale)))
+        return rc;
+    hipLaunchKernelGGL(trlda::classify_forward_kernel<false>, dim3((unsigned)blocks), dim3(trlda::kClassifyThreads),
+                       lds, stream, C, (C + 3) / 4 * 4, Kp, rows, 0LL, x->measure, table, scale.get(),
+                       ids_host ? ids.get() : (const long long *)nullptr, coef.get(), (const int *)nullptr,
+                       (const double *)nullptr, (double *)nullptr, (double *)nullptr, label.get(),
+                       proba_out ? proba.get() : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(labels_out, label, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+    hipError_t e2 = proba_out ? hipMemcpyAsync(proba_out, proba, (size_t)rows * C * sizeof(double),
+                                               hipMemcpyDeviceToHost, stream)
+                              : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }

@@ -10,7 +10,9 @@ a distance of each document -- with the density-based groups built on it (csrc/n
 DESIGN.md 3.29), and the minimum spanning tree of the indexed corpus with the single-linkage hierarchy
 and HDBSCAN* on it (csrc/mst_kernels.h); and topic prevalence against what the caller
 knows about the documents -- group means, topics over time, the regression on covariates
-(csrc/effects_kernels.h).
+(csrc/effects_kernels.h); and the reverse direction, a document's class predicted from
+its topic proportions -- multinomial logistic regression and a nearest-neighbour baseline
+(csrc/classify_kernels.h).
 No counterpart in the reference package.
 """
 import ctypes as C
@@ -27,6 +29,8 @@ MAX_CLUSTERS = 4096                          # TRLDA_CLUSTER_MAX_CLUSTERS
 MAX_NEIGHBORS = 99                           # kTsneMaxNeighbors
 MAX_PERPLEXITY = 33                          # 3 * perplexity <= MAX_NEIGHBORS
 MAX_DESIGN_COLUMNS = 256                     # TRLDA_EFFECTS_MAX_COLUMNS
+MAX_CLASSES = 128                            # TRLDA_CLASSIFY_MAX_CLASSES
+LBFGS_MEMORY = 10                            # pairs the classifier's optimiser keeps: a chosen number
 
 
 def _measure(name):
@@ -803,6 +807,151 @@ class DocumentIndex(object):
             tss = self._residuals(handle, np.ones((N, 1), dtype=np.float64), w, (cross[0] / gram[0, 0])[None, :])
         return _effects_closing(gram, cross, rss, tss, nobs, intercept)
 
+    # -- classification from topic proportions (csrc/classify_kernels.h) -------------
+    def set_classify_slab(self, rows):
+        """A/B switch: rows of scratch per slab of the classifier's evaluations, rounded down to whole
+        chunks (0: default, what 256 MiB hold).  Results do not depend on it."""
+        _ffi.check(_ffi.lib().trlda_docindex_set_classify_slab(self._live(), operator.index(rows)))
+
+    def _classify_set(self, handle, lab, C, w):
+        """The labels and weights of a fit to the device, once: (weight sum, counts)."""
+        omega = np.zeros(1, dtype=np.float64)
+        counts = np.zeros(C, dtype=np.int64)
+        _ffi.check(_ffi.lib().trlda_docindex_classify_set(handle, lab.ctypes.data, C,
+                                                          None if w is None else w.ctypes.data, omega.ctypes.data,
+                                                          counts.ctypes.data))
+        return float(omega[0]), counts
+
+    def _classify_eval(self, handle, W):
+        """(loss_sum, grad_sum C x K) at the coefficients W (C x K) under the labels that are set."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        loss = np.zeros(1, dtype=np.float64)
+        grad = np.empty(W.shape, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_docindex_classify_eval(handle, W.ctypes.data, loss.ctypes.data, grad.ctypes.data))
+        return float(loss[0]), grad
+
+    def classifier_loss(self, coef, labels, weights=None, num_classes=None):
+        """The device's part of ``fit_classifier`` on its own: ``(loss_sum, grad_sum, weight_sum)`` of
+        the multinomial logistic regression of ``labels`` on theta at the coefficients ``coef``
+        (C x K).  With ``z_dc = sum_k theta_dk coef_ck`` and ``p_d = softmax(z_d)``: ``loss_sum = sum_d
+        w_d (log sum_c exp(z_dc) - z_{d,y_d})``, ``grad_sum`` (C x K) ``= sum_d w_d (p_dc - [c = y_d])
+        theta_dk`` and ``weight_sum = sum_d w_d``, each over the documents with a label >= 0: the sums
+        are unnormalised and carry no penalty.  Labels and weights as for ``fit_classifier``.  Two
+        calls agree bitwise, whatever ``set_classify_slab`` says and however the index was filled."""
+        N = len(self)
+        lab, C = _class_labels(labels, N, num_classes)
+        w = _effects_weights(weights, N)
+        W = _coefficients(coef, self._K, C)
+        handle = self._live()
+        try:
+            omega, _ = self._classify_set(handle, lab, C, w)
+            loss, grad = self._classify_eval(handle, W)
+        finally:
+            _ffi.lib().trlda_docindex_classify_clear(handle)
+        return loss, grad, omega
+
+    def fit_classifier(self, labels, num_classes=None, l2=1e-4, weights=None, max_iter=200, tol=1e-6, init=None):
+        """Multinomial logistic regression of a label on the indexed documents' topic proportions
+        (Blei, Ng & Jordan 2003, section 7.2): the coefficients ``W`` (C x K) that minimise ``F(W) = (1 /
+        Omega) sum_d w_d (log sum_c exp(z_dc) - z_{d,y_d}) + (l2 / 2) |W|_F^2`` with ``z_dc = sum_k
+        theta_dk W_ck`` and ``Omega = sum_d w_d``, over the documents with ``y_d >= 0``.  There is no
+        separate intercept: theta sums to 1, so W contains one.
+
+        ``labels``: N integers -- those of ``cluster``, ``dbscan``, ``hdbscan`` or any the caller
+        brings; -1 leaves a document out; values below -1 or at or above ``num_classes`` (default
+        ``max(labels) + 1``) are a ValueError; ``2 <= num_classes <= 128``, else RuntimeError.  A class
+        without members is allowed: only the penalty acts on its row.  ``weights``: N finite values
+        >= 0, not all zero, or None; no labelled document of positive weight is a ValueError.  ``l2``
+        must be finite and positive (ValueError): F is then l2-strongly convex and the optimum unique.
+
+        The loss and its gradient are formed on the device (``classifier_loss``); labels and weights
+        go there once, and per evaluation C x K doubles go up and 1 + C x K come down.  The optimiser
+        is ``lbfgs_minimize`` on the host, from ``init`` (C x K) or zeros, deterministic.  Returns a
+        dict: ``coef`` (C x K), ``loss`` (F) and ``grad_norm`` (the largest absolute entry of F's
+        gradient) at return, ``iterations``, ``evaluations``, ``converged`` (``grad_norm <= tol``;
+        False at ``max_iter`` or when the line search can no longer decrease F -- never an error),
+        ``nobs`` (the labelled documents of weight > 0), ``counts`` (int64, the members of each class)
+        and ``l2``.  Nothing is drawn."""
+        N = len(self)
+        lab, C = _class_labels(labels, N, num_classes)
+        w = _effects_weights(weights, N)
+        l2 = _penalty(l2)
+        max_iter = operator.index(max_iter)
+        tol = float(tol)
+        if max_iter < 0 or not tol >= 0.0:
+            raise ValueError("`max_iter` and `tol` should not be negative.")
+        W0 = np.zeros((C, self._K), dtype=np.float64) if init is None else _coefficients(init, self._K, C)
+        nobs = int(np.count_nonzero(lab >= 0 if w is None else (lab >= 0) & (w > 0.0)))
+        if nobs < 1:
+            raise ValueError("No labelled document has a positive weight.")
+        handle = self._live()
+        try:
+            omega, counts = self._classify_set(handle, lab, C, w)
+
+            def fun(W):
+                loss, grad = self._classify_eval(handle, W)
+                return loss / omega + 0.5 * l2 * float(np.sum(W * W)), grad / omega + l2 * W
+            fit = lbfgs_minimize(fun, W0, max_iter=max_iter, tol=tol)
+        finally:
+            _ffi.lib().trlda_docindex_classify_clear(handle)
+        fit.update(nobs=nobs, counts=counts, l2=l2)
+        return fit
+
+    def predict(self, coef, gamma=None, ids=None, return_proba=False):
+        """The class of each scored document under the coefficients ``coef`` (C x K, as
+        ``fit_classifier`` returns them): the argmax of the logits ``z_dc = sum_k theta_dk coef_ck``,
+        equal logits going to the smaller class id.  int32.  Scored are all indexed documents
+        (``gamma`` and ``ids`` both None), the documents ``ids`` (any order, repeats allowed), or new
+        documents given by their ``gamma`` (K x M; no E-step); both together are a ValueError.  A
+        document gets the same bits whether it is indexed or passed by its gamma.  With
+        ``return_proba=True`` also the softmax of the logits, float64 M x C."""
+        if ids is not None and gamma is not None:
+            raise ValueError("Give `ids` or `gamma`, not both.")
+        W = _coefficients(coef, self._K)
+        C = W.shape[0]
+        handle = self._live()
+        N = self._size()
+        rows = _silhouette_ids(ids, N)
+        g = None if gamma is None else self._gamma(gamma)
+        if g is not None and g.shape[1] < 1:
+            raise RuntimeError("`gamma` should hold at least one document.")
+        M = N if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+        labels = np.empty(M, dtype=np.int32)
+        proba = np.empty((M, C), dtype=np.float64) if return_proba else None
+        _ffi.check(_ffi.lib().trlda_docindex_classify_predict(handle, W.ctypes.data, C,
+                                                              None if g is None else g.ctypes.data, M,
+                                                              None if rows is None else rows.ctypes.data,
+                                                              labels.ctypes.data,
+                                                              proba.ctypes.data if return_proba else None))
+        return (labels, proba) if return_proba else labels
+
+    def knn_predict(self, labels, gamma=None, ids=None, top_n=10, weighting="uniform", num_classes=None,
+                    return_votes=False):
+        """The baseline classifier: the class most of a document's ``top_n`` nearest indexed
+        documents carry.  ``labels`` as for ``fit_classifier`` (-1: the document does not vote).  New
+        documents are given by ``gamma`` (K x M) and searched with ``query_gamma``; indexed documents
+        (``ids``, or all of them) take their neighbours from ``nearest_neighbors``, which leaves the
+        own id out: leave-one-out classification.  ``weighting='uniform'`` counts a vote as 1,
+        ``'similarity'`` as the neighbour's similarity s; the votes are added in rank order, ties go
+        to the smaller class id, and a document none of whose neighbours votes gets -1.  Host
+        arithmetic on the two searches' results.  int32; with ``return_votes=True`` also the votes
+        (M x C float64)."""
+        if weighting not in ("uniform", "similarity"):
+            raise ValueError("`weighting` should be 'uniform' or 'similarity'.")
+        if ids is not None and gamma is not None:
+            raise ValueError("Give `ids` or `gamma`, not both.")
+        N = len(self)
+        lab, C = _class_labels(labels, N, num_classes)
+        if gamma is not None:
+            nearest, sim = self.query_gamma(gamma, top_n=top_n, return_similarity=True)
+        else:
+            rows = _silhouette_ids(ids, N)
+            nearest, sim = self.nearest_neighbors(top_n=top_n, return_similarity=True)
+            if rows is not None:
+                nearest, sim = nearest[rows], sim[rows]
+        pred, votes = knn_votes(nearest, sim, lab, C, weighting)
+        return (pred, votes) if return_votes else pred
+
     # -- the map (csrc/tsne_kernels.h, DESIGN.md 3.32) ----------------------------------------------
     def set_tsne_tile(self, rows):
         """A/B switch: rows per workgroup of the map's repulsion kernel (0: default).  Results do not
@@ -1464,6 +1613,151 @@ def _effects_closing(gram, cross, rss, tss, nobs, intercept):
         with np.errstate(divide="ignore", invalid="ignore"):
             out["tss"], out["r2"] = tss, 1.0 - rss / tss
     return out
+
+
+def _class_labels(labels, N, num_classes=None):
+    """(labels as contiguous int32, C) of the classifiers' labels for an index of N documents, or the
+    documented error; no device is needed."""
+    lab = np.asarray(labels)
+    if lab.dtype.kind not in "iu":
+        raise TypeError("`labels` should be an array of integers.")
+    if N < 1:
+        raise RuntimeError("The index is empty.")
+    if lab.ndim != 1 or lab.shape[0] != N:
+        raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
+    low, high = int(lab.min()), int(lab.max())
+    C = high + 1 if num_classes is None else operator.index(num_classes)
+    if not 2 <= C <= MAX_CLASSES:
+        raise RuntimeError("`num_classes` should lie between 2 and %d." % MAX_CLASSES)
+    if low < -1 or high >= C:
+        raise ValueError("`labels` should lie between -1 (left out) and `num_classes` - 1.")
+    return np.ascontiguousarray(lab, dtype=np.int32), C
+
+
+def _coefficients(coef, K, C=None):
+    """``coef`` as contiguous float64 C x K, or the documented error."""
+    try:
+        W = np.array(coef, dtype=np.float64, order="C")
+    except (TypeError, ValueError):
+        raise TypeError("`coef` should be of type `ndarray`.")
+    if W.ndim != 2 or W.shape[1] != K or (C is not None and W.shape[0] != C):
+        raise RuntimeError("`coef` should hold one row of %d coefficients per class." % K)
+    if not 2 <= W.shape[0] <= MAX_CLASSES:
+        raise RuntimeError("The number of classes should lie between 2 and %d." % MAX_CLASSES)
+    if not np.all(np.isfinite(W)):
+        raise ValueError("`coef` should be finite.")
+    return np.ascontiguousarray(W)
+
+
+def _penalty(l2):
+    l2 = float(l2)
+    if not (l2 > 0.0 and math.isfinite(l2)):
+        raise ValueError("`l2` should be finite and positive.")
+    return l2
+
+
+def lbfgs_minimize(fun, W0, max_iter=200, tol=1e-6, memory=LBFGS_MEMORY):
+    """L-BFGS (Nocedal 1980; the two-loop recursion with ``memory`` pairs, the first direction scaled
+    by ``s.y / y.y``) with a backtracking line search, on float64 arrays of any one shape:
+    ``fun(W) -> (F, grad)``.  Deterministic: every inner product is ``np.sum(a * b)``.
+
+    The step t starts at 1 (``1 / |grad|_2``, capped at 1, while the memory is empty) and is halved
+    until ``F(W + t d) <= F(W) + 1e-4 t grad.d`` (Armijo).  Near the optimum the decrease of F falls
+    below its rounding -- about ``|grad|^2 / (2 l2)`` against ``2^-52 F`` -- long before the gradient
+    stops shrinking, so a step whose F differs from F(W) by no more than ``64 * 2^-52 |F|`` is also
+    taken when it shrinks the slope, ``|grad(W + t d).d| <= 0.9 |grad.d|`` (the approximate Wolfe
+    condition of Hager & Zhang 2005).  A direction that is not a descent direction, or a search that
+    fails after 40 halvings, drops the memory and tries the steepest descent once; if that fails too
+    the search can no longer decrease F and the loop ends.
+
+    Stops at ``max |grad| <= tol`` (``converged``), at ``max_iter`` iterations or at the failed
+    search.  Returns a dict: ``coef``, ``loss``, ``grad_norm`` (max |grad|), ``iterations``,
+    ``evaluations``, ``converged``."""
+    W = np.array(W0, dtype=np.float64)
+    F, g = fun(W)
+    F, g = float(F), np.asarray(g, dtype=np.float64)
+    evaluations, iterations = 1, 0
+    S, Y, RHO = [], [], []
+    eps = 64.0 * 2.0 ** -52
+    while iterations < max_iter and not float(np.max(np.abs(g))) <= tol:
+        stepped = False
+        for attempt in (0, 1):
+            if attempt == 1:
+                if not S:
+                    break
+                S, Y, RHO = [], [], []
+            q = g.copy()
+            alphas = []
+            for s, y, rho in zip(reversed(S), reversed(Y), reversed(RHO)):
+                a = rho * float(np.sum(s * q))
+                alphas.append(a)
+                q = q - a * y
+            if S:
+                q = q * (float(np.sum(S[-1] * Y[-1])) / float(np.sum(Y[-1] * Y[-1])))
+            for (s, y, rho), a in zip(zip(S, Y, RHO), reversed(alphas)):
+                b = rho * float(np.sum(y * q))
+                q = q + s * (a - b)
+            d = -q
+            slope = float(np.sum(g * d))
+            if not slope < 0.0:
+                continue
+            t = 1.0 if S else min(1.0, 1.0 / math.sqrt(float(np.sum(g * g))))
+            for _ in range(40):
+                Wn = W + t * d
+                Fn, gn = fun(Wn)
+                Fn, gn = float(Fn), np.asarray(gn, dtype=np.float64)
+                evaluations += 1
+                if math.isfinite(Fn) and np.all(np.isfinite(gn)):
+                    if Fn <= F + 1e-4 * t * slope:
+                        stepped = True
+                    elif abs(Fn - F) <= eps * max(abs(F), abs(Fn)) and \
+                            abs(float(np.sum(gn * d))) <= 0.9 * abs(slope):
+                        stepped = True
+                if stepped:
+                    break
+                t *= 0.5
+            if stepped:
+                break
+        if not stepped:
+            break
+        s, y = Wn - W, gn - g
+        sy = float(np.sum(s * y))
+        if sy > 0.0:
+            S.append(s)
+            Y.append(y)
+            RHO.append(1.0 / sy)
+            if len(S) > memory:
+                S.pop(0), Y.pop(0), RHO.pop(0)
+        W, F, g = Wn, Fn, gn
+        iterations += 1
+    grad_norm = float(np.max(np.abs(g)))
+    return {"coef": W, "loss": F, "grad_norm": grad_norm, "iterations": iterations, "evaluations": evaluations,
+            "converged": bool(grad_norm <= tol)}
+
+
+def knn_votes(nearest, sim, labels, num_classes, weighting="uniform"):
+    """The vote of ``knn_predict``: ``nearest`` (M x T ids of labelled documents in rank order, a
+    negative id: no neighbour), ``sim`` (M x T similarities), ``labels`` (-1: no vote).  Returns
+    ``(pred int32 M, votes float64 M x num_classes)``.  The votes are added one rank after the other,
+    each rank as one vectorised step over all documents; ties go to the smaller class id; a document
+    without a voting neighbour gets -1."""
+    nearest = np.asarray(nearest, dtype=np.int64)
+    sim = np.asarray(sim, dtype=np.float64)
+    labels = np.asarray(labels)
+    M, T = nearest.shape
+    votes = np.zeros((M, num_classes), dtype=np.float64)
+    voted = np.zeros(M, dtype=bool)
+    rows = np.arange(M)
+    for j in range(T):
+        nb = nearest[:, j]
+        lab = np.where(nb >= 0, labels[np.maximum(nb, 0)], -1)
+        v = lab >= 0
+        add = sim[:, j] if weighting == "similarity" else np.ones(M)
+        votes[rows[v], lab[v]] = votes[rows[v], lab[v]] + add[v]
+        voted |= v
+    pred = np.argmax(votes, axis=1).astype(np.int32)
+    pred[~voted] = -1
+    return pred, votes
 
 
 def _correlation(scatter):
