@@ -2961,18 +2961,25 @@ int check_split_exchange(trlda_model *m)
                                "for a peer's signal; the results of that call are void");
 }
 
-// The end of an entry point that brings results back: `queued` are the statuses of the copies it
-// has queued on the model's stream (all of them are queued before the first is looked at, so the
-// stream is waited for whatever they said: host buffers may go out of scope behind this).  The
-// first failed copy, then the wait, then a launch's error, then the exchange.
-int wait_for_results(trlda_model *m, std::initializer_list<hipError_t> queued)
+// The wait of an entry point for copies it has queued on the model's stream: `queued` are their
+// statuses (all of them are queued before the first is looked at, so the stream is waited for
+// whatever they said: host buffers may go out of scope behind this).  The first failed copy, then
+// the wait, then a launch's error.
+int wait_for_copies(trlda_model *m, std::initializer_list<hipError_t> queued)
 {
     const hipError_t waited = hipStreamSynchronize(m->stream);
     for (hipError_t copy_queued : queued)
         HIP_TRY(copy_queued);
     HIP_TRY(waited);
     HIP_TRY(hipGetLastError());
-    return check_split_exchange(m);
+    return TRLDA_OK;
+}
+
+// The end of an entry point that brings results of the E-step back: the copies, then the exchange.
+int wait_for_results(trlda_model *m, std::initializer_list<hipError_t> queued)
+{
+    int rc = wait_for_copies(m, queued);
+    return rc ? rc : check_split_exchange(m);
 }
 
 // before an accumulator on the model's device is deleted: the stream's kernels may still read its buffers
@@ -5882,8 +5889,6 @@ int trlda_cooc_destroy(trlda_cooc *c)
 
 // ---- nearest documents in topic space (csrc/docindex_kernels.h) ----
 
-// The index: the table of rows (row-major, Kp doubles each) on the model's device, and the grow-only
-// workspaces of a query -- the queries' rows, a staged gamma, the slabs' lists, the results
 // What a classifier's fit keeps on the device between its evaluations (trlda_docindex_classify_set):
 // the labels and weights, the rows' sums of a cosine index, the slab of R and the partial sums
 struct ClassifyFit {
@@ -5895,6 +5900,8 @@ struct ClassifyFit {
     DevBuf<double> w, scale, R, part_c, part_loss, coef, grad, loss;
 };
 
+// The index: the table of rows (row-major, Kp doubles each) on the model's device, and the grow-only
+// workspaces of a query -- the queries' rows, a staged gamma, the slabs' lists, the results
 struct trlda_docindex {
     trlda_model *model = nullptr;
     int classify_slab = 0;               // rows of R per slab of trlda_docindex_classify_eval (0: default)
@@ -5911,6 +5918,8 @@ struct trlda_docindex {
 };
 
 namespace {
+
+constexpr int pad4(int n) { return (n + 3) / 4 * 4; }    // rows of K, C or P doubles hold whole groups of four
 
 // room for `need` rows: doubling from max(1024, first request), the rows in use copied on the
 // model's stream
@@ -5959,13 +5968,27 @@ int docindex_slab_rows(const trlda_docindex *x)
     return x->slab_rows > 0 ? x->slab_rows : trlda::kDocIndexSlabRows;
 }
 
-// what every query checks before anything is waited for, drawn, copied or launched
-int docindex_query_checks(const trlda_docindex *x, int top_n)
+int docindex_check_filled(const trlda_docindex *x)
 {
     if (x->n < 1)
         return fail(TRLDA_ERR_ARG, "the index is empty");
+    return TRLDA_OK;
+}
+
+int docindex_check_top(const trlda_docindex *x, int top_n)
+{
     if (top_n < 1 || top_n > trlda::kDocIndexMaxTop || (int64_t)top_n > x->n)
         return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(number of indexed documents, 100)]");
+    return TRLDA_OK;
+}
+
+// what every query checks before anything is waited for, drawn, copied or launched
+int docindex_query_checks(const trlda_docindex *x, int top_n)
+{
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
+    if (int rc_arg = docindex_check_top(x, top_n))
+        return rc_arg;
     const int sr = docindex_slab_rows(x);
     if ((x->n + sr - 1) / sr > 65535)                    // (grid dimension y)
         return fail(TRLDA_ERR_ARG, "too many slabs: raise trlda_docindex_set_slab_rows");
@@ -5979,16 +6002,158 @@ int docindex_batch_checks(const trlda_model *m, const trlda_batch *b)
     return batch_matches_model(m, b);
 }
 
-template <int SW>
-int docindex_launch_query(trlda_docindex *x, int B, int top_n, int slab_rows, int slabs)
+// The rows an entry point scores are the whole index, M of its ids, or the M columns of a gamma.  The
+// arguments: ids or a gamma but not both, at least one document, a gamma's columns an int
+int docindex_scored_args(const int64_t *ids, const double *gamma, int64_t M)
 {
-    const size_t lds = trlda::docindex_query_lds(SW, top_n);
+    if (ids && gamma)
+        return fail(TRLDA_ERR_ARG, "the scored rows are either ids or a gamma, not both");
+    if ((ids || gamma) && M < 1)
+        return fail(TRLDA_ERR_ARG, "a list of ids or a gamma needs at least one document");
+    if (gamma && M > INT_MAX)
+        return fail(TRLDA_ERR_ARG, "too many gamma columns in one call");
+    return TRLDA_OK;
+}
+
+// ids on the host, if any: each the id of an indexed document, or TRLDA_ERR_VALUE
+int docindex_check_ids(const trlda_docindex *x, const int64_t *ids, int64_t M)
+{
+    if (ids)
+        for (int64_t i = 0; i < M; ++i)
+            if (ids[i] < 0 || ids[i] >= x->n)
+                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
+    return TRLDA_OK;
+}
+
+// the values of the scored rows: the ids in range, the gamma finite and positive
+int docindex_scored_values(const trlda_docindex *x, const int64_t *ids, const double *gamma, int64_t M)
+{
+    if (int rc_val = docindex_check_ids(x, ids, M))
+        return rc_val;
+    return gamma ? docindex_check_gamma(gamma, (size_t)x->K * (size_t)M) : TRLDA_OK;
+}
+
+// gamma (K x B host, checked) -> rows (B x Kp) on the model's stream, through `stage`
+int docindex_gamma_rows(trlda_docindex *x, const double *gamma, int B, DevBuf<double> &stage, DevBuf<double> &rows)
+{
+    const size_t count = (size_t)x->K * B;
+    int rc = stage.alloc(count);
+    if (!rc) rc = rows.alloc((size_t)B * x->Kp);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(stage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
+    return docindex_launch_rows(x, stage, B, rows);
+}
+
+// The scored rows onto the model's stream: the ids into `ids` (allocated by the caller, before its
+// ensure_dynamic_lds), or the gamma's rows into `rows`.  (The host arrays live until the caller's wait.)
+int docindex_scored_rows(trlda_docindex *x, const int64_t *ids_host, const double *gamma_host, int64_t M,
+                         DevBuf<long long> &ids, DevBuf<double> &stage, DevBuf<double> &rows)
+{
+    if (ids_host)
+        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, x->model->stream));
+    return gamma_host ? docindex_gamma_rows(x, gamma_host, (int)M, stage, rows) : TRLDA_OK;
+}
+
+// Labels on the host, one per indexed document: each in [lowest, C), or TRLDA_ERR_VALUE with `message`;
+// members[c]: the documents of label c >= 0
+int docindex_count_labels(const trlda_docindex *x, const int32_t *labels, int lowest, int C, const char *message,
+                          std::vector<int64_t> &members)
+{
+    members.assign((size_t)C, 0);
+    for (int64_t d = 0; d < x->n; ++d) {
+        const int32_t l = labels[d];
+        if (l < lowest || l >= C)
+            return fail(TRLDA_ERR_VALUE, message);
+        if (l >= 0)
+            ++members[(size_t)l];
+    }
+    return TRLDA_OK;
+}
+
+// The stable counting sort of the index's ids by label (cluster_kernels.h): the blocks' counts and
+// their prefix sums (count, off), the labels' runs and chunks (start, size, cstart), and where the
+// scatter puts the ids (order).  The hist pass touches count alone, the scatter off and order, the
+// prefix pass the rest; each caller allocates what its passes touch.  cluster and group_moments run
+// all three and get the N ids in label order.  silhouette has a prefix kernel of its own that starts
+// every label's run on a tile of 16: its off are padded offsets, its order the P padded positions
+// (set to -1 first), and it has no start or cstart.
+struct LabelSort {
+    DevBuf<int> count;
+    DevBuf<long long> off, start, size, cstart, order;
+};
+
+int label_sort_hist(trlda_docindex *x, LabelSort &s, const int *label, int C)
+{
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
+                       (size_t)C * sizeof(int), x->model->stream, N, C, nb, label, s.count.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int label_sort_prefix(trlda_docindex *x, LabelSort &s, int C)
+{
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    hipLaunchKernelGGL(trlda::cluster_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, x->model->stream, N, C,
+                       nb, s.count.get(), s.off.get(), s.start.get(), s.size.get(), s.cstart.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+int label_sort_scatter(trlda_docindex *x, LabelSort &s, const int *label, int C)
+{
+    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
+    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
+                       (size_t)C * sizeof(long long), x->model->stream, N, C, nb, label, s.off.get(), s.order.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The sums of the n rows at `rows` (n x Kp) into `scale` on the model's stream: what theta^ of a
+// cosine index divides by
+int docindex_launch_scale(trlda_docindex *x, const double *rows, long long n, double *scale)
+{
+    constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
+    hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)),
+                       dim3(trlda::kTopicDocsThreads), 0, x->model->stream, x->K, x->Kp, n, rows, scale);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// ... into a fresh `scale`.  A hellinger index needs none: `scale` stays empty.
+int docindex_scale(trlda_docindex *x, const double *rows, long long n, DevBuf<double> &scale)
+{
+    if (x->measure == 0)
+        return TRLDA_OK;
+    int rc = scale.alloc((size_t)n);
+    return rc ? rc : docindex_launch_scale(x, rows, n, scale);
+}
+
+template <int SW>
+int docindex_launch_query(trlda_docindex *x, const double *qrows, int B, int top, int slab_rows, int slabs)
+{
+    const size_t lds = trlda::docindex_query_lds(SW, top);
     int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::docindex_query_kernel<SW>), lds);
     if (rc)
         return rc;
     hipLaunchKernelGGL(trlda::docindex_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
-                       dim3(trlda::kDocIndexThreads), lds, x->model->stream, x->Kp, (long long)x->n, B, top_n,
-                       slab_rows, x->rows, x->qrows, x->cand_s, x->cand_i);
+                       dim3(trlda::kDocIndexThreads), lds, x->model->stream, x->Kp, (long long)x->n, B, top,
+                       slab_rows, x->rows, qrows, x->cand_s, x->cand_i);
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// The B rows at `qrows` against every slab, then the slabs' lists merged into x->out_i / x->out_s
+// (B x top): 128 query rows per workgroup while their lists fit beside the operands, 64 beyond
+int docindex_search(trlda_docindex *x, const double *qrows, int B, int top, int slab_rows, int slabs)
+{
+    int rc = top <= trlda::kDocIndexWideMaxTop ? docindex_launch_query<2>(x, qrows, B, top, slab_rows, slabs)
+                                               : docindex_launch_query<1>(x, qrows, B, top, slab_rows, slabs);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(B), dim3(trlda::kDocIndexThreads), 0, x->model->stream,
+                       B, top, slabs, x->cand_s, x->cand_i, x->out_i, x->out_s);
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
@@ -6006,17 +6171,7 @@ int docindex_query_device(trlda_docindex *x, const double *gamma_dev, int B, int
     if (!rc) rc = x->out_s.grow(cells);
     if (!rc) rc = x->out_i.grow(cells);
     if (!rc) rc = docindex_launch_rows(x, gamma_dev, B, x->qrows);
-    if (rc)
-        return rc;
-    // (128 query rows per workgroup while their lists fit beside the operands, 64 beyond)
-    rc = top_n <= trlda::kDocIndexWideMaxTop ? docindex_launch_query<2>(x, B, top_n, sr, slabs)
-                                             : docindex_launch_query<1>(x, B, top_n, sr, slabs);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(B), dim3(trlda::kDocIndexThreads), 0, x->model->stream,
-                       B, top_n, slabs, x->cand_s, x->cand_i, x->out_i, x->out_s);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return rc ? rc : docindex_search(x, x->qrows, B, top_n, sr, slabs);
 }
 
 // the results to the host; waits
@@ -6027,10 +6182,7 @@ int docindex_download(trlda_docindex *x, int B, int top_n, int64_t *ids_out, dou
     trlda_model *m = x->model;
     hipError_t e1 = hipMemcpyAsync(ids_out, x->out_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(sim_out, x->out_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // namespace
@@ -6051,7 +6203,7 @@ int trlda_docindex_create(trlda_model *m, int measure, trlda_docindex **out)
     x->model = m;
     x->measure = measure;
     x->K = m->K;
-    x->Kp = (m->K + 3) / 4 * 4;
+    x->Kp = pad4(m->K);
     *out = x;
     return TRLDA_OK;
 }
@@ -6218,9 +6370,7 @@ int trlda_docindex_read_rows(trlda_docindex *x, int64_t first, int64_t count, do
     hipError_t e1 = hipMemcpy2DAsync(rows_out, (size_t)x->K * sizeof(double), x->rows + (size_t)first * x->Kp,
                                      (size_t)x->Kp * sizeof(double), (size_t)x->K * sizeof(double), (size_t)count,
                                      hipMemcpyDeviceToHost, x->model->stream);
-    hipError_t e2 = hipStreamSynchronize(x->model->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    return TRLDA_OK;
+    return wait_for_copies(x->model, {e1});
 }
 
 int trlda_docindex_destroy(trlda_docindex *x)
@@ -6236,27 +6386,6 @@ int trlda_docindex_destroy(trlda_docindex *x)
 
 // ---- topic summaries of an indexed corpus (csrc/topicdocs_kernels.h) ----
 
-namespace {
-
-// The rows' sums into `scale` (N doubles) on the model's stream: what theta^ of a cosine index divides
-// by.  A hellinger index needs none: `scale` stays empty.
-int topicdocs_scale(trlda_docindex *x, DevBuf<double> &scale)
-{
-    if (x->measure == 0)
-        return TRLDA_OK;
-    int rc = scale.alloc((size_t)x->n);
-    if (rc)
-        return rc;
-    constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
-    hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((unsigned)((x->n + per_wg - 1) / per_wg)),
-                       dim3(trlda::kTopicDocsThreads), 0, x->model->stream, x->K, x->Kp, (long long)x->n,
-                       x->rows.get(), scale.get());
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int trlda_docindex_topic_documents(trlda_docindex *x, int top_n, int64_t *ids_out, double *theta_out)
@@ -6264,10 +6393,10 @@ int trlda_docindex_topic_documents(trlda_docindex *x, int top_n, int64_t *ids_ou
     static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
     if (!x || !ids_out)
         return fail(TRLDA_ERR_ARG, "NULL index / ids");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
-    if (top_n < 1 || top_n > trlda::kDocIndexMaxTop || (int64_t)top_n > x->n)
-        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(number of indexed documents, 100)]");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
+    if (int rc_arg = docindex_check_top(x, top_n))
+        return rc_arg;
     const int sr = docindex_slab_rows(x), K = x->K;
     const int64_t slabs = (x->n + sr - 1) / sr;
     const int ktiles = (K + trlda::kTopicDocsSelTopics - 1) / trlda::kTopicDocsSelTopics;
@@ -6280,8 +6409,8 @@ int trlda_docindex_topic_documents(trlda_docindex *x, int top_n, int64_t *ids_ou
     const size_t cells = (size_t)K * top_n;
     DevBuf<double> scale, cand_v, out_v;
     DevBuf<long long> cand_i, out_i;
-    if ((rc = topicdocs_scale(x, scale)) || (rc = cand_v.alloc(cells * slabs)) || (rc = cand_i.alloc(cells * slabs)) ||
-        (rc = out_v.alloc(cells)) || (rc = out_i.alloc(cells)))
+    if ((rc = docindex_scale(x, x->rows, x->n, scale)) || (rc = cand_v.alloc(cells * slabs)) ||
+        (rc = cand_i.alloc(cells * slabs)) || (rc = out_v.alloc(cells)) || (rc = out_i.alloc(cells)))
         return rc;
     const size_t lds = trlda::topicdocs_select_lds(top_n);
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topicdocs_select_kernel), lds)))
@@ -6298,9 +6427,7 @@ int trlda_docindex_topic_documents(trlda_docindex *x, int top_n, int64_t *ids_ou
     hipError_t e2 = theta_out ? hipMemcpyAsync(theta_out, out_v, cells * sizeof(double), hipMemcpyDeviceToHost,
                                                m->stream)
                               : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_docindex_set_moment_chunk(trlda_docindex *x, int rows)
@@ -6315,8 +6442,8 @@ int trlda_docindex_topic_moments(trlda_docindex *x, double *mean_out, double *sc
 {
     if (!x || !mean_out || !scatter_out)
         return fail(TRLDA_ERR_ARG, "NULL index / mean / scatter");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     const int K = x->K;
     const long long N = x->n;
     const long long cr = x->moment_chunk > 0 ? x->moment_chunk : trlda::topicdocs_chunk_rows(K, N);
@@ -6333,8 +6460,8 @@ int trlda_docindex_topic_moments(trlda_docindex *x, double *mean_out, double *sc
     hipStream_t stream = m->stream;
     const dim3 block(trlda::kTopicDocsThreads);
     DevBuf<double> scale, mpart, mean, part, out;
-    if ((rc = topicdocs_scale(x, scale)) || (rc = mpart.alloc((size_t)mblocks * K)) || (rc = mean.alloc(K)) ||
-        (rc = part.alloc((size_t)chunks * n)) || (rc = out.alloc(n)))
+    if ((rc = docindex_scale(x, x->rows, x->n, scale)) || (rc = mpart.alloc((size_t)mblocks * K)) ||
+        (rc = mean.alloc(K)) || (rc = part.alloc((size_t)chunks * n)) || (rc = out.alloc(n)))
         return rc;
     hipLaunchKernelGGL(trlda::topicdocs_mean_kernel, dim3((unsigned)mblocks), block, 0, stream, K, x->Kp, N,
                        x->measure, x->rows.get(), scale.get(), mpart.get());
@@ -6352,9 +6479,7 @@ int trlda_docindex_topic_moments(trlda_docindex *x, double *mean_out, double *sc
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(mean_out, mean, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(scatter_out, out, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"
@@ -6407,12 +6532,9 @@ int trlda_docindex_query_likelihood(trlda_docindex *x, const trlda_batch *b, int
     if ((rc = lambda_rowsums(m, &rs)))
         return rc;
     std::vector<double> rs_host((size_t)K);
-    {
-        hipError_t e1 = hipMemcpyAsync(rs_host.data(), rs, (size_t)K * sizeof(double), hipMemcpyDeviceToHost,
-                                       m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        HIP_TRY(e1); HIP_TRY(e2);
-    }
+    hipError_t e0 = hipMemcpyAsync(rs_host.data(), rs, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    if ((rc = wait_for_copies(m, {e0})))
+        return rc;
     for (int k = 0; k < K; ++k)
         if (!(rs_host[(size_t)k] > 0.0) || !std::isfinite(rs_host[(size_t)k]))
             return fail(TRLDA_ERR_ARG, "query likelihood needs finite, positive row sums of lambda");
@@ -6421,8 +6543,8 @@ int trlda_docindex_query_likelihood(trlda_docindex *x, const trlda_batch *b, int
     DevBuf<double> wtab, wcnt, scale, cand_s, out_s;
     DevBuf<long long> cand_i, out_i;
     if ((rc = toff.alloc((size_t)B + 1)) || (rc = wtab.alloc(wrows * Kp)) || (rc = wcnt.alloc(wrows)) ||
-        (rc = topicdocs_scale(x, scale)) || (rc = cand_s.alloc(cells * lists)) || (rc = cand_i.alloc(cells * lists)) ||
-        (rc = out_s.alloc(cells)) || (rc = out_i.alloc(cells)))
+        (rc = docindex_scale(x, x->rows, x->n, scale)) || (rc = cand_s.alloc(cells * lists)) ||
+        (rc = cand_i.alloc(cells * lists)) || (rc = out_s.alloc(cells)) || (rc = out_i.alloc(cells)))
         return rc;
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::querylik_score_kernel), lds)))
         return rc;
@@ -6448,10 +6570,7 @@ int trlda_docindex_query_likelihood(trlda_docindex *x, const trlda_batch *b, int
     (void)batch_end(m, b);
     hipError_t e1 = hipMemcpyAsync(ids_out, out_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(loglik_out, out_s, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"
@@ -6463,8 +6582,8 @@ namespace {
 // what both calls check before anything is waited for, copied or launched
 int cluster_checks(const trlda_docindex *x, int C)
 {
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (C < 1 || C > trlda::kClusterMaxClusters || (int64_t)C > x->n)
         return fail(TRLDA_ERR_ARG, "the number of clusters must lie in [1, min(number of indexed documents, " +
                                        std::to_string(trlda::kClusterMaxClusters) + ")]");
@@ -6474,22 +6593,11 @@ int cluster_checks(const trlda_docindex *x, int C)
 // The temporaries of one call, freed when it returns
 struct ClusterWork {
     DevBuf<double> gstage, crows, sim, part, scale, theta;
-    DevBuf<int> label[2], changed, count;
-    DevBuf<long long> total, off, start, size, cstart, order;
+    DevBuf<int> label[2], changed;
+    DevBuf<long long> total;
+    LabelSort sort;
     int cur = 0;                         // label[cur]: the latest assignment
 };
-
-// gamma (K x B host, checked) -> rows (B x Kp) on the model's stream, through `stage`
-int cluster_rows(trlda_docindex *x, const double *gamma, int B, DevBuf<double> &stage, DevBuf<double> &rows)
-{
-    const size_t count = (size_t)x->K * B;
-    int rc = stage.alloc(count);
-    if (!rc) rc = rows.alloc((size_t)B * x->Kp);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(stage, gamma, count * sizeof(double), hipMemcpyHostToDevice, x->model->stream));
-    return docindex_launch_rows(x, stage, B, rows);
-}
 
 // One assignment of the n rows at `docs` to the C centroid rows on the model's stream: into the other
 // label buffer, which becomes the latest; with `count` the labels that differ from the latest so far
@@ -6529,50 +6637,30 @@ int cluster_assign_buffers(trlda_docindex *x, ClusterWork &w, long long n)
 }
 
 // The first two passes of the counting sort of the index's ids by the latest labels: the blocks'
-// counts and their prefix sums (w.count, w.off) and the clusters' runs and chunks (w.start, w.size,
-// w.cstart).
+// counts and their prefix sums and the clusters' runs and chunks.
 int cluster_count(trlda_docindex *x, ClusterWork &w, int C)
 {
-    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
-    hipStream_t stream = x->model->stream;
-    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
-                       (size_t)C * sizeof(int), stream, N, C, nb, w.label[w.cur].get(), w.count.get());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(trlda::cluster_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, N, C, nb,
-                       w.count.get(), w.off.get(), w.start.get(), w.size.get(), w.cstart.get());
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    int rc = label_sort_hist(x, w.sort, w.label[w.cur], C);
+    return rc ? rc : label_sort_prefix(x, w.sort, C);
 }
 
-// The stable counting sort itself: after cluster_count the ids take their places in w.order.
-int cluster_sort(trlda_docindex *x, ClusterWork &w, int C)
-{
-    int rc = cluster_count(x, w, C);
-    if (rc)
-        return rc;
-    const long long N = x->n, nb = trlda::cluster_sort_blocks(N);
-    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
-                       (size_t)C * sizeof(long long), x->model->stream, N, C, nb, w.label[w.cur].get(), w.off.get(),
-                       w.order.get());
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
-}
-
-// m_c = S_c / |S_c| from the latest labels, into w.crows
+// m_c = S_c / |S_c| from the latest labels, into w.crows: the sort itself, the clusters' sums, the means
 int cluster_update(trlda_docindex *x, ClusterWork &w, int C)
 {
-    int rc = cluster_sort(x, w, C);
+    int rc = cluster_count(x, w, C);
+    if (!rc) rc = label_sort_scatter(x, w.sort, w.label[w.cur], C);
     if (rc)
         return rc;
     hipStream_t stream = x->model->stream;
+    const LabelSort &s = w.sort;
     const long long chunks = trlda::cluster_max_chunks(x->n, C);
     hipLaunchKernelGGL(trlda::cluster_sum_kernel, dim3((unsigned)chunks), dim3(trlda::kClusterThreads), 0, stream,
-                       x->Kp, C, x->rows.get(), w.order.get(), w.start.get(), w.size.get(), w.cstart.get(),
+                       x->Kp, C, x->rows.get(), s.order.get(), s.start.get(), s.size.get(), s.cstart.get(),
                        w.part.get());
     HIP_TRY(hipGetLastError());
     constexpr int per_wg = trlda::kClusterThreads / trlda::kWave;
     hipLaunchKernelGGL(trlda::cluster_normalise_kernel, dim3((C + per_wg - 1) / per_wg), dim3(trlda::kClusterThreads),
-                       0, stream, x->K, x->Kp, C, w.size.get(), w.cstart.get(), w.part.get(), w.crows.get());
+                       0, stream, x->K, x->Kp, C, s.size.get(), s.cstart.get(), w.part.get(), w.crows.get());
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
@@ -6606,9 +6694,9 @@ int trlda_docindex_assign(trlda_docindex *x, const double *centroids, int C, con
         return rc;
     ClusterWork w;
     DevBuf<double> qstage, qrows;
-    if ((rc = cluster_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, n)))
+    if ((rc = docindex_gamma_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, n)))
         return rc;
-    if (gamma && (rc = cluster_rows(x, gamma, B, qstage, qrows)))
+    if (gamma && (rc = docindex_gamma_rows(x, gamma, B, qstage, qrows)))
         return rc;
     if ((rc = cluster_assign(x, w, gamma ? qrows.get() : x->rows.get(), n, C, false)))
         return rc;
@@ -6617,10 +6705,7 @@ int trlda_docindex_assign(trlda_docindex *x, const double *centroids, int C, con
     hipError_t e2 = sim_out ? hipMemcpyAsync(sim_out, w.sim, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
                                              m->stream)
                             : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_iter, int32_t *labels_out,
@@ -6645,12 +6730,13 @@ int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_
         return rc;
     hipStream_t stream = m->stream;
     ClusterWork w;
-    if ((rc = cluster_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, N)) ||
-        (rc = w.count.alloc((size_t)C * nb)) || (rc = w.off.alloc((size_t)C * nb)) || (rc = w.start.alloc(C)) ||
-        (rc = w.size.alloc(C)) || (rc = w.cstart.alloc((size_t)C + 1)) || (rc = w.theta.alloc((size_t)K * C)))
+    if ((rc = docindex_gamma_rows(x, centroids, C, w.gstage, w.crows)) || (rc = cluster_assign_buffers(x, w, N)) ||
+        (rc = w.sort.count.alloc((size_t)C * nb)) || (rc = w.sort.off.alloc((size_t)C * nb)) ||
+        (rc = w.sort.start.alloc(C)) || (rc = w.sort.size.alloc(C)) || (rc = w.sort.cstart.alloc((size_t)C + 1)) ||
+        (rc = w.theta.alloc((size_t)K * C)))
         return rc;
     // (only an update sorts the ids and sums their rows)
-    if (max_iter > 0 && ((rc = w.order.alloc((size_t)N)) ||
+    if (max_iter > 0 && ((rc = w.sort.order.alloc((size_t)N)) ||
                          (rc = w.part.alloc((size_t)trlda::cluster_max_chunks(N, C) * x->Kp))))
         return rc;
     if (x->measure != 0 && (rc = w.scale.alloc(C)))
@@ -6664,9 +6750,9 @@ int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_
             return rc;
         ++iterations;
         long long changed = -1;
-        hipError_t e1 = hipMemcpyAsync(&changed, w.total, sizeof(long long), hipMemcpyDeviceToHost, stream);
-        hipError_t e2 = hipStreamSynchronize(stream);
-        HIP_TRY(e1); HIP_TRY(e2);
+        hipError_t e0 = hipMemcpyAsync(&changed, w.total, sizeof(long long), hipMemcpyDeviceToHost, stream);
+        if ((rc = wait_for_copies(m, {e0})))
+            return rc;
         if (changed == 0) {
             converged = 1;
             break;
@@ -6675,13 +6761,8 @@ int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_
     // the sizes under the returned labels; theta^ of the final rows
     if ((rc = cluster_count(x, w, C)))
         return rc;
-    if (x->measure != 0) {
-        constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
-        hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((C + per_wg - 1) / per_wg),
-                           dim3(trlda::kTopicDocsThreads), 0, stream, K, x->Kp, (long long)C, w.crows.get(),
-                           w.scale.get());
-        HIP_TRY(hipGetLastError());
-    }
+    if (x->measure != 0 && (rc = docindex_launch_scale(x, w.crows, C, w.scale)))
+        return rc;
     const size_t cells = (size_t)K * C;
     hipLaunchKernelGGL(trlda::cluster_theta_kernel,
                        dim3((unsigned)((cells + trlda::kClusterThreads - 1) / trlda::kClusterThreads)),
@@ -6692,13 +6773,12 @@ int trlda_docindex_cluster(trlda_docindex *x, int C, double *centroids, int max_
                                    stream);
     hipError_t e2 = sim_out ? hipMemcpyAsync(sim_out, w.sim, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream)
                             : hipSuccess;
-    hipError_t e3 = sizes_out ? hipMemcpyAsync(sizes_out, w.size, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                               stream)
+    hipError_t e3 = sizes_out ? hipMemcpyAsync(sizes_out, w.sort.size, (size_t)C * sizeof(int64_t),
+                                               hipMemcpyDeviceToHost, stream)
                               : hipSuccess;
     hipError_t e4 = hipMemcpyAsync(centroids, w.theta, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e5 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
-    HIP_TRY(hipGetLastError());
+    if ((rc = wait_for_copies(m, {e1, e2, e3, e4})))
+        return rc;
     *iterations_out = iterations;
     *converged_out = converged;
     return TRLDA_OK;
@@ -6716,8 +6796,8 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, labels int32");
     if (!x || !labels_host || !sil_out)
         return fail(TRLDA_ERR_ARG, "NULL index / labels / silhouette");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (C < 2 || C > trlda::kClusterMaxClusters)
         return fail(TRLDA_ERR_ARG, "the number of label values must lie in [2, " +
                                        std::to_string(trlda::kClusterMaxClusters) + "]");
@@ -6729,13 +6809,9 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
     if (blocks > INT_MAX || nb > INT_MAX)                // (grid dimension x)
         return fail(TRLDA_ERR_ARG, "too many rows to score in one call");
     // the labels and ids, counted on the host
-    std::vector<long long> members((size_t)C, 0);
-    for (long long d = 0; d < N; ++d) {
-        const int32_t lab = labels_host[d];
-        if (lab < 0 || lab >= C)
-            return fail(TRLDA_ERR_VALUE, "a label lies outside [0, C)");
-        ++members[(size_t)lab];
-    }
+    std::vector<int64_t> members;
+    if (int rc_val = docindex_count_labels(x, labels_host, 0, C, "a label lies outside [0, C)", members))
+        return rc_val;
     long long padded = 0;
     int nonempty = 0;
     for (int c = 0; c < C; ++c) {
@@ -6744,21 +6820,21 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
     }
     if (nonempty < 2)
         return fail(TRLDA_ERR_VALUE, "a silhouette needs at least two clusters with members");
-    if (ids_host)
-        for (int64_t i = 0; i < M; ++i)
-            if (ids_host[i] < 0 || ids_host[i] >= N)
-                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
+    if (int rc_val = docindex_check_ids(x, ids_host, M))
+        return rc_val;
     const long long P = trlda::silhouette_positions(padded);
     trlda_model *m = x->model;
     int rc = check_model(m);
     if (rc)
         return rc;
     hipStream_t stream = m->stream;
-    DevBuf<int> label, count, flush, nbr;
-    DevBuf<long long> ids, off, size, pos;
+    DevBuf<int> label, flush, nbr;
+    DevBuf<long long> ids;
+    LabelSort sort;                      // (the padded form: count, off, size and P positions in order)
     DevBuf<double> sil, a, b;
-    if ((rc = label.alloc((size_t)N)) || (rc = count.alloc((size_t)C * nb)) || (rc = off.alloc((size_t)C * nb)) ||
-        (rc = size.alloc(C)) || (rc = pos.alloc((size_t)P)) || (rc = flush.alloc((size_t)(P / 16))) ||
+    if ((rc = label.alloc((size_t)N)) || (rc = sort.count.alloc((size_t)C * nb)) ||
+        (rc = sort.off.alloc((size_t)C * nb)) || (rc = sort.size.alloc(C)) || (rc = sort.order.alloc((size_t)P)) ||
+        (rc = flush.alloc((size_t)(P / 16))) ||
         (rc = sil.alloc((size_t)rows)) || (rc = a.alloc((size_t)rows)) || (rc = b.alloc((size_t)rows)) ||
         (rc = nbr.alloc((size_t)rows)))
         return rc;
@@ -6772,21 +6848,20 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
     if (ids_host)
         HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
     // every position a padding one, no tile a cluster's last: all bits set is -1
-    HIP_TRY(hipMemsetAsync(pos, 0xFF, (size_t)P * sizeof(long long), stream));
+    HIP_TRY(hipMemsetAsync(sort.order, 0xFF, (size_t)P * sizeof(long long), stream));
     HIP_TRY(hipMemsetAsync(flush, 0xFF, (size_t)(P / 16) * sizeof(int), stream));
-    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
-                       (size_t)C * sizeof(int), stream, N, C, nb, label.get(), count.get());
-    HIP_TRY(hipGetLastError());
+    // the counting sort with a prefix pass of its own: the runs start on tiles, the tiles' last are marked
+    if ((rc = label_sort_hist(x, sort, label, C)))
+        return rc;
     hipLaunchKernelGGL(trlda::silhouette_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, C, nb,
-                       count.get(), off.get(), size.get(), flush.get());
+                       sort.count.get(), sort.off.get(), sort.size.get(), flush.get());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
-                       (size_t)C * sizeof(long long), stream, N, C, nb, label.get(), off.get(), pos.get());
-    HIP_TRY(hipGetLastError());
+    if ((rc = label_sort_scatter(x, sort, label, C)))
+        return rc;
     hipLaunchKernelGGL(trlda::silhouette_pairs_kernel, dim3((unsigned)blocks), dim3(trlda::kSilhouetteThreads), lds,
                        stream, x->Kp, rows, P, x->measure, x->rows.get(),
-                       ids_host ? ids.get() : (const long long *)nullptr, label.get(), size.get(), pos.get(),
-                       flush.get(), sil.get(), a.get(), b.get(), nbr.get());
+                       ids_host ? ids.get() : (const long long *)nullptr, label.get(), sort.size.get(),
+                       sort.order.get(), flush.get(), sil.get(), a.get(), b.get(), nbr.get());
     HIP_TRY(hipGetLastError());
     const size_t bytes = (size_t)rows * sizeof(double);
     hipError_t e1 = hipMemcpyAsync(sil_out, sil, bytes, hipMemcpyDeviceToHost, stream);
@@ -6795,10 +6870,7 @@ int trlda_docindex_silhouette(trlda_docindex *x, const int32_t *labels_host, int
     hipError_t e4 = neighbour_out ? hipMemcpyAsync(neighbour_out, nbr, (size_t)rows * sizeof(int32_t),
                                                    hipMemcpyDeviceToHost, stream)
                                   : hipSuccess;
-    hipError_t e5 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2, e3, e4});
 }
 
 }  // extern "C"
@@ -6814,14 +6886,10 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
     static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
     if (!x || !indptr_out)
         return fail(TRLDA_ERR_ARG, "NULL index / indptr");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
-    if (ids_host && gamma_host)
-        return fail(TRLDA_ERR_ARG, "the scored rows are either ids or a gamma, not both");
-    if ((ids_host || gamma_host) && M < 1)
-        return fail(TRLDA_ERR_ARG, "a list of ids or a gamma needs at least one document");
-    if (gamma_host && M > INT_MAX)
-        return fail(TRLDA_ERR_ARG, "too many gamma columns in one call");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
+    if (int rc_arg = docindex_scored_args(ids_host, gamma_host, M))
+        return rc_arg;
     if (capacity < 0)
         return fail(TRLDA_ERR_ARG, "the capacity must not be negative");
     if (val_out && !ids_out)
@@ -6839,13 +6907,8 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
         return fail(TRLDA_ERR_ARG, "too many rows or slabs: raise trlda_docindex_set_slab_rows");
     if (!(radius >= 0.0) || !std::isfinite(radius))
         return fail(TRLDA_ERR_VALUE, "the radius should be finite and not negative");
-    if (ids_host)
-        for (int64_t i = 0; i < M; ++i)
-            if (ids_host[i] < 0 || ids_host[i] >= N)
-                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
-    if (gamma_host)
-        if (int rc_val = docindex_check_gamma(gamma_host, (size_t)x->K * (size_t)M))
-            return rc_val;
+    if (int rc_val = docindex_scored_values(x, ids_host, gamma_host, M))
+        return rc_val;
     trlda_model *m = x->model;
     int rc = check_model(m);
     if (rc)
@@ -6864,9 +6927,7 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
         (rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::neighbors_fill_kernel), lds)))
         return rc;
     // (ids_host and gamma_host live until the synchronisation below)
-    if (ids_host)
-        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-    if (gamma_host && (rc = cluster_rows(x, gamma_host, (int)M, gstage, qrows)))
+    if ((rc = docindex_scored_rows(x, ids_host, gamma_host, M, ids, gstage, qrows)))
         return rc;
     const double *xrows = gamma_host ? qrows.get() : x->rows.get();
     const long long *ids_dev = ids_host ? ids.get() : (const long long *)nullptr;
@@ -6878,13 +6939,10 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
     hipLaunchKernelGGL(trlda::neighbors_scan_kernel, dim3(1), dim3(trlda::kNeighborsScanThreads), 0, stream, rows,
                        nslab, count.get(), off.get(), indptr.get());
     HIP_TRY(hipGetLastError());
-    {
-        hipError_t e1 = hipMemcpyAsync(indptr_out, indptr, ((size_t)rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                       stream);
-        hipError_t e2 = hipStreamSynchronize(stream);
-        HIP_TRY(e1); HIP_TRY(e2);
-        HIP_TRY(hipGetLastError());
-    }
+    hipError_t e0 = hipMemcpyAsync(indptr_out, indptr, ((size_t)rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   stream);
+    if ((rc = wait_for_copies(m, {e0})))
+        return rc;
     const int64_t total = indptr_out[rows];
     // count only; or the caller's arrays are too small (it compares indptr_out[M] with its capacity)
     if (!ids_out || total > capacity || total == 0)
@@ -6899,10 +6957,7 @@ int trlda_docindex_neighbors(trlda_docindex *x, double radius, const int64_t *id
     hipError_t e2 = val_out ? hipMemcpyAsync(val_out, hit_val, (size_t)total * sizeof(double), hipMemcpyDeviceToHost,
                                              stream)
                             : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"
@@ -6917,8 +6972,8 @@ int trlda_docindex_mst_sweep(trlda_docindex *x, const int32_t *comp_host, const 
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, components int32");
     if (!x || !comp_host || !best_out || !weight_out)
         return fail(TRLDA_ERR_ARG, "NULL index / components / best / weight");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (x->n > INT_MAX)                                  // (the kernel's columns are ints)
         return fail(TRLDA_ERR_ARG, "too many indexed documents for a spanning tree");
     // the slab: the A/B switch, else the default for this size (the 2048 rows of a search would leave
@@ -6954,10 +7009,7 @@ int trlda_docindex_mst_sweep(trlda_docindex *x, const int32_t *comp_host, const 
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(best_out, best, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(weight_out, weight, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"
@@ -7023,8 +7075,8 @@ int trlda_docindex_group_moments(trlda_docindex *x, const int32_t *labels_host, 
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "ids are int64, labels int32");
     if (!x || !labels_host || !mean_out || !wsum_out || !count_out)
         return fail(TRLDA_ERR_ARG, "NULL index / labels / mean / weight sums / counts");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (G < 1 || G > trlda::kClusterMaxClusters - 1)
         return fail(TRLDA_ERR_ARG, "the number of groups must lie in [1, " +
                                        std::to_string(trlda::kClusterMaxClusters - 1) + "]");
@@ -7036,16 +7088,11 @@ int trlda_docindex_group_moments(trlda_docindex *x, const int32_t *labels_host, 
     if (nb > INT_MAX || chunks > INT_MAX || fblocks > (size_t)INT_MAX)   // (grid dimension x)
         return fail(TRLDA_ERR_ARG, "too many rows or groups for one call");
     // the labels, counted on the host; -1 takes the slot past the last group
+    std::vector<int64_t> members;
+    if (int rc_val = docindex_count_labels(x, labels_host, -1, G, "a label lies outside [-1, G)", members))
+        return rc_val;
     std::vector<int32_t> lab((size_t)N);
-    std::vector<int64_t> members((size_t)G, 0);
-    for (long long d = 0; d < N; ++d) {
-        const int32_t l = labels_host[d];
-        if (l < -1 || l >= G)
-            return fail(TRLDA_ERR_VALUE, "a label lies outside [-1, G)");
-        lab[(size_t)d] = l < 0 ? G : l;
-        if (l >= 0)
-            ++members[(size_t)l];
-    }
+    std::replace_copy(labels_host, labels_host + N, lab.begin(), -1, G);
     int rc = effects_check_weights(weights_host, N);
     if (rc)
         return rc;
@@ -7053,13 +7100,14 @@ int trlda_docindex_group_moments(trlda_docindex *x, const int32_t *labels_host, 
     if ((rc = check_model(m)))
         return rc;
     hipStream_t stream = m->stream;
-    DevBuf<int> label, count;
-    DevBuf<long long> off, start, size, cstart, order;
+    DevBuf<int> label;
+    LabelSort s;
     DevBuf<double> scale, w, part, wpart, mean, wsum, ss;
-    if ((rc = label.alloc((size_t)N)) || (rc = count.alloc((size_t)C * nb)) || (rc = off.alloc((size_t)C * nb)) ||
-        (rc = start.alloc(C)) || (rc = size.alloc(C)) || (rc = cstart.alloc((size_t)C + 1)) ||
-        (rc = order.alloc((size_t)N)) || (rc = topicdocs_scale(x, scale)) || (rc = part.alloc((size_t)chunks * K)) ||
-        (rc = wpart.alloc((size_t)chunks)) || (rc = mean.alloc(cells)) || (rc = wsum.alloc(G)))
+    if ((rc = label.alloc((size_t)N)) || (rc = s.count.alloc((size_t)C * nb)) || (rc = s.off.alloc((size_t)C * nb)) ||
+        (rc = s.start.alloc(C)) || (rc = s.size.alloc(C)) || (rc = s.cstart.alloc((size_t)C + 1)) ||
+        (rc = s.order.alloc((size_t)N)) || (rc = docindex_scale(x, x->rows, x->n, scale)) ||
+        (rc = part.alloc((size_t)chunks * K)) || (rc = wpart.alloc((size_t)chunks)) || (rc = mean.alloc(cells)) ||
+        (rc = wsum.alloc(G)))
         return rc;
     if (weights_host && (rc = w.alloc((size_t)N)))
         return rc;
@@ -7070,40 +7118,32 @@ int trlda_docindex_group_moments(trlda_docindex *x, const int32_t *labels_host, 
     if (weights_host)
         HIP_TRY(hipMemcpyAsync(w, weights_host, (size_t)N * sizeof(double), hipMemcpyHostToDevice, stream));
     const double *wd = weights_host ? w.get() : (const double *)nullptr;
-    // the stable counting sort of cluster_kernels.h, launched as trlda_docindex_silhouette launches it
-    hipLaunchKernelGGL(trlda::cluster_hist_kernel, dim3((unsigned)nb), dim3(trlda::kClusterThreads),
-                       (size_t)C * sizeof(int), stream, N, C, nb, label.get(), count.get());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(trlda::cluster_prefix_kernel, dim3(1), dim3(trlda::kClusterThreads), 0, stream, N, C, nb,
-                       count.get(), off.get(), start.get(), size.get(), cstart.get());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(trlda::cluster_scatter_kernel, dim3((unsigned)nb), dim3(trlda::kWave),
-                       (size_t)C * sizeof(long long), stream, N, C, nb, label.get(), off.get(), order.get());
-    HIP_TRY(hipGetLastError());
+    if ((rc = label_sort_hist(x, s, label, C)) || (rc = label_sort_prefix(x, s, C)) ||
+        (rc = label_sort_scatter(x, s, label, C)))
+        return rc;
     const dim3 block(trlda::kEffectsThreads);
     hipLaunchKernelGGL(trlda::effects_group_kernel<false>, dim3((unsigned)chunks), block, 0, stream, K, x->Kp, G,
-                       x->measure, x->rows.get(), scale.get(), wd, order.get(), start.get(), size.get(), cstart.get(),
-                       (const double *)nullptr, part.get(), wpart.get());
+                       x->measure, x->rows.get(), scale.get(), wd, s.order.get(), s.start.get(), s.size.get(),
+                       s.cstart.get(), (const double *)nullptr, part.get(), wpart.get());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(trlda::effects_group_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, K, G, 1,
-                       cstart.get(), part.get(), wpart.get(), mean.get(), wsum.get());
+                       s.cstart.get(), part.get(), wpart.get(), mean.get(), wsum.get());
     HIP_TRY(hipGetLastError());
     if (ss_out) {
         hipLaunchKernelGGL(trlda::effects_group_kernel<true>, dim3((unsigned)chunks), block, 0, stream, K, x->Kp, G,
-                           x->measure, x->rows.get(), scale.get(), wd, order.get(), start.get(), size.get(),
-                           cstart.get(), mean.get(), part.get(), wpart.get());
+                           x->measure, x->rows.get(), scale.get(), wd, s.order.get(), s.start.get(), s.size.get(),
+                           s.cstart.get(), mean.get(), part.get(), wpart.get());
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(trlda::effects_group_finish_kernel, dim3((unsigned)fblocks), block, 0, stream, K, G, 0,
-                           cstart.get(), part.get(), wpart.get(), ss.get(), wsum.get());
+                           s.cstart.get(), part.get(), wpart.get(), ss.get(), wsum.get());
         HIP_TRY(hipGetLastError());
     }
     hipError_t e1 = hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(wsum_out, wsum, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e3 = ss_out ? hipMemcpyAsync(ss_out, ss, cells * sizeof(double), hipMemcpyDeviceToHost, stream)
                            : hipSuccess;
-    hipError_t e4 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    HIP_TRY(hipGetLastError());
+    if ((rc = wait_for_copies(m, {e1, e2, e3})))
+        return rc;
     std::copy(members.begin(), members.end(), count_out);
     return TRLDA_OK;
 }
@@ -7113,12 +7153,12 @@ int trlda_docindex_regress_products(trlda_docindex *x, const double *z_host, int
 {
     if (!x || !z_host || !gram_out || !cross_out)
         return fail(TRLDA_ERR_ARG, "NULL index / design / Gram / cross products");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (P < 1 || P > trlda::kEffectsMaxColumns)
         return fail(TRLDA_ERR_ARG, "the number of design columns must lie in [1, " +
                                        std::to_string(trlda::kEffectsMaxColumns) + "]");
-    const int K = x->K, Pp = (P + 3) / 4 * 4;
+    const int K = x->K, Pp = pad4(P);
     const long long N = x->n;
     const long long cr = x->moment_chunk > 0 ? x->moment_chunk : trlda::effects_chunk_rows(P, K, N);
     const long long chunks = (N + cr - 1) / cr, items = trlda::effects_product_items(P, K);
@@ -7138,7 +7178,7 @@ int trlda_docindex_regress_products(trlda_docindex *x, const double *z_host, int
         return rc;
     hipStream_t stream = m->stream;
     DevBuf<double> z, w, scale, part_g, part_c, gram, cross;
-    if ((rc = effects_upload(x, zpad, Pp, weights_host, z, w)) || (rc = topicdocs_scale(x, scale)) ||
+    if ((rc = effects_upload(x, zpad, Pp, weights_host, z, w)) || (rc = docindex_scale(x, x->rows, x->n, scale)) ||
         (rc = part_g.alloc((size_t)chunks * ng)) || (rc = part_c.alloc((size_t)chunks * nc)) ||
         (rc = gram.alloc(ng)) || (rc = cross.alloc(nc)))
         return rc;
@@ -7152,10 +7192,7 @@ int trlda_docindex_regress_products(trlda_docindex *x, const double *z_host, int
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(gram_out, gram, ng * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(cross_out, cross, nc * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, int P, const double *weights_host,
@@ -7163,12 +7200,12 @@ int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, in
 {
     if (!x || !z_host || !coef_host || !rss_out)
         return fail(TRLDA_ERR_ARG, "NULL index / design / coefficients / residual sums");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (P < 1 || P > trlda::kEffectsMaxColumns)
         return fail(TRLDA_ERR_ARG, "the number of design columns must lie in [1, " +
                                        std::to_string(trlda::kEffectsMaxColumns) + "]");
-    const int K = x->K, Pp = (P + 3) / 4 * 4;
+    const int K = x->K, Pp = pad4(P);
     const long long N = x->n;
     const long long blocks = (N + trlda::kEffectsBlockDocs - 1) / trlda::kEffectsBlockDocs;
     if (blocks > INT_MAX)                                // (grid dimension x)
@@ -7187,7 +7224,7 @@ int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, in
     hipStream_t stream = m->stream;
     DevBuf<double> z, w, coef, scale, part, rss;
     if ((rc = effects_upload(x, zpad, Pp, weights_host, z, w)) || (rc = coef.alloc((size_t)K * Pp)) ||
-        (rc = topicdocs_scale(x, scale)) || (rc = part.alloc((size_t)blocks * K)) || (rc = rss.alloc(K)))
+        (rc = docindex_scale(x, x->rows, x->n, scale)) || (rc = part.alloc((size_t)blocks * K)) || (rc = rss.alloc(K)))
         return rc;
     const size_t lds = trlda::effects_residual_lds();
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::effects_residual_kernel), lds)))
@@ -7203,10 +7240,7 @@ int trlda_docindex_regress_residuals(trlda_docindex *x, const double *z_host, in
                        part.get(), rss.get());
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(rss_out, rss, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e2 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1});
 }
 
 }  // extern "C"
@@ -7220,21 +7254,6 @@ int classify_check_classes(int C)
     if (C < 2 || C > trlda::kClassifyMaxClasses)
         return fail(TRLDA_ERR_ARG, "the number of classes must lie in [2, " +
                                        std::to_string(trlda::kClassifyMaxClasses) + "]");
-    return TRLDA_OK;
-}
-
-// the rows' sums of `rows` (n x Kp) into `scale` on the model's stream; a hellinger index needs none
-int classify_scale(trlda_docindex *x, const double *rows, long long n, DevBuf<double> &scale)
-{
-    if (x->measure == 0)
-        return TRLDA_OK;
-    int rc = scale.alloc((size_t)n);
-    if (rc)
-        return rc;
-    constexpr int per_wg = trlda::kTopicDocsThreads / trlda::kWave;
-    hipLaunchKernelGGL(trlda::topicdocs_scale_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)),
-                       dim3(trlda::kTopicDocsThreads), 0, x->model->stream, x->K, x->Kp, n, rows, scale.get());
-    HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
 
@@ -7269,11 +7288,11 @@ int trlda_docindex_classify_set(trlda_docindex *x, const int32_t *labels_host, i
     static_assert(sizeof(int) == sizeof(int32_t), "labels are int32");
     if (!x || !labels_host || !weight_sum_out || !count_out)
         return fail(TRLDA_ERR_ARG, "NULL index / labels / weight sum / counts");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (int rc_arg = classify_check_classes(C))
         return rc_arg;
-    const int K = x->K, Cp = (C + 3) / 4 * 4;
+    const int K = x->K, Cp = pad4(C);
     const long long N = x->n;
     const long long cr = trlda::classify_chunk_rows(C, K, N), chunks = (N + cr - 1) / cr;
     const long long slab = trlda::classify_slab_rows(x->classify_slab, cr, Cp);
@@ -7281,15 +7300,10 @@ int trlda_docindex_classify_set(trlda_docindex *x, const int32_t *labels_host, i
     // (grid dimensions x, y of a slab's launches)
     if (std::min(slab, N) / trlda::kClassifyBlockDocs + 1 > INT_MAX || std::min(slab / cr, chunks) > 65535)
         return fail(TRLDA_ERR_ARG, "too many rows per slab: lower trlda_docindex_set_classify_slab");
-    std::vector<int64_t> members((size_t)C, 0);
+    std::vector<int64_t> members;
+    if (int rc_val = docindex_count_labels(x, labels_host, -1, C, "a label lies outside [-1, C)", members))
+        return rc_val;
     double omega = 0.0;                                  // the weights of the labelled documents, ascending id
-    for (long long d = 0; d < N; ++d) {
-        const int32_t l = labels_host[d];
-        if (l < -1 || l >= C)
-            return fail(TRLDA_ERR_VALUE, "a label lies outside [-1, C)");
-        if (l >= 0)
-            ++members[(size_t)l];
-    }
     int rc = effects_check_weights(weights_host, N);
     if (rc)
         return rc;
@@ -7315,7 +7329,7 @@ int trlda_docindex_classify_set(trlda_docindex *x, const int32_t *labels_host, i
     f->blocks = blocks;
     const size_t ck = (size_t)C * K;
     if ((rc = f->labels.alloc((size_t)N)) || (weights_host && (rc = f->w.alloc((size_t)N))) ||
-        (rc = classify_scale(x, x->rows.get(), N, f->scale)) ||
+        (rc = docindex_scale(x, x->rows.get(), N, f->scale)) ||
         (rc = f->R.alloc((size_t)std::min(slab, chunks * cr) * Cp)) || (rc = f->part_c.alloc((size_t)chunks * ck)) ||
         (rc = f->part_loss.alloc((size_t)blocks)) || (rc = f->coef.alloc((size_t)C * x->Kp)) ||
         (rc = f->grad.alloc(ck)) || (rc = f->loss.alloc(1)))
@@ -7325,9 +7339,8 @@ int trlda_docindex_classify_set(trlda_docindex *x, const int32_t *labels_host, i
     hipError_t e2 = weights_host ? hipMemcpyAsync(f->w, weights_host, (size_t)N * sizeof(double),
                                                   hipMemcpyHostToDevice, stream)
                                  : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
+    if ((rc = wait_for_copies(m, {e1, e2})))
+        return rc;
     x->fit = std::move(f);
     *weight_sum_out = omega;
     std::copy(members.begin(), members.end(), count_out);
@@ -7388,9 +7401,8 @@ int trlda_docindex_classify_eval(trlda_docindex *x, const double *coef_host, dou
     double loss = 0.0;
     hipError_t e1 = hipMemcpyAsync(&loss, f->loss, sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(grad_out, f->grad, ck * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
+    if ((rc = wait_for_copies(m, {e1, e2})))
+        return rc;
     *loss_out = loss;
     return TRLDA_OK;
 }
@@ -7401,29 +7413,20 @@ int trlda_docindex_classify_predict(trlda_docindex *x, const double *coef_host, 
     static_assert(sizeof(long long) == sizeof(int64_t), "ids are int64");
     if (!x || !coef_host || !labels_out)
         return fail(TRLDA_ERR_ARG, "NULL index / coefficients / labels");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     if (int rc_arg = classify_check_classes(C))
         return rc_arg;
-    if (ids_host && gamma_host)
-        return fail(TRLDA_ERR_ARG, "the scored rows are either ids or a gamma, not both");
-    if ((ids_host || gamma_host) && M < 1)
-        return fail(TRLDA_ERR_ARG, "a list of ids or a gamma needs at least one document");
-    if (gamma_host && M > INT_MAX)
-        return fail(TRLDA_ERR_ARG, "too many gamma columns in one call");
+    if (int rc_arg = docindex_scored_args(ids_host, gamma_host, M))
+        return rc_arg;
     const int K = x->K, Kp = x->Kp;
     const long long N = x->n;
     const long long rows = ids_host || gamma_host ? (long long)M : N;
     const long long blocks = (rows + trlda::kClassifyBlockDocs - 1) / trlda::kClassifyBlockDocs;
     if (blocks > INT_MAX)                                // (grid dimension x)
         return fail(TRLDA_ERR_ARG, "too many rows for one call");
-    if (ids_host)
-        for (int64_t i = 0; i < M; ++i)
-            if (ids_host[i] < 0 || ids_host[i] >= N)
-                return fail(TRLDA_ERR_VALUE, "an id lies outside [0, number of indexed documents)");
-    if (gamma_host)
-        if (int rc_val = docindex_check_gamma(gamma_host, (size_t)K * (size_t)M))
-            return rc_val;
+    if (int rc_val = docindex_scored_values(x, ids_host, gamma_host, M))
+        return rc_val;
     std::vector<double> ccopy;
     const double *cpad = nullptr;
     int rc = effects_padded_rows(coef_host, C, K, Kp, ccopy, &cpad, "the coefficients");
@@ -7444,15 +7447,13 @@ int trlda_docindex_classify_predict(trlda_docindex *x, const double *coef_host, 
         return rc;
     // (ccopy, ids_host and gamma_host live until the synchronisation below)
     HIP_TRY(hipMemcpyAsync(coef, cpad, (size_t)C * Kp * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (ids_host)
-        HIP_TRY(hipMemcpyAsync(ids, ids_host, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-    if (gamma_host && (rc = cluster_rows(x, gamma_host, (int)M, gstage, qrows)))
+    if ((rc = docindex_scored_rows(x, ids_host, gamma_host, M, ids, gstage, qrows)))
         return rc;
     const double *table = gamma_host ? qrows.get() : x->rows.get();
-    if ((rc = classify_scale(x, table, gamma_host ? rows : N, scale)))
+    if ((rc = docindex_scale(x, table, gamma_host ? rows : N, scale)))
         return rc;
     hipLaunchKernelGGL(trlda::classify_forward_kernel<false>, dim3((unsigned)blocks), dim3(trlda::kClassifyThreads),
-                       lds, stream, C, (C + 3) / 4 * 4, Kp, rows, 0LL, x->measure, table, scale.get(),
+                       lds, stream, C, pad4(C), Kp, rows, 0LL, x->measure, table, scale.get(),
                        ids_host ? ids.get() : (const long long *)nullptr, coef.get(), (const int *)nullptr,
                        (const double *)nullptr, (double *)nullptr, (double *)nullptr, label.get(),
                        proba_out ? proba.get() : (double *)nullptr);
@@ -7461,10 +7462,7 @@ int trlda_docindex_classify_predict(trlda_docindex *x, const double *coef_host, 
     hipError_t e2 = proba_out ? hipMemcpyAsync(proba_out, proba, (size_t)rows * C * sizeof(double),
                                                hipMemcpyDeviceToHost, stream)
                               : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"
@@ -7472,20 +7470,6 @@ int trlda_docindex_classify_predict(trlda_docindex *x, const double *coef_host, 
 // ---- a 2-D map of an indexed corpus (csrc/tsne_kernels.h) ----
 
 namespace {
-
-template <int SW>
-int docindex_launch_self(trlda_docindex *x, const double *qrows, int B, int top, int slab_rows, int slabs)
-{
-    const size_t lds = trlda::docindex_query_lds(SW, top);
-    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::docindex_query_kernel<SW>), lds);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(trlda::docindex_query_kernel<SW>, dim3((B + 64 * SW - 1) / (64 * SW), slabs),
-                       dim3(trlda::kDocIndexThreads), lds, x->model->stream, x->Kp, (long long)x->n, B, top,
-                       slab_rows, x->rows, qrows, x->cand_s, x->cand_i);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
-}
 
 // what the neighbour graph checks before anything is waited for, copied or launched
 int docindex_nearest_checks(const trlda_docindex *x, int top_n, int block_rows)
@@ -7525,14 +7509,8 @@ int docindex_nearest_device(trlda_docindex *x, int top_n, int block_rows, DevBuf
         return rc;
     for (int64_t b0 = 0; b0 < x->n; b0 += nb) {
         const int B = (int)std::min<int64_t>(nb, x->n - b0);
-        const double *qrows = x->rows + (size_t)b0 * x->Kp;
-        rc = top <= trlda::kDocIndexWideMaxTop ? docindex_launch_self<2>(x, qrows, B, top, sr, slabs)
-                                               : docindex_launch_self<1>(x, qrows, B, top, sr, slabs);
-        if (rc)
+        if ((rc = docindex_search(x, x->rows + (size_t)b0 * x->Kp, B, top, sr, slabs)))
             return rc;
-        hipLaunchKernelGGL(trlda::docindex_merge_kernel, dim3(B), dim3(trlda::kDocIndexThreads), 0,
-                           x->model->stream, B, top, slabs, x->cand_s, x->cand_i, x->out_i, x->out_s);
-        HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(trlda::tsne_selfdrop_kernel, dim3((B + trlda::kTsneThreads - 1) / trlda::kTsneThreads),
                            dim3(trlda::kTsneThreads), 0, x->model->stream, B, top_n, (long long)b0, x->out_i.get(),
                            x->out_s.get(), nn_i.get(), nn_s.get());
@@ -7667,10 +7645,7 @@ int trlda_docindex_nearest(trlda_docindex *x, int top_n, int block_rows, int64_t
     const size_t cells = (size_t)x->n * top_n;
     hipError_t e1 = hipMemcpyAsync(ids_out, nn_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(sim_out, nn_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_docindex_affinities(trlda_docindex *x, double perplexity, int block_rows, int64_t *ids_out, double *p_out,
@@ -7704,18 +7679,15 @@ int trlda_docindex_affinities(trlda_docindex *x, double perplexity, int block_ro
     hipError_t e1 = hipMemcpyAsync(ids_out, nn_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(p_out, pc, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipError_t e3 = hipMemcpyAsync(beta_out, beta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2, e3});
 }
 
 int trlda_docindex_tsne_project(trlda_docindex *x, const double *mean_host, const double *axes_host, double *y_out)
 {
     if (!x || !mean_host || !axes_host || !y_out)
         return fail(TRLDA_ERR_ARG, "NULL index / mean / axes / map");
-    if (x->n < 1)
-        return fail(TRLDA_ERR_ARG, "the index is empty");
+    if (int rc_arg = docindex_check_filled(x))
+        return rc_arg;
     const long long N = x->n;
     if ((N + 3) / 4 > INT_MAX)
         return fail(TRLDA_ERR_ARG, "too many indexed documents");
@@ -7735,10 +7707,7 @@ int trlda_docindex_tsne_project(trlda_docindex *x, const double *mean_host, cons
                        m->stream, x->K, x->Kp, N, x->measure, x->rows.get(), mean.get(), axes.get(), Y.get());
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(y_out, Y, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1});
 }
 
 int trlda_docindex_tsne_gradient(trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p,
@@ -7764,10 +7733,7 @@ int trlda_docindex_tsne_gradient(trlda_docindex *x, const int64_t *indptr, const
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(grad_out, w.grad, (size_t)2 * w.N * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(kl_out, w.scal.get() + 1, sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_docindex_tsne_run(trlda_docindex *x, const int64_t *indptr, const int64_t *ids, const double *p, double *y,
@@ -7815,10 +7781,7 @@ int trlda_docindex_tsne_run(trlda_docindex *x, const int64_t *indptr, const int6
     }
     hipError_t e1 = hipMemcpyAsync(y, w.Y, (size_t)n2 * sizeof(double), hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipMemcpyAsync(kl_out, kl, (size_t)num_iterations * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e3 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // extern "C"

@@ -143,6 +143,15 @@ class DocumentIndex(object):
             raise RuntimeError("`top_n` should lie between 1 and min(len(index), %d)." % MAX_TOP_N)
         return top_n
 
+    def _scored(self, ids, gamma, N):
+        """(ids as int64 or None, gamma as K x M or None, M) of the documents a call scores: all N, the
+        ids, or a gamma's columns."""
+        rows = _silhouette_ids(ids, N)
+        g = None if gamma is None else self._gamma(gamma)
+        if g is not None and g.shape[1] < 1:
+            raise RuntimeError("`gamma` should hold at least one document.")
+        return rows, g, N if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+
     def _result(self, ids, sim, return_similarity):
         if return_similarity:
             return ids, sim
@@ -497,7 +506,7 @@ class DocumentIndex(object):
         ``radius=0`` finds a duplicate only where the two rows' own dot rounds to at least 1, which a
         unit-length row in floating point need not give: look for duplicates with a small positive
         radius (1e-6 is far above the rounding of a distance at any K)."""
-        handle = self._live()
+        self._live()                                         # (a closed index is reported before a bad radius)
         radius = float(radius)
         if not (radius >= 0.0 and math.isfinite(radius)):
             raise ValueError("`radius` should be finite and not negative.")
@@ -506,14 +515,7 @@ class DocumentIndex(object):
         max_pairs = operator.index(max_pairs)
         if max_pairs < 1:
             raise ValueError("`max_pairs` should be positive.")
-        N = int(_ffi.lib().trlda_docindex_size(handle))
-        if N < 1:
-            raise RuntimeError("The index is empty.")
-        rows = _silhouette_ids(ids, N)
-        g = None if gamma is None else self._gamma(gamma)
-        if g is not None and g.shape[1] < 1:
-            raise RuntimeError("`gamma` should hold at least one document.")
-        M = N if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+        rows, g, M = self._scored(ids, gamma, self._size())
         indptr = np.empty(M + 1, dtype=np.int64)
         if count_only:
             self._neighbors(radius, rows, g, False, 0, indptr, None, None)
@@ -911,11 +913,7 @@ class DocumentIndex(object):
         C = W.shape[0]
         handle = self._live()
         N = self._size()
-        rows = _silhouette_ids(ids, N)
-        g = None if gamma is None else self._gamma(gamma)
-        if g is not None and g.shape[1] < 1:
-            raise RuntimeError("`gamma` should hold at least one document.")
-        M = N if rows is None and g is None else (rows.shape[0] if g is None else g.shape[1])
+        rows, g, M = self._scored(ids, gamma, N)
         labels = np.empty(M, dtype=np.int32)
         proba = np.empty((M, C), dtype=np.float64) if return_proba else None
         _ffi.check(_ffi.lib().trlda_docindex_classify_predict(handle, W.ctypes.data, C,
@@ -1193,9 +1191,9 @@ def _pca_axes(scatter, N):
     return np.ascontiguousarray(axes * (1e-4 / math.sqrt(top / N) if top > 0.0 else 0.0))
 
 
-def _silhouette_labels(labels, N):
-    """(labels as contiguous int32, C) of ``silhouette``'s labels for an index of N documents, or the
-    documented error; no device is needed."""
+def _document_labels(labels, N):
+    """(labels, smallest, largest) of one integer label per document of an index of N, or the documented
+    error; what `labels` may hold is the caller's to check, before it narrows them to int32."""
     lab = np.asarray(labels)
     if lab.dtype.kind not in "iu":
         raise TypeError("`labels` should be an array of integers.")
@@ -1204,6 +1202,13 @@ def _silhouette_labels(labels, N):
     if lab.ndim != 1 or lab.shape[0] != N:
         raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
     low, high = int(lab.min()), int(lab.max())
+    return lab, low, high
+
+
+def _silhouette_labels(labels, N):
+    """(labels as contiguous int32, C) of ``silhouette``'s labels for an index of N documents, or the
+    documented error; no device is needed."""
+    lab, low, high = _document_labels(labels, N)
     if low < 0 or high >= MAX_CLUSTERS:
         raise RuntimeError("`labels` should lie between 0 and %d." % (MAX_CLUSTERS - 1))
     if low == high:                                          # (the smallest is also the largest: one cluster)
@@ -1445,14 +1450,7 @@ def _hdbscan_labels(u, v, w, N, min_cluster_size, selection="eom", allow_single_
 def _group_labels(labels, N, num_groups=None):
     """(labels as contiguous int32, G) of ``group_prevalence``'s labels for an index of N documents, or
     the documented error; no device is needed."""
-    lab = np.asarray(labels)
-    if lab.dtype.kind not in "iu":
-        raise TypeError("`labels` should be an array of integers.")
-    if N < 1:
-        raise RuntimeError("The index is empty.")
-    if lab.ndim != 1 or lab.shape[0] != N:
-        raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
-    low, high = int(lab.min()), int(lab.max())
+    lab, low, high = _document_labels(labels, N)
     G = max(high + 1, 1) if num_groups is None else operator.index(num_groups)
     if not 1 <= G <= MAX_CLUSTERS - 1:
         raise RuntimeError("`num_groups` should lie between 1 and %d." % (MAX_CLUSTERS - 1))
@@ -1618,14 +1616,7 @@ def _effects_closing(gram, cross, rss, tss, nobs, intercept):
 def _class_labels(labels, N, num_classes=None):
     """(labels as contiguous int32, C) of the classifiers' labels for an index of N documents, or the
     documented error; no device is needed."""
-    lab = np.asarray(labels)
-    if lab.dtype.kind not in "iu":
-        raise TypeError("`labels` should be an array of integers.")
-    if N < 1:
-        raise RuntimeError("The index is empty.")
-    if lab.ndim != 1 or lab.shape[0] != N:
-        raise RuntimeError("`labels` should hold one label per indexed document (%d)." % N)
-    low, high = int(lab.min()), int(lab.max())
+    lab, low, high = _document_labels(labels, N)
     C = high + 1 if num_classes is None else operator.index(num_classes)
     if not 2 <= C <= MAX_CLASSES:
         raise RuntimeError("`num_classes` should lie between 2 and %d." % MAX_CLASSES)
