@@ -570,6 +570,63 @@ int trlda_cooc_add(trlda_cooc *cooc, const trlda_batch *batch);
 int trlda_cooc_read(trlda_cooc *cooc, int64_t *doc_freq, int64_t *co_doc_freq, int64_t *num_docs);
 int trlda_cooc_destroy(trlda_cooc *cooc);
 
+/* Spectral initialisation (csrc/anchor_kernels.h): the word co-occurrence matrix Q of
+ * a corpus stream, FastAnchorWords on its row-normalised form and RecoverL2 (Arora et al. 2013).  The
+ * accumulator is made for `model`'s V and device, runs on the model's stream and must be destroyed
+ * before the model.  Q (V rows of stride ceil(V / 4) * 4 doubles) and, from the first selection or
+ * recovery on, one work copy of the same size live on the device: when the two exceed max_bytes the
+ * call fails with TRLDA_ERR_ARG and a message naming the bytes needed, before anything is allocated.
+ * No reference counterpart. */
+typedef struct trlda_anchor trlda_anchor;
+int trlda_anchor_create(trlda_model *model, size_t max_bytes, trlda_anchor **out);
+/* Adds a batch (made for the model's V and device, else TRLDA_ERR_ARG).  A document with counts c and
+ * n = sum c >= 2 adds ((int64) c_w c_v - [w = v] c_w) / (double)(n (n - 1)) -- an exact integer, one
+ * division -- to Q_wv for every pair of its entries; the others are skipped and counted.  Row w belongs
+ * to one workgroup that walks w's documents in ascending order: one addition per (document, pair), in
+ * document order across the stream, no floating-point atomics -- Q is symmetric bit for bit and does
+ * not depend on how the corpus is cut into batches.  A batch with a negative count, or one that lists a
+ * word twice in a document, fails with TRLDA_ERR_VALUE and adds nothing.  The call waits once, for the
+ * repeated-word flag of the batch's entries; the row kernel is still running when it returns -- on the
+ * model's stream, which every reader of Q follows, and the batch may be destroyed at once. */
+int trlda_anchor_add(trlda_anchor *acc, const trlda_batch *batch);
+/* Replaces Q by the V x V row-major host matrix (finite, non-negative and symmetric bit for bit, else
+ * TRLDA_ERR_VALUE) and doc_freq by the V given values (NULL: none -- no threshold applies to the
+ * candidates then); the other counters are cleared. */
+int trlda_anchor_load(trlda_anchor *acc, const double *Q, const int64_t *doc_freq);
+/* doc_freq[V] (contributing documents with an entry (w, c), c > 0), word_count[V] (their counts of w)
+ * and counters[3]: documents that contributed, documents skipped, tokens of the contributing ones. */
+int trlda_anchor_counts(trlda_anchor *acc, int64_t *doc_freq, int64_t *word_count, int64_t *counters);
+/* Rows of Q into out (n x V, host): rows[i] (in [0, V)), or the first n rows when rows is NULL. */
+int trlda_anchor_read(trlda_anchor *acc, const int32_t *rows, int n, double *out);
+/* r[V], the row sums of Q, and *total, the sum of r.  The order of every sum of n values here: thread
+ * t of 256 adds the values t, t + 256, ... in ascending order from +0, then the 256 partial sums are
+ * folded as p[t] += p[t + s] for s = 128, 64, ..., 1. */
+int trlda_anchor_row_sums(trlda_anchor *acc, double *r, double *total);
+/* FastAnchorWords: `num` anchors among the candidates -- words with r_w > 0 and, when min_doc_freq >= 0,
+ * doc_freq >= min_doc_freq; fewer candidates than anchors is TRLDA_ERR_VALUE.  The work copy holds the
+ * rows Q_w / r_w.  Round 0 takes the candidate row of the largest squared norm and subtracts it from
+ * every candidate row; each later round takes the largest squared residual norm, divides that row by
+ * its norm and takes its component out of every candidate row (modified Gram-Schmidt on the work
+ * copy; norms and dot products in the order above; the winner in the order norm^2 descending, word id
+ * ascending; a chosen word leaves the candidates).  ids[num] in selection order, score[num] the
+ * winning norm^2 of each round, runner[num] the runner-up's (-1 when there is none). */
+int trlda_anchor_select(trlda_anchor *acc, int num, int64_t min_doc_freq, int32_t *ids, double *score,
+                        double *runner);
+/* RecoverL2 for the A anchors (distinct, in [0, V), A <= 640, else TRLDA_ERR_ARG): H = Qbar Qbar_S'
+ * (V x A) by the staged fp64 tile product over the words in ascending chunks, G = its anchors' rows, and
+ * per word, a wave each, min over the simplex of |Qbar_w - x' Qbar_S|^2 by projected gradient with
+ * Nesterov's momentum and gradient restart, step 1 / (2 max_i sum_j |G_ij|), from x = 1 / A, the exact
+ * projection (Michelot), until the word's Frank-Wolfe gap is at most tol |Qbar_w|^2 or max_iter
+ * iterations have run.  beta[V x A] (word-major: K x V in Fortran order): x_wk p_w normalised over w,
+ * p_w = r_w / total; pi[A]: the columns' masses; unless NULL, x[V x A], iters[V] and gaps[V] (the final
+ * gap / |Qbar_w|^2).  A word's result depends on its row, the anchors' rows and A alone. */
+int trlda_anchor_recover(trlda_anchor *acc, const int32_t *anchors, int A, double tol, int max_iter,
+                         double *beta, double *pi, double *x, int32_t *iters, double *gaps);
+/* 0 (default): the solver holds G in LDS up to 128 anchors and reads it from global memory above;
+ * 1: always from global memory.  The results are the same bit for bit. */
+int trlda_anchor_set_gram_lds(trlda_anchor *acc, int mode);
+int trlda_anchor_destroy(trlda_anchor *acc);
+
 /* Nearest documents in topic space (csrc/docindex_kernels.h): a table of the
  * documents' topic proportions theta = gamma / sum(gamma) on the model's device, and the top_n
  * nearest indexed documents of each document of a batch.  measure TRLDA_MEASURE_HELLINGER stores

@@ -23,3 +23,4 @@ def seed(value):
 from . import models  # noqa: E402,F401
 from . import utils  # noqa: E402,F401
 from .index import DocumentIndex  # noqa: E402,F401
+from .anchor import WordCooccurrence  # noqa: E402,F401

@@ -184,6 +184,16 @@ _SIGNATURES = {
     "trlda_cooc_add": (C.c_int, [vp, vp]),
     "trlda_cooc_read": (C.c_int, [vp, i64p, i64p, C.POINTER(C.c_int64)]),
     "trlda_cooc_destroy": (C.c_int, [vp]),
+    "trlda_anchor_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "trlda_anchor_add": (C.c_int, [vp, vp]),
+    "trlda_anchor_load": (C.c_int, [vp, vp, vp]),
+    "trlda_anchor_counts": (C.c_int, [vp, i64p, i64p, i64p]),
+    "trlda_anchor_read": (C.c_int, [vp, vp, C.c_int, vp]),
+    "trlda_anchor_row_sums": (C.c_int, [vp, vp, C.POINTER(C.c_double)]),
+    "trlda_anchor_select": (C.c_int, [vp, C.c_int, C.c_int64, i32p, vp, vp]),
+    "trlda_anchor_recover": (C.c_int, [vp, i32p, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
+    "trlda_anchor_set_gram_lds": (C.c_int, [vp, C.c_int]),
+    "trlda_anchor_destroy": (C.c_int, [vp]),
     "trlda_docindex_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "trlda_docindex_reserve": (C.c_int, [vp, C.c_int64]),
     "trlda_docindex_add": (C.c_int, [vp, vp, vp, C.c_int, C.c_double]),

@@ -70,6 +70,7 @@
 #include "wordsim_kernels.h"
 #include "diagnostics_kernels.h"
 #include "tsne_kernels.h"
+#include "anchor_kernels.h"
 
 namespace {
 
@@ -5877,6 +5878,407 @@ int trlda_cooc_read(trlda_cooc *c, int64_t *doc_freq, int64_t *co_doc_freq, int6
 }
 
 int trlda_cooc_destroy(trlda_cooc *c)
+{
+    if (!c)
+        return TRLDA_OK;
+    wait_before_delete(c->model);
+    delete c;
+    return TRLDA_OK;
+}
+
+}  // extern "C"
+
+// ---- spectral initialisation: word co-occurrence, anchor words, RecoverL2 (csrc/anchor_kernels.h,
+// DESIGN.md 3.36) ----
+
+// The accumulator: Q (V rows of stride Vp = ceil(V / 4) * 4, the tail zero) and, from the first selection
+// or recovery on, one work copy of the same size; the counters; per batch the documents' lengths and the
+// word-major entries' CSR positions.
+struct trlda_anchor {
+    trlda_model *model = nullptr;
+    int V = 0, Vp = 0;
+    bool has_doc_freq = true;            // (a loaded matrix may come without)
+    int gram_lds = 0;                    // 0: G in LDS up to kAnchorGramLdsTopics; 1: never
+    DevBuf<double> Q, W;                 // V x Vp each
+    DevBuf<long long> doc_freq, word_count;   // V
+    DevBuf<unsigned long long> counters; // documents that contributed, documents skipped, tokens
+    DevBuf<int> flag;                    // set by a batch that lists a word twice in a document
+    DevBuf<long long> docn;              // B
+    DevBuf<int32_t> wpos;                // nnz
+    DevBuf<double> r, total, norm2;      // V, 1, V
+    DevBuf<int> cand;                    // V
+    DevBuf<double> u;                    // Vp
+};
+
+namespace {
+
+size_t anchor_matrix_bytes(int V) { return (size_t)V * ((size_t)(V + 3) / 4 * 4) * sizeof(double); }
+
+// r = the row sums of Q and *total = their sum, each in the order of anchor_block_sum
+int anchor_row_sums(trlda_anchor *c)
+{
+    trlda_model *m = c->model;
+    hipLaunchKernelGGL(trlda::anchor_sums_kernel, dim3(c->V), dim3(trlda::kAnchorThreads), 0, m->stream, c->V, c->Vp,
+                       c->Q.get(), c->r.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::anchor_sums_kernel, dim3(1), dim3(trlda::kAnchorThreads), 0, m->stream, c->V, c->V,
+                       c->r.get(), c->total.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+// W = the row-normalised Q, norm2 = its rows' squared norms (after anchor_row_sums)
+int anchor_normalise(trlda_anchor *c)
+{
+    trlda_model *m = c->model;
+    int rc = c->W.grow((size_t)c->V * c->Vp);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(trlda::anchor_normalise_kernel, dim3(c->V), dim3(trlda::kAnchorThreads), 0, m->stream, c->V,
+                       c->Vp, c->Q.get(), c->r.get(), c->W.get(), c->norm2.get());
+    HIP_TRY(hipGetLastError());
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trlda_anchor_create(trlda_model *m, size_t max_bytes, trlda_anchor **out)
+{
+    if (!out)
+        return fail(TRLDA_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int V = m->V;
+    const size_t need = 2 * anchor_matrix_bytes(V);
+    if (need > max_bytes)
+        return fail(TRLDA_ERR_ARG, "the co-occurrence matrix and its work copy need " + std::to_string(need) +
+                                       " bytes for " + std::to_string(V) + " words, more than max_bytes = " +
+                                       std::to_string(max_bytes));
+    trlda_anchor *c = new trlda_anchor();
+    c->model = m;
+    c->V = V;
+    c->Vp = (V + 3) / 4 * 4;
+    const size_t n = (size_t)V * c->Vp;
+    rc = c->Q.alloc(n);
+    if (!rc) rc = c->doc_freq.alloc((size_t)V);
+    if (!rc) rc = c->word_count.alloc((size_t)V);
+    if (!rc) rc = c->counters.alloc(3);
+    if (!rc) rc = c->flag.alloc(1);
+    if (!rc) rc = c->r.alloc((size_t)V);
+    if (!rc) rc = c->total.alloc(1);
+    if (!rc) rc = c->norm2.alloc((size_t)V);
+    if (!rc) rc = c->cand.alloc((size_t)V);
+    if (!rc) rc = c->u.alloc((size_t)c->Vp);
+    if (!rc) {
+        hipError_t e1 = hipMemsetAsync(c->Q, 0, n * sizeof(double), m->stream);
+        hipError_t e2 = hipMemsetAsync(c->doc_freq, 0, (size_t)V * sizeof(long long), m->stream);
+        hipError_t e3 = hipMemsetAsync(c->word_count, 0, (size_t)V * sizeof(long long), m->stream);
+        hipError_t e4 = hipMemsetAsync(c->counters, 0, 3 * sizeof(unsigned long long), m->stream);
+        hipError_t e5 = hipMemsetAsync(c->flag, 0, sizeof(int), m->stream);
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess)
+            rc = fail(TRLDA_ERR_HIP, "clearing the co-occurrence matrix failed");
+    }
+    if (rc) {
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return TRLDA_OK;
+}
+
+int trlda_anchor_add(trlda_anchor *c, const trlda_batch *b)
+{
+    if (!c || !b)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / batch");
+    if (int rc_built = batch_wait(b))
+        return rc_built;
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    if (int rc_arg = batch_matches_model(m, b))
+        return rc_arg;
+    if (b->B == 0)
+        return TRLDA_OK;
+    if (!b->cnts_nonneg)
+        return fail(TRLDA_ERR_VALUE, "a co-occurrence batch must not hold a negative count");
+    if ((rc = c->docn.grow((size_t)b->B)) || (rc = c->wpos.grow((size_t)b->nnz)))
+        return rc;
+    if ((rc = batch_begin(m, b)))
+        return rc;
+    const int T = trlda::kAnchorThreads;
+    // the entries first: a batch that lists a word twice in a document is refused before it counts
+    if (b->nnz > 0) {
+        hipLaunchKernelGGL(trlda::anchor_entries_kernel, dim3((unsigned)((b->nnz + T - 1) / T)), dim3(T), 0, m->stream,
+                           (long long)b->nnz, b->ids, b->wrank, b->wptr, b->wdoc, c->wpos.get(), c->flag.get());
+        HIP_TRY(hipGetLastError());
+    }
+    int flag = 0;
+    hipError_t e1 = hipMemcpyAsync(&flag, c->flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    if (flag) {
+        HIP_TRY(hipMemsetAsync(c->flag, 0, sizeof(int), m->stream));
+        (void)batch_end(m, b);
+        return fail(TRLDA_ERR_VALUE, "a co-occurrence batch must list a word at most once per document");
+    }
+    hipLaunchKernelGGL(trlda::anchor_docs_kernel, dim3((b->B + T - 1) / T), dim3(T), 0, m->stream, b->B, b->indptr,
+                       b->cnts, c->docn.get(), c->counters.get());
+    HIP_TRY(hipGetLastError());
+    if (b->nnz > 0) {
+        hipLaunchKernelGGL(trlda::anchor_cooc_rows_kernel, dim3(c->V), dim3(T), 0, m->stream, c->Vp, b->indptr, b->ids,
+                           b->cnts, b->wptr, b->wdoc, c->wpos.get(), c->docn.get(), c->Q.get(), c->doc_freq.get(),
+                           c->word_count.get());
+        HIP_TRY(hipGetLastError());
+    }
+    (void)batch_end(m, b);
+    return TRLDA_OK;
+}
+
+int trlda_anchor_load(trlda_anchor *c, const double *Q, const int64_t *doc_freq)
+{
+    if (!c || !Q)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / matrix");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int V = c->V, Vp = c->Vp;
+    for (int i = 0; i < V; ++i)
+        for (int j = 0; j < V; ++j) {
+            const double q = Q[(size_t)i * V + j];
+            if (!(q >= 0.0) || !std::isfinite(q))
+                return fail(TRLDA_ERR_VALUE, "the co-occurrence matrix must be finite and non-negative");
+            if (j < i && q != Q[(size_t)j * V + i])
+                return fail(TRLDA_ERR_VALUE, "the co-occurrence matrix must be symmetric");
+        }
+    if (doc_freq)
+        for (int i = 0; i < V; ++i)
+            if (doc_freq[i] < 0)
+                return fail(TRLDA_ERR_VALUE, "doc_freq must not be negative");
+    const size_t n = (size_t)V * Vp;
+    hipError_t e0 = hipMemsetAsync(c->Q, 0, n * sizeof(double), m->stream);
+    hipError_t e1 = hipMemcpy2DAsync(c->Q, (size_t)Vp * sizeof(double), Q, (size_t)V * sizeof(double),
+                                     (size_t)V * sizeof(double), (size_t)V, hipMemcpyHostToDevice, m->stream);
+    hipError_t e2 = doc_freq ? hipMemcpyAsync(c->doc_freq, doc_freq, (size_t)V * sizeof(long long),
+                                              hipMemcpyHostToDevice, m->stream)
+                             : hipMemsetAsync(c->doc_freq, 0, (size_t)V * sizeof(long long), m->stream);
+    hipError_t e3 = hipMemsetAsync(c->word_count, 0, (size_t)V * sizeof(long long), m->stream);
+    hipError_t e4 = hipMemsetAsync(c->counters, 0, 3 * sizeof(unsigned long long), m->stream);
+    hipError_t e5 = hipStreamSynchronize(m->stream);        // (the caller's arrays are free again)
+    HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
+    c->has_doc_freq = doc_freq != nullptr;
+    return TRLDA_OK;
+}
+
+int trlda_anchor_counts(trlda_anchor *c, int64_t *doc_freq, int64_t *word_count, int64_t *counters)
+{
+    if (!c || !doc_freq || !word_count || !counters)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    hipError_t e1 = hipMemcpyAsync(doc_freq, c->doc_freq, (size_t)c->V * sizeof(long long), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e2 = hipMemcpyAsync(word_count, c->word_count, (size_t)c->V * sizeof(long long), hipMemcpyDeviceToHost,
+                                   m->stream);
+    hipError_t e3 = hipMemcpyAsync(counters, c->counters, 3 * sizeof(long long), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    return TRLDA_OK;
+}
+
+int trlda_anchor_read(trlda_anchor *c, const int32_t *rows, int n, double *out)
+{
+    if (!c || !out)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int V = c->V;
+    if (n < 0 || (!rows && n > V))
+        return fail(TRLDA_ERR_ARG, "bad number of rows");
+    for (int i = 0; rows && i < n; ++i)
+        if (rows[i] < 0 || rows[i] >= V)
+            return fail(TRLDA_ERR_ARG, "row out of range");
+    const size_t rb = (size_t)V * sizeof(double);
+    if (!rows && n > 0)
+        HIP_TRY(hipMemcpy2DAsync(out, rb, c->Q, (size_t)c->Vp * sizeof(double), rb, (size_t)n, hipMemcpyDeviceToHost,
+                                 m->stream));
+    for (int i = 0; rows && i < n; ++i)
+        HIP_TRY(hipMemcpyAsync(out + (size_t)i * V, c->Q + (size_t)rows[i] * c->Vp, rb, hipMemcpyDeviceToHost,
+                               m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return TRLDA_OK;
+}
+
+int trlda_anchor_row_sums(trlda_anchor *c, double *r, double *total)
+{
+    if (!c || !r || !total)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc || (rc = anchor_row_sums(c)))
+        return rc;
+    hipError_t e1 = hipMemcpyAsync(r, c->r, (size_t)c->V * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(total, c->total, sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    return TRLDA_OK;
+}
+
+int trlda_anchor_set_gram_lds(trlda_anchor *c, int mode)
+{
+    if (!c || mode < 0 || mode > 1)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator, or a mode other than 0 (G in LDS where it fits) and 1 (never)");
+    c->gram_lds = mode;
+    return TRLDA_OK;
+}
+
+int trlda_anchor_select(trlda_anchor *c, int num, int64_t min_doc_freq, int32_t *ids, double *score, double *runner)
+{
+    if (!c || !ids || !score || !runner)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int V = c->V, Vp = c->Vp, T = trlda::kAnchorThreads;
+    if (num < 1 || num > V)
+        return fail(TRLDA_ERR_ARG, "the number of anchors must lie in [1, num_words]");
+    if (min_doc_freq >= 0 && !c->has_doc_freq)
+        return fail(TRLDA_ERR_ARG, "the matrix was loaded without doc_freq: no threshold applies");
+    if ((rc = anchor_row_sums(c)))
+        return rc;
+    hipLaunchKernelGGL(trlda::anchor_candidates_kernel, dim3((V + T - 1) / T), dim3(T), 0, m->stream, V,
+                       (long long)min_doc_freq, c->r.get(), c->doc_freq.get(), c->cand.get());
+    HIP_TRY(hipGetLastError());
+    std::vector<int> cand((size_t)V);
+    hipError_t e1 = hipMemcpyAsync(cand.data(), c->cand, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2);
+    long long have = 0;
+    for (int w = 0; w < V; ++w)
+        have += cand[w];
+    if (have < num)
+        return fail(TRLDA_ERR_VALUE, "only " + std::to_string(have) + " candidate words for " + std::to_string(num) +
+                                         " anchors");
+    if ((rc = anchor_normalise(c)))
+        return rc;
+    DevBuf<int32_t> d_ids;
+    DevBuf<double> d_sc;
+    if ((rc = d_ids.alloc((size_t)num)) || (rc = d_sc.alloc(2 * (size_t)num)))
+        return rc;
+    for (int round = 0; round < num; ++round) {
+        hipLaunchKernelGGL(trlda::anchor_pick_kernel, dim3(1), dim3(T), 0, m->stream, V, Vp, round, c->W.get(),
+                           c->norm2.get(), c->cand.get(), c->u.get(), d_ids.get(), d_sc.get(), d_sc.get() + num);
+        HIP_TRY(hipGetLastError());
+        if (round + 1 < num) {
+            hipLaunchKernelGGL(trlda::anchor_update_kernel, dim3(V), dim3(T), 0, m->stream, V, Vp, round == 0 ? 1 : 0,
+                               c->W.get(), c->cand.get(), c->u.get(), c->norm2.get());
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    hipError_t e3 = hipMemcpyAsync(ids, d_ids, (size_t)num * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipMemcpyAsync(score, d_sc, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e5 = hipMemcpyAsync(runner, d_sc + num, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e6 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6);
+    return TRLDA_OK;
+}
+
+int trlda_anchor_recover(trlda_anchor *c, const int32_t *anchors, int A, double tol, int max_iter, double *beta,
+                         double *pi, double *x, int32_t *iters, double *gaps)
+{
+    if (!c || !anchors || !beta || !pi)
+        return fail(TRLDA_ERR_ARG, "NULL accumulator / anchors / output");
+    trlda_model *m = c->model;
+    int rc = check_model(m);
+    if (rc)
+        return rc;
+    const int V = c->V, Vp = c->Vp, T = trlda::kAnchorThreads;
+    if (A < 1 || A > trlda::kAnchorMaxTopics || A > V)
+        return fail(TRLDA_ERR_ARG, "the number of anchors must lie in [1, min(num_words, " +
+                                       std::to_string(trlda::kAnchorMaxTopics) + ")]");
+    if (!(tol >= 0.0) || max_iter < 1)
+        return fail(TRLDA_ERR_ARG, "tol must not be negative and max_iter at least 1");
+    {
+        std::vector<char> seen((size_t)V, 0);
+        for (int k = 0; k < A; ++k) {
+            if (anchors[k] < 0 || anchors[k] >= V)
+                return fail(TRLDA_ERR_ARG, "anchor word out of range");
+            if (seen[anchors[k]])
+                return fail(TRLDA_ERR_ARG, "an anchor word occurs twice");
+            seen[anchors[k]] = 1;
+        }
+    }
+    if ((rc = anchor_row_sums(c)))
+        return rc;
+    double total = 0.0;
+    hipError_t t1 = hipMemcpyAsync(&total, c->total, sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t t2 = hipStreamSynchronize(m->stream);
+    HIP_TRY(t1); HIP_TRY(t2);
+    if (!(total > 0.0))
+        return fail(TRLDA_ERR_VALUE, "the co-occurrence matrix is empty");
+    if ((rc = anchor_normalise(c)))
+        return rc;
+    const size_t VA = (size_t)V * A;
+    DevBuf<int32_t> d_anc, d_it;
+    DevBuf<double> H, G, X, Bt, small;                      // small: L, then pi, then the gaps
+    if ((rc = d_anc.alloc((size_t)A)) || (rc = d_it.alloc((size_t)V)) || (rc = H.alloc(VA)) ||
+        (rc = G.alloc((size_t)A * A)) || (rc = X.alloc(VA)) || (rc = Bt.alloc(VA)) ||
+        (rc = small.alloc(1 + (size_t)A + V)))
+        return rc;
+    double *d_L = small, *d_pi = d_L + 1, *d_gap = d_pi + A;
+    HIP_TRY(hipMemcpyAsync(d_anc, anchors, (size_t)A * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(trlda::anchor_product_kernel, dim3((V + 63) / 64), dim3(T), trlda::tile_operands_lds(64),
+                       m->stream, V, Vp, A, c->W.get(), d_anc.get(), H.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::anchor_gram_kernel, dim3(1), dim3(T), 0, m->stream, A, H.get(), d_anc.get(), G.get(),
+                       d_L);
+    HIP_TRY(hipGetLastError());
+    const bool glds = c->gram_lds == 0 && A <= trlda::kAnchorGramLdsTopics;
+    const size_t lds = ((glds ? (size_t)A * A : 0) +
+                        (size_t)trlda::kAnchorSolveWaves * trlda::kAnchorSolveVectors * A) * sizeof(double);
+    const void *fn = glds ? reinterpret_cast<const void *>(trlda::anchor_solve_kernel<true>)
+                          : reinterpret_cast<const void *>(trlda::anchor_solve_kernel<false>);
+    if (lds > (size_t)kLdsDynBytes)
+        return fail(TRLDA_ERR_ARG, "too many anchors for the solver's LDS");
+    if ((rc = ensure_dynamic_lds(fn, lds)))
+        return rc;
+    const dim3 grid((V + trlda::kAnchorSolveWaves - 1) / trlda::kAnchorSolveWaves);
+    if (glds)
+        hipLaunchKernelGGL(trlda::anchor_solve_kernel<true>, grid, dim3(T), lds, m->stream, V, A, H.get(), G.get(),
+                           d_L, c->norm2.get(), tol, max_iter, X.get(), d_it.get(), d_gap);
+    else
+        hipLaunchKernelGGL(trlda::anchor_solve_kernel<false>, grid, dim3(T), lds, m->stream, V, A, H.get(), G.get(),
+                           d_L, c->norm2.get(), tol, max_iter, X.get(), d_it.get(), d_gap);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::anchor_mass_kernel, dim3(A), dim3(T), 0, m->stream, V, A, X.get(), c->r.get(),
+                       c->total.get(), d_pi);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(trlda::anchor_beta_kernel, dim3((unsigned)((VA + T - 1) / T)), dim3(T), 0, m->stream, V, A,
+                       X.get(), c->r.get(), c->total.get(), d_pi, Bt.get());
+    HIP_TRY(hipGetLastError());
+    hipError_t e1 = hipMemcpyAsync(beta, Bt, VA * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e2 = hipMemcpyAsync(pi, d_pi, (size_t)A * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = x ? hipMemcpyAsync(x, X, VA * sizeof(double), hipMemcpyDeviceToHost, m->stream) : hipSuccess;
+    hipError_t e4 = iters ? hipMemcpyAsync(iters, d_it, (size_t)V * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream)
+                          : hipSuccess;
+    hipError_t e5 = gaps ? hipMemcpyAsync(gaps, d_gap, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, m->stream)
+                         : hipSuccess;
+    hipError_t e6 = hipStreamSynchronize(m->stream);
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6);
+    return TRLDA_OK;
+}
+
+int trlda_anchor_destroy(trlda_anchor *c)
 {
     if (!c)
         return TRLDA_OK;

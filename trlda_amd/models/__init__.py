@@ -1330,6 +1330,148 @@ class LDA(Distribution):
                          "num_documents": int(num_docs.value)}
         return coh
 
+    # -- spectral initialisation: anchor words from word co-occurrence (csrc/anchor_kernels.h) -----
+    def word_cooccurrence(self, docs=None, max_bytes=None):
+        """A ``trlda_amd.WordCooccurrence`` for this model's vocabulary: the device-resident matrix Q
+        of Arora et al.'s unbiased word co-occurrence estimator, with ``docs`` (a batch or an iterator
+        of batches, as ``topic_coherence`` takes them) added when given.  ``max_bytes`` (default
+        16 GiB) bounds Q plus its one work copy: a larger vocabulary raises RuntimeError naming the
+        bytes needed before anything is allocated.  The accumulator is closed with the model
+        (DESIGN.md 3.36)."""
+        from ..anchor import DEFAULT_MAX_BYTES, WordCooccurrence
+        self._settle()
+        cooc = WordCooccurrence(self, DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+        if docs is not None:
+            try:
+                cooc.add(docs)
+            except Exception:
+                cooc.close()
+                raise
+        return cooc
+
+    def _own_cooc(self, cooc):
+        from ..anchor import WordCooccurrence
+        if not isinstance(cooc, WordCooccurrence):
+            raise RuntimeError("`cooc` should be a WordCooccurrence of this model.")
+        if cooc._model is not self:
+            raise RuntimeError("The co-occurrence matrix was made for a different model.")
+        return cooc._live()
+
+    def anchor_words(self, cooc, num_anchors=None, min_doc_freq=None, return_scores=False):
+        """FastAnchorWords on the row-normalised ``Qbar_w = Q_w / sum_v Q_wv`` of ``cooc``:
+        ``num_anchors`` (default: the number of topics) int32 word ids in selection order.
+
+        Candidates are the words with ``doc_freq >= min_doc_freq`` (default ``max(2, ceil(0.005 *
+        num_documents))``) and a positive row sum; for a matrix loaded without ``doc_freq`` every
+        word with a positive row sum is one.  Fewer candidates than anchors raise RuntimeError.
+        Round 0 takes the candidate row of the largest squared norm and subtracts it from every
+        candidate row; each later round takes the largest squared residual norm, normalises that row
+        and removes its component from every candidate row of the work copy (modified Gram-Schmidt).
+        Norms and dot products are fixed-order sums of the row alone (``WordCooccurrence.row_sums``
+        documents the order); the winner is the first in the order (norm^2 descending, word id
+        ascending) and leaves the candidates.  With ``return_scores=True`` returns ``(anchors,
+        scores)``, scores a dict of each round's ``winner`` and ``runner_up`` norm^2 (-1 where there
+        is no runner-up): near-ties show there.  lambda, alpha, eta, the counters and the random stream
+        are left as they are."""
+        handle = self._own_cooc(cooc)
+        num = self._K if num_anchors is None else operator.index(num_anchors)
+        if num < 1:
+            raise RuntimeError("`num_anchors` should be positive.")
+        if not cooc.has_doc_freq:
+            if min_doc_freq is not None:
+                raise RuntimeError("The matrix was loaded without `doc_freq`: no threshold applies.")
+            min_df = -1
+        elif min_doc_freq is None:
+            min_df = max(2, -(-5 * cooc.num_documents // 1000))
+        else:
+            min_df = operator.index(min_doc_freq)
+            if min_df < 0:
+                raise RuntimeError("`min_doc_freq` should not be negative.")
+        ids = np.empty(num, dtype=np.int32)
+        score, runner = np.empty(num, dtype=np.float64), np.empty(num, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_anchor_select(handle, num, min_df, ids, score.ctypes.data,
+                                                  runner.ctypes.data))
+        if return_scores:
+            return ids, {"winner": score, "runner_up": runner}
+        return ids
+
+    def recover_topics(self, cooc, anchors, tol=1e-7, max_iter=2000, return_info=False):
+        """RecoverL2: for every word ``min over the simplex of |Qbar_w - x' Qbar_S|^2`` with S the
+        ``anchors`` (distinct word ids; out of range or repeated ones raise RuntimeError), then
+        ``(beta, pi)``: beta, K x V in Fortran order like ``lambdas``, column k of ``x_wk p_w``
+        normalised over the words (``p = cooc.word_probabilities()``), and pi, the K column masses.
+
+        ``H = Qbar Qbar_S'`` comes from the staged fp64 tile product over the words in ascending
+        chunks and ``G`` is its anchors' rows.  A wave per word runs projected gradient with Nesterov's
+        momentum and gradient restart (reset when ``(y - x+) . (x+ - x) > 0``), step ``1 / L`` with
+        ``L = 2 max_i sum_j |G_ij|``, from ``x = 1 / K``, with the exact Euclidean projection onto the
+        simplex (Michelot's finite iteration), and stops on its own when its Frank-Wolfe gap
+        ``x . g - min_k g_k`` is at most ``tol |Qbar_w|^2``, or after ``max_iter`` iterations: a word's
+        result depends on its row and the anchors' rows alone.  Words with a zero row get beta = 0.
+        With ``return_info=True`` returns ``(beta, pi, info)``, info a dict of ``x`` (V x K),
+        ``iterations`` (int32 per word) and ``gaps`` (the final gap over ``|Qbar_w|^2``)."""
+        handle = self._own_cooc(cooc)
+        try:
+            a = np.asarray(anchors)
+        except (TypeError, ValueError):
+            raise RuntimeError("`anchors` should be a one-dimensional array of word ids.")
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise RuntimeError("`anchors` should be a one-dimensional array of word ids.")
+        if a.min() < 0 or a.max() >= self._V:
+            raise RuntimeError("Anchor word out of range.")
+        if len(np.unique(a)) != len(a):
+            raise RuntimeError("An anchor word occurs twice.")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        A, V = len(a), self._V
+        tol = float(tol)
+        max_iter = operator.index(max_iter)
+        if not tol >= 0.0 or max_iter < 1:
+            raise RuntimeError("`tol` should not be negative and `max_iter` at least 1.")
+        beta = np.empty((A, V), dtype=np.float64, order="F")
+        pi = np.empty(A, dtype=np.float64)
+        x = np.empty((V, A), dtype=np.float64)
+        iters = np.empty(V, dtype=np.int32)
+        gaps = np.empty(V, dtype=np.float64)
+        _ffi.check(_ffi.lib().trlda_anchor_recover(handle, a, A, tol, max_iter, beta.ctypes.data,
+                                                   pi.ctypes.data, x.ctypes.data, iters.ctypes.data,
+                                                   gaps.ctypes.data))
+        if return_info:
+            return beta, pi, {"x": x, "iterations": iters, "gaps": gaps}
+        return beta, pi
+
+    def initialize_spectral(self, docs_or_cooc, strength=None, **kw):
+        """Sets ``lambda_kw = eta + (strength * pi_k) * beta_kw`` from the anchor words of a corpus:
+        ``word_cooccurrence`` (unless a ``WordCooccurrence`` is given), ``anchor_words`` with K
+        anchors and ``recover_topics``, in that order; ``strength`` defaults to the accumulator's
+        ``num_tokens`` -- a matrix loaded with ``from_matrix`` has counted none and needs ``strength``
+        given (RuntimeError otherwise).  Keywords ``min_doc_freq``, ``tol``, ``max_iter`` and ``max_bytes`` go to the
+        stage that takes them.  Returns the anchors.  alpha, eta and the counters are left alone and
+        nothing is drawn from the random stream: the same corpus gives the same lambda."""
+        from ..anchor import WordCooccurrence
+        unknown = set(kw) - {"min_doc_freq", "tol", "max_iter", "max_bytes"}
+        if unknown:
+            raise TypeError("initialize_spectral() got an unexpected keyword argument %r" % sorted(unknown)[0])
+        self._settle()
+        owned = not isinstance(docs_or_cooc, WordCooccurrence)
+        cooc = self.word_cooccurrence(docs_or_cooc, kw.get("max_bytes")) if owned else docs_or_cooc
+        try:
+            if strength is None:
+                strength = cooc.num_tokens
+                if strength == 0:
+                    raise RuntimeError("The accumulator has counted no tokens (a loaded matrix, or no "
+                                       "document of two tokens): give `strength`.")
+            strength = float(strength)
+            if not (strength > 0.0 and np.isfinite(strength)):
+                raise RuntimeError("`strength` should be positive.")
+            anchors = self.anchor_words(cooc, min_doc_freq=kw.get("min_doc_freq"))
+            beta, pi = self.recover_topics(cooc, anchors, tol=kw.get("tol", 1e-7),
+                                           max_iter=kw.get("max_iter", 2000))
+        finally:
+            if owned:
+                cooc.close()
+        self.lambdas = self._eta + (strength * pi)[:, None] * beta
+        return anchors
+
     # -- relevance, saliency and topic prevalence (csrc/relevance_kernels.h) -----------------------
     def _rank_top_n(self, top_n):
         top_n = operator.index(top_n)
