@@ -2976,6 +2976,19 @@ int wait_for_copies(trlda_model *m, std::initializer_list<hipError_t> queued)
     return TRLDA_OK;
 }
 
+// An array of the caller's onto the device in the middle of a call, waited for: it is the caller's and
+// need not outlive an early return.
+int upload_waited(trlda_model *m, void *dst, const void *src, size_t bytes)
+{
+    return wait_for_copies(m, {hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, m->stream)});
+}
+
+// an int that the launches queued so far have left on the device, read in the middle of a call
+int read_flag(trlda_model *m, const int *flag_dev, int *flag)
+{
+    return wait_for_copies(m, {hipMemcpyAsync(flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, m->stream)});
+}
+
 // The end of an entry point that brings results of the E-step back: the copies, then the exchange.
 int wait_for_results(trlda_model *m, std::initializer_list<hipError_t> queued)
 {
@@ -5660,7 +5673,64 @@ int trlda_model_word_topics(trlda_model *m, const trlda_batch *b, double *gamma,
     return wait_for_results(m, {e1, e2, e3});
 }
 
+}  // extern "C"
+
 // ---- topic coherence: top words and document counts (csrc/coherence_kernels.h) ----
+
+namespace {
+
+// The top-N tree over `rows` rows of V values: the first level leaves n candidates per tile of words
+// (c1 per row), a merge level n per group of kTopnGroup (at most c2 <= c1 per row: a level's output
+// fits where its input was read from, in the other half).  Keys and ids of `cap` elements each, the
+// halves at 0 and off_b.  Relevance and saliency rank with the same tree.
+struct TopnPlan {
+    int tiles;
+    size_t c1, c2, off_b, cap;
+};
+
+TopnPlan topn_plan(int V, int rows, int n)
+{
+    TopnPlan p;
+    p.tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
+    p.c1 = (size_t)p.tiles * n;
+    p.c2 = (p.c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;
+    p.off_b = (size_t)rows * p.c1;
+    p.cap = p.off_b + (size_t)rows * p.c2;
+    return p;
+}
+
+int topn_check(const trlda_model *m, int top_n)
+{
+    if (top_n < 1 || top_n > trlda::kTopnMax || top_n > m->V)
+        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
+    if (m->K > 65535 || topn_plan(m->V, 1, top_n).tiles > 65535)    // (grid dimensions y)
+        return fail(TRLDA_ERR_ARG, "num_topics or num_words too large for the top-word kernels");
+    return TRLDA_OK;
+}
+
+// The levels between the first and the last: topn_merge_kernel while a row has more than kTopnGroup
+// candidates.  `at` is the half (0 or off_b) that holds the last level's input, `c` its candidates per
+// row; the caller launches the last level, which ranks.
+int topn_merge_levels(trlda_model *m, const TopnPlan &p, int rows, int n, uint64_t *keys, int32_t *ids, size_t &at,
+                      size_t &c)
+{
+    size_t out = p.off_b;
+    at = 0;
+    c = p.c1;
+    while (c > (size_t)trlda::kTopnGroup) {
+        const size_t groups = (c + trlda::kTopnGroup - 1) / trlda::kTopnGroup;
+        hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3((unsigned)groups, rows), dim3(trlda::kWave), 0,
+                           m->stream, n, (int)c, keys + at, ids + at, keys + out, ids + out, (int32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+        std::swap(at, out);
+        c = groups * n;
+    }
+    return TRLDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 // The top words: one read of lambda by tiles of word columns, then per topic a tree of merges of
 // 1024 candidates each, the last of which sorts
@@ -5671,51 +5741,31 @@ int trlda_model_top_words(trlda_model *m, int top_n, int32_t *words_out)
         return rc;
     if (!words_out)
         return fail(TRLDA_ERR_ARG, "words_out is NULL");
-    if (top_n < 1 || top_n > trlda::kTopnMax || top_n > m->V)
-        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
-    const int K = m->K, V = m->V, n = top_n;
-    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    if (K > 65535 || tiles > 65535)                      // (grid dimensions y)
-        return fail(TRLDA_ERR_ARG, "num_topics or num_words too large for the top-word kernels");
-    const size_t c1 = (size_t)tiles * n;                 // candidates per topic after the first level
-    const size_t c2 = (c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;   // after the second
-    // one allocation: the first level's candidates, the later levels' (ping-pong), the ids
-    const size_t off_b = (size_t)K * c1, cap = off_b + (size_t)K * c2;
-    DevBuf<uint64_t> keys;
-    DevBuf<int32_t> ids;
-    if ((rc = keys.alloc(cap)) || (rc = ids.alloc(cap + (size_t)K * n)))
+    if ((rc = topn_check(m, top_n)))
         return rc;
-    uint64_t *kb = keys;
-    int32_t *ib = ids;
-    int32_t *wout = ib + cap;
+    const int K = m->K, V = m->V, n = top_n;
+    const TopnPlan p = topn_plan(V, K, n);
+    DevBuf<uint64_t> keys;
+    DevBuf<int32_t> ids;                                 // (the ranked ids behind the tree's)
+    if ((rc = keys.alloc(p.cap)) || (rc = ids.alloc(p.cap + (size_t)K * n)))
+        return rc;
+    int32_t *wout = ids + p.cap;
     const size_t lds = (size_t)trlda::kTopnTileTopics * trlda::kTopnTileStride * sizeof(uint64_t);
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topn_tile_kernel), lds)))
         return rc;
     hipLaunchKernelGGL(trlda::topn_tile_kernel,
-                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, tiles),
-                       dim3(trlda::kTopnThreads), lds, m->stream, K, V, n, m->lambda, kb, ib);
+                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, p.tiles),
+                       dim3(trlda::kTopnThreads), lds, m->stream, K, V, n, m->lambda, keys.get(), ids.get());
     HIP_TRY(hipGetLastError());
-    // (c2 <= c1: a level's output fits where its input was read from, in the other half)
-    uint64_t *ik = kb, *ok = kb + off_b;
-    int32_t *ii = ib, *oi = ib + off_b;
-    size_t c = c1;
-    while (c > (size_t)trlda::kTopnGroup) {
-        const size_t groups = (c + trlda::kTopnGroup - 1) / trlda::kTopnGroup;
-        hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3((unsigned)groups, K), dim3(trlda::kWave), 0,
-                           m->stream, n, (int)c, ik, ii, ok, oi, (int32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
-        std::swap(ik, ok);
-        std::swap(ii, oi);
-        c = groups * n;
-    }
+    size_t at = 0, c = 0;
+    if ((rc = topn_merge_levels(m, p, K, n, keys, ids, at, c)))
+        return rc;
     hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3(1, K), dim3(trlda::kWave), 0, m->stream, n, (int)c,
-                       ik, ii, (uint64_t *)nullptr, (int32_t *)nullptr, wout);
+                       keys + at, ids + at, (uint64_t *)nullptr, (int32_t *)nullptr, wout);
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(words_out, wout, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost,
                                    m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1});
 }
 
 }  // extern "C"
@@ -5861,8 +5911,8 @@ int trlda_cooc_read(trlda_cooc *c, int64_t *doc_freq, int64_t *co_doc_freq, int6
                                    m->stream);
     hipError_t e2 = hipMemcpyAsync(co_doc_freq, c->co, TN * N * sizeof(long long), hipMemcpyDeviceToHost,
                                    m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    if ((rc = wait_for_copies(m, {e1, e2})))
+        return rc;
     for (int t = 0; t < T; ++t) {
         int64_t *co = co_doc_freq + (size_t)t * N * N;
         for (int i = 0; i < N; ++i) {
@@ -6018,9 +6068,8 @@ int trlda_anchor_add(trlda_anchor *c, const trlda_batch *b)
         HIP_TRY(hipGetLastError());
     }
     int flag = 0;
-    hipError_t e1 = hipMemcpyAsync(&flag, c->flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
+    if ((rc = read_flag(m, c->flag, &flag)))
+        return rc;
     if (flag) {
         HIP_TRY(hipMemsetAsync(c->flag, 0, sizeof(int), m->stream));
         (void)batch_end(m, b);
@@ -6069,8 +6118,8 @@ int trlda_anchor_load(trlda_anchor *c, const double *Q, const int64_t *doc_freq)
                              : hipMemsetAsync(c->doc_freq, 0, (size_t)V * sizeof(long long), m->stream);
     hipError_t e3 = hipMemsetAsync(c->word_count, 0, (size_t)V * sizeof(long long), m->stream);
     hipError_t e4 = hipMemsetAsync(c->counters, 0, 3 * sizeof(unsigned long long), m->stream);
-    hipError_t e5 = hipStreamSynchronize(m->stream);        // (the caller's arrays are free again)
-    HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5);
+    if ((rc = wait_for_copies(m, {e0, e1, e2, e3, e4})))   // (the caller's arrays are free again)
+        return rc;
     c->has_doc_freq = doc_freq != nullptr;
     return TRLDA_OK;
 }
@@ -6088,9 +6137,7 @@ int trlda_anchor_counts(trlda_anchor *c, int64_t *doc_freq, int64_t *word_count,
     hipError_t e2 = hipMemcpyAsync(word_count, c->word_count, (size_t)c->V * sizeof(long long), hipMemcpyDeviceToHost,
                                    m->stream);
     hipError_t e3 = hipMemcpyAsync(counters, c->counters, 3 * sizeof(long long), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2, e3});
 }
 
 int trlda_anchor_read(trlda_anchor *c, const int32_t *rows, int n, double *out)
@@ -6108,14 +6155,19 @@ int trlda_anchor_read(trlda_anchor *c, const int32_t *rows, int n, double *out)
         if (rows[i] < 0 || rows[i] >= V)
             return fail(TRLDA_ERR_ARG, "row out of range");
     const size_t rb = (size_t)V * sizeof(double);
+    // (every row's copy is queued and the first failed status kept: the wait comes whatever they said,
+    // so nothing returns with a copy into `out` in flight)
+    hipError_t queued = hipSuccess;
     if (!rows && n > 0)
-        HIP_TRY(hipMemcpy2DAsync(out, rb, c->Q, (size_t)c->Vp * sizeof(double), rb, (size_t)n, hipMemcpyDeviceToHost,
-                                 m->stream));
-    for (int i = 0; rows && i < n; ++i)
-        HIP_TRY(hipMemcpyAsync(out + (size_t)i * V, c->Q + (size_t)rows[i] * c->Vp, rb, hipMemcpyDeviceToHost,
-                               m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return TRLDA_OK;
+        queued = hipMemcpy2DAsync(out, rb, c->Q, (size_t)c->Vp * sizeof(double), rb, (size_t)n,
+                                  hipMemcpyDeviceToHost, m->stream);
+    for (int i = 0; rows && i < n; ++i) {
+        const hipError_t e = hipMemcpyAsync(out + (size_t)i * V, c->Q + (size_t)rows[i] * c->Vp, rb,
+                                            hipMemcpyDeviceToHost, m->stream);
+        if (queued == hipSuccess)
+            queued = e;
+    }
+    return wait_for_copies(m, {queued});
 }
 
 int trlda_anchor_row_sums(trlda_anchor *c, double *r, double *total)
@@ -6128,9 +6180,7 @@ int trlda_anchor_row_sums(trlda_anchor *c, double *r, double *total)
         return rc;
     hipError_t e1 = hipMemcpyAsync(r, c->r, (size_t)c->V * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(total, c->total, sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 int trlda_anchor_set_gram_lds(trlda_anchor *c, int mode)
@@ -6161,8 +6211,8 @@ int trlda_anchor_select(trlda_anchor *c, int num, int64_t min_doc_freq, int32_t 
     HIP_TRY(hipGetLastError());
     std::vector<int> cand((size_t)V);
     hipError_t e1 = hipMemcpyAsync(cand.data(), c->cand, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
+    if ((rc = wait_for_copies(m, {e1})))
+        return rc;
     long long have = 0;
     for (int w = 0; w < V; ++w)
         have += cand[w];
@@ -6185,12 +6235,10 @@ int trlda_anchor_select(trlda_anchor *c, int num, int64_t min_doc_freq, int32_t 
             HIP_TRY(hipGetLastError());
         }
     }
-    hipError_t e3 = hipMemcpyAsync(ids, d_ids, (size_t)num * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipMemcpyAsync(score, d_sc, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e5 = hipMemcpyAsync(runner, d_sc + num, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e6 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6);
-    return TRLDA_OK;
+    hipError_t e2 = hipMemcpyAsync(ids, d_ids, (size_t)num * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e3 = hipMemcpyAsync(score, d_sc, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    hipError_t e4 = hipMemcpyAsync(runner, d_sc + num, (size_t)num * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    return wait_for_copies(m, {e2, e3, e4});
 }
 
 int trlda_anchor_recover(trlda_anchor *c, const int32_t *anchors, int A, double tol, int max_iter, double *beta,
@@ -6222,8 +6270,8 @@ int trlda_anchor_recover(trlda_anchor *c, const int32_t *anchors, int A, double 
         return rc;
     double total = 0.0;
     hipError_t t1 = hipMemcpyAsync(&total, c->total, sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t t2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(t1); HIP_TRY(t2);
+    if ((rc = wait_for_copies(m, {t1})))
+        return rc;
     if (!(total > 0.0))
         return fail(TRLDA_ERR_VALUE, "the co-occurrence matrix is empty");
     if ((rc = anchor_normalise(c)))
@@ -6236,6 +6284,8 @@ int trlda_anchor_recover(trlda_anchor *c, const int32_t *anchors, int A, double 
         (rc = small.alloc(1 + (size_t)A + V)))
         return rc;
     double *d_L = small, *d_pi = d_L + 1, *d_gap = d_pi + A;
+    // (not waited for here: every path from here on ends in wait_for_copies or in a DevBuf's hipFree,
+    // which waits for the device)
     HIP_TRY(hipMemcpyAsync(d_anc, anchors, (size_t)A * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(trlda::anchor_product_kernel, dim3((V + 63) / 64), dim3(T), trlda::tile_operands_lds(64),
                        m->stream, V, Vp, A, c->W.get(), d_anc.get(), H.get());
@@ -6273,9 +6323,7 @@ int trlda_anchor_recover(trlda_anchor *c, const int32_t *anchors, int A, double 
                           : hipSuccess;
     hipError_t e5 = gaps ? hipMemcpyAsync(gaps, d_gap, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, m->stream)
                          : hipSuccess;
-    hipError_t e6 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4); HIP_TRY(e5); HIP_TRY(e6);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2, e3, e4, e5});
 }
 
 int trlda_anchor_destroy(trlda_anchor *c)
@@ -8544,16 +8592,6 @@ int trlda_model_heldout_ranks(trlda_model *m, const trlda_batch *o, const trlda_
 
 namespace {
 
-int relevance_topn_check(const trlda_model *m, int top_n)
-{
-    if (top_n < 1 || top_n > trlda::kTopnMax || top_n > m->V)
-        return fail(TRLDA_ERR_ARG, "top_n must lie in [1, min(num_words, 100)]");
-    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    if (m->K > 65535 || tiles > 65535)                   // (grid dimensions y)
-        return fail(TRLDA_ERR_ARG, "num_topics or num_words too large for the top-word kernels");
-    return TRLDA_OK;
-}
-
 // the given topic weights, checked and normalised to sum 1 (in long double: one rounding each) into
 // `pi`; no weights: `pi` stays empty
 int relevance_weights(const trlda_model *m, const double *topic_weights, std::vector<double> &pi)
@@ -8591,12 +8629,8 @@ int relevance_coef(trlda_model *m, const std::vector<double> &pi)
     if (rc)
         return rc;
     HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(int), m->stream));
-    if (!pi.empty()) {
-        // (waited for here: `pi` is the caller's and need not outlive an early return)
-        hipError_t e1 = hipMemcpyAsync(g.pi, pi.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        HIP_TRY(e1); HIP_TRY(e2);
-    }
+    if (!pi.empty() && (rc = upload_waited(m, g.pi, pi.data(), (size_t)K * sizeof(double))))
+        return rc;
     hipLaunchKernelGGL(trlda::relevance_coef_kernel, dim3(1), dim3(trlda::kWave), 0, m->stream, K, rs,
                        pi.empty() ? (const double *)nullptr : (const double *)g.pi, g.coef.get());
     HIP_TRY(hipGetLastError());
@@ -8625,51 +8659,36 @@ int relevance_stats(trlda_model *m, const std::vector<double> &pi)
 int relevance_settle(trlda_model *m, const char *what = "relevance")
 {
     int flag = 0;
-    hipError_t e1 = hipMemcpyAsync(&flag, m->relevance.flag, sizeof(int), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    HIP_TRY(hipGetLastError());
+    int rc = read_flag(m, m->relevance.flag, &flag);
+    if (rc)
+        return rc;
     if (flag)
         return fail(TRLDA_ERR_VALUE, std::string(what) + " needs a positive, finite lambda");
     return TRLDA_OK;
 }
 
-// room for the selection of `rows` rows: the first level's candidates and the later levels'
-// (ping-pong) as in trlda_model_top_words, the ranked ids behind them, and the scores
-int relevance_select_room(trlda_model *m, int rows, int n, size_t &off_b, size_t &cap)
+// room for the selection of `rows` rows: the tree's keys and ids (topn_plan), the ranked ids behind
+// them, and the scores
+int relevance_select_room(trlda_model *m, const TopnPlan &p, int rows, int n)
 {
     auto &g = m->relevance;
-    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    const size_t c1 = (size_t)tiles * n;
-    const size_t c2 = (c1 + trlda::kTopnGroup - 1) / trlda::kTopnGroup * n;
-    off_b = (size_t)rows * c1;
-    cap = off_b + (size_t)rows * c2;
-    int rc = g.keys.grow(cap);
-    if (!rc) rc = g.ids.grow(cap + (size_t)rows * n);
+    int rc = g.keys.grow(p.cap);
+    if (!rc) rc = g.ids.grow(p.cap + (size_t)rows * n);
     if (!rc) rc = g.scores.grow((size_t)rows * n);
     return rc;
 }
 
-// the levels after the first: topn_merge_kernel while a row has more than 1024 candidates, then the
-// level that ranks and gives the scores (ids at relevance.ids + cap, scores at relevance.scores)
-int relevance_select_levels(trlda_model *m, int rows, int n, size_t off_b, size_t cap)
+// the levels after the first: the merges, then the level that ranks and gives the scores (ids at
+// relevance.ids + cap, scores at relevance.scores)
+int relevance_select_levels(trlda_model *m, const TopnPlan &p, int rows, int n)
 {
     auto &g = m->relevance;
-    const int tiles = (m->V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    uint64_t *ik = g.keys, *ok = g.keys + off_b;
-    int32_t *ii = g.ids, *oi = g.ids + off_b;
-    size_t c = (size_t)tiles * n;
-    while (c > (size_t)trlda::kTopnGroup) {
-        const size_t groups = (c + trlda::kTopnGroup - 1) / trlda::kTopnGroup;
-        hipLaunchKernelGGL(trlda::topn_merge_kernel, dim3((unsigned)groups, rows), dim3(trlda::kWave), 0,
-                           m->stream, n, (int)c, ik, ii, ok, oi, (int32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
-        std::swap(ik, ok);
-        std::swap(ii, oi);
-        c = groups * n;
-    }
+    size_t at = 0, c = 0;
+    int rc = topn_merge_levels(m, p, rows, n, g.keys, g.ids, at, c);
+    if (rc)
+        return rc;
     hipLaunchKernelGGL(trlda::relevance_final_kernel, dim3(rows), dim3(trlda::kWave), 0, m->stream, n, (int)c,
-                       ik, ii, g.ids + cap, g.scores.get());
+                       g.keys + at, g.ids + at, g.ids + p.cap, g.scores.get());
     HIP_TRY(hipGetLastError());
     return TRLDA_OK;
 }
@@ -8683,9 +8702,7 @@ int relevance_results(trlda_model *m, size_t cells, size_t cap, int32_t *words_o
     hipError_t e2 = scores_out ? hipMemcpyAsync(scores_out, g.scores, cells * sizeof(double),
                                                 hipMemcpyDeviceToHost, m->stream)
                                : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // namespace
@@ -8712,9 +8729,7 @@ int trlda_model_word_stats(trlda_model *m, const double *topic_weights, double *
     hipError_t e1 = hipMemcpyAsync(p_out, st, bytes, hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(distinct_out, st + V, bytes, hipMemcpyDeviceToHost, m->stream);
     hipError_t e3 = hipMemcpyAsync(saliency_out, st + 2 * V, bytes, hipMemcpyDeviceToHost, m->stream);
-    hipError_t e4 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2, e3});
 }
 
 int trlda_model_relevant_words(trlda_model *m, int top_n, double weight, const double *topic_weights,
@@ -8724,7 +8739,7 @@ int trlda_model_relevant_words(trlda_model *m, int top_n, double weight, const d
         return fail(TRLDA_ERR_ARG, "model is NULL");
     if (!words_out)
         return fail(TRLDA_ERR_ARG, "words_out is NULL");
-    if (int rc_arg = relevance_topn_check(m, top_n))
+    if (int rc_arg = topn_check(m, top_n))
         return rc_arg;
     if (!(weight >= 0.0 && weight <= 1.0))
         return fail(TRLDA_ERR_ARG, "weight must lie in [0, 1]");
@@ -8736,24 +8751,23 @@ int trlda_model_relevant_words(trlda_model *m, int top_n, double weight, const d
         return rc;
     auto &g = m->relevance;
     const int K = m->K, V = m->V, n = top_n;
-    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    size_t off_b = 0, cap = 0;
-    rc = relevance_select_room(m, K, n, off_b, cap);
+    const TopnPlan p = topn_plan(V, K, n);
+    rc = relevance_select_room(m, p, K, n);
     if (!rc) rc = relevance_stats(m, pi);
     if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::relevance_tile_kernel),
                                      (size_t)trlda::kRelevanceTileLds);
     if (rc)
         return rc;
     hipLaunchKernelGGL(trlda::relevance_tile_kernel,
-                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, tiles),
+                       dim3((K + trlda::kTopnTileTopics - 1) / trlda::kTopnTileTopics, p.tiles),
                        dim3(trlda::kTopnThreads), (size_t)trlda::kRelevanceTileLds, m->stream, K, V, n, 1.0 - weight,
                        m->lambda, g.coef + (size_t)K, g.stats + 3 * (size_t)V, g.keys.get(), g.ids.get());
     HIP_TRY(hipGetLastError());
-    rc = relevance_select_levels(m, K, n, off_b, cap);
+    rc = relevance_select_levels(m, p, K, n);
     if (!rc) rc = relevance_settle(m);
     if (rc)
         return rc;
-    return relevance_results(m, (size_t)K * n, cap, words_out, scores_out);
+    return relevance_results(m, (size_t)K * n, p.cap, words_out, scores_out);
 }
 
 int trlda_model_salient_words(trlda_model *m, int top_n, const double *topic_weights, int32_t *words_out,
@@ -8763,7 +8777,7 @@ int trlda_model_salient_words(trlda_model *m, int top_n, const double *topic_wei
         return fail(TRLDA_ERR_ARG, "model is NULL");
     if (!words_out)
         return fail(TRLDA_ERR_ARG, "words_out is NULL");
-    if (int rc_arg = relevance_topn_check(m, top_n))
+    if (int rc_arg = topn_check(m, top_n))
         return rc_arg;
     std::vector<double> pi;
     if (int rc_arg = relevance_weights(m, topic_weights, pi))
@@ -8773,23 +8787,22 @@ int trlda_model_salient_words(trlda_model *m, int top_n, const double *topic_wei
         return rc;
     auto &g = m->relevance;
     const int V = m->V, n = top_n;
-    const int tiles = (V + trlda::kTopnTileWords - 1) / trlda::kTopnTileWords;
-    size_t off_b = 0, cap = 0;
-    rc = relevance_select_room(m, 1, n, off_b, cap);
+    const TopnPlan p = topn_plan(V, 1, n);
+    rc = relevance_select_room(m, p, 1, n);
     if (!rc) rc = relevance_stats(m, pi);
     const size_t lds = (size_t)trlda::kTopnTileTopics * trlda::kTopnTileStride * sizeof(uint64_t);
     if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trlda::topn_tile_kernel), lds);
     if (rc)
         return rc;
     // (the 1 x V vector S as a one-topic lambda)
-    hipLaunchKernelGGL(trlda::topn_tile_kernel, dim3(1, tiles), dim3(trlda::kTopnThreads), lds, m->stream, 1, V, n,
+    hipLaunchKernelGGL(trlda::topn_tile_kernel, dim3(1, p.tiles), dim3(trlda::kTopnThreads), lds, m->stream, 1, V, n,
                        g.stats + 2 * (size_t)V, g.keys.get(), g.ids.get());
     HIP_TRY(hipGetLastError());
-    rc = relevance_select_levels(m, 1, n, off_b, cap);
+    rc = relevance_select_levels(m, p, 1, n);
     if (!rc) rc = relevance_settle(m);
     if (rc)
         return rc;
-    return relevance_results(m, (size_t)n, cap, words_out, saliency_out);
+    return relevance_results(m, (size_t)n, p.cap, words_out, saliency_out);
 }
 
 }  // extern "C"
@@ -8928,8 +8941,8 @@ int trlda_prevalence_read(trlda_prevalence *p, double *prevalence_out, int64_t *
     hipError_t e1 = hipMemcpyAsync(sums.data(), p->sums, (size_t)K * sizeof(double), hipMemcpyDeviceToHost,
                                    m->stream);
     hipError_t e2 = hipMemcpyAsync(&docs, p->docs, sizeof(long long), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    if ((rc = wait_for_copies(m, {e1, e2})))
+        return rc;
     *num_docs = docs;
     if (docs <= 0)
         return fail(TRLDA_ERR_VALUE, "prevalence: no document with a positive count has been added");
@@ -8964,7 +8977,7 @@ int trlda_model_word_diagnostics(trlda_model *m, int top_n, const double *topic_
         return fail(TRLDA_ERR_ARG, "model is NULL");
     if (!words || !eff_out || !entropy_out || !uniform_out || !corpus_out || !exclusivity_out)
         return fail(TRLDA_ERR_ARG, "NULL words / output");
-    if (int rc_arg = relevance_topn_check(m, top_n))
+    if (int rc_arg = topn_check(m, top_n))
         return rc_arg;
     std::vector<double> pi;
     if (int rc_arg = relevance_weights(m, topic_weights, pi))
@@ -8996,14 +9009,9 @@ int trlda_model_word_diagnostics(trlda_model *m, int top_n, const double *topic_
     if (!rc) rc = g.ratio.grow(cells);
     if (!rc) rc = g.words.grow(cells);
     if (!rc) rc = relevance_stats(m, pi);                // (the row sums, log R, log p and the flag)
+    if (!rc) rc = upload_waited(m, g.words, words, cells * sizeof(int32_t));
     if (rc)
         return rc;
-    {
-        // (waited for here: `words` is the caller's and need not outlive an early return)
-        hipError_t e1 = hipMemcpyAsync(g.words, words, cells * sizeof(int32_t), hipMemcpyHostToDevice, m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        HIP_TRY(e1); HIP_TRY(e2);
-    }
     constexpr int T = trlda::kRelevanceThreads;
     const double *rs = m->rowsums.rs;
     hipLaunchKernelGGL(trlda::diagnostics_scale_kernel, dim3((K + T - 1) / T), dim3(T), 0, m->stream, K, rs,
@@ -9030,8 +9038,8 @@ int trlda_model_word_diagnostics(trlda_model *m, int top_n, const double *topic_
     std::vector<double> sums(4 * (size_t)K);
     hipError_t e1 = hipMemcpyAsync(sums.data(), g.sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost,
                                    m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
+    if ((rc = wait_for_copies(m, {e1})))
+        return rc;
     const long double logV = logl((long double)V);
     for (int k = 0; k < K; ++k) {
         const double H = -sums[(size_t)K + k];
@@ -9179,8 +9187,8 @@ int trlda_topicdiag_read(trlda_topicdiag *p, double *tokens_out, double *entropy
                                    m->stream);
     hipError_t e2 = hipMemcpyAsync(counts.data(), p->counts, counts.size() * sizeof(long long),
                                    hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    if ((rc = wait_for_copies(m, {e1, e2})))
+        return rc;
     *num_docs = counts[3 * K];
     if (counts[3 * K] <= 0)
         return fail(TRLDA_ERR_VALUE, "topic diagnostics: no document with a positive count has been added");
@@ -9239,17 +9247,11 @@ int wordsim_check_ids(const trlda_model *m, const int32_t *word_ids, int B)
     return TRLDA_OK;
 }
 
-// the B query ids onto the device (waited for: they are the caller's)
+// the B query ids onto the device
 int wordsim_upload_ids(trlda_model *m, const int32_t *word_ids, int B)
 {
-    auto &g = m->wordsim;
-    int rc = g.ids.grow((size_t)B);
-    if (rc)
-        return rc;
-    hipError_t e1 = hipMemcpyAsync(g.ids, word_ids, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    return TRLDA_OK;
+    int rc = m->wordsim.ids.grow((size_t)B);
+    return rc ? rc : upload_waited(m, m->wordsim.ids, word_ids, (size_t)B * sizeof(int32_t));
 }
 
 // c (relevance_coef) and the column pass: every word's scale under `measure`, and the flag
@@ -9323,10 +9325,7 @@ int wordsim_rank(trlda_model *m, int B, int top_n, int measure, const double *qs
     const size_t cells = (size_t)B * top_n;
     hipError_t e1 = hipMemcpyAsync(words_out, g.out_w, cells * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream);
     hipError_t e2 = hipMemcpyAsync(sim_out, g.out_s, cells * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e3 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
-    HIP_TRY(hipGetLastError());
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1, e2});
 }
 
 }  // namespace
@@ -9402,14 +9401,8 @@ int trlda_model_similar_words_rows(trlda_model *m, const double *proportions, in
     const int K = m->K, Kp = (K + 3) / 4 * 4;
     rc = wordsim_room(m, B, top_n);
     if (!rc) rc = g.stage.grow(count);
-    if (rc)
-        return rc;
-    {
-        hipError_t e1 = hipMemcpyAsync(g.stage, proportions, count * sizeof(double), hipMemcpyHostToDevice, m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        HIP_TRY(e1); HIP_TRY(e2);
-    }
-    rc = wordsim_norms(m, pi, measure);
+    if (!rc) rc = upload_waited(m, g.stage, proportions, count * sizeof(double));
+    if (!rc) rc = wordsim_norms(m, pi, measure);
     if (rc)
         return rc;
     // (unit rows as the document index makes them: their scale is 1)
@@ -9455,9 +9448,7 @@ int trlda_model_word_topic_proportions(trlda_model *m, const int32_t *word_ids, 
     if (rc)
         return rc;
     hipError_t e1 = hipMemcpyAsync(out, g.stage, count * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    hipError_t e2 = hipStreamSynchronize(m->stream);
-    HIP_TRY(e1); HIP_TRY(e2);
-    return TRLDA_OK;
+    return wait_for_copies(m, {e1});
 }
 
 }  // extern "C"
@@ -9565,8 +9556,8 @@ int trlda_model_topic_distances(trlda_model *m, trlda_model *other, const double
                        stream, K, K2, (int)chunks, measure, self ? 1 : 0, part.get(), sa, sb, out.get());
     HIP_TRY(hipGetLastError());
     hipError_t e1 = hipMemcpyAsync(dist_out, out, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-    hipError_t e2 = hipStreamSynchronize(stream);
-    HIP_TRY(e1); HIP_TRY(e2);
+    if ((rc = wait_for_copies(m, {e1})))                 // (stream is m's)
+        return rc;
     m->d2h_bytes += (int64_t)(n * sizeof(double));
     return TRLDA_OK;
 }
